@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: LightningDiT-B/1 (f8d16) flow-matching TRAIN STEP throughput on synthetic 32x32x16 latents.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (images/s, ms_per_step).  --full adds everything else
+the benchmark measures: the roofline / HBM blocks, the H2D-inclusive loop, package power, the CPU baseline and, at N = 1 and batch 256,
+the extra workloads (BASELINE configs 4 and 5, the tokenizer paths, sampling, CelebA-HQ, drop-in, data-parallel).  --dump-outputs DIR
+writes what the last timed step computed (dump_outputs below) as .npy files; the inputs and initial weights are seeded, so two builds
+can be compared output for output.
 
 N > 1: either the driver starts the ranks (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...: RANK /
 LOCAL_RANK / WORLD_SIZE in the environment), or -- WORLD_SIZE unset -- bench.py starts them itself the same way (the parent never
@@ -481,8 +487,28 @@ def bench_dp_config(args, device, launch_modes=("tile", "persistent")):
     return res
 
 
+DUMP_SAMPLE = 1 << 20             # slab positions kept per dumped array: 4 MB each in float32
+
+
+def dump_outputs(out_dir, loss, opt):
+    """--dump-outputs: what the last timed step hands its caller -- the loss, and the state it updated: parameters, EMA, AdamW moments and
+    the gradients it computed.  Each slab holds every trainable float of the model (~130 M for B/1), so one fixed, seeded sample of
+    DUMP_SAMPLE positions, the same in every file and every run, stands for it (5 x 4 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    f = opt.flat
+    n = f.n_trainable
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(f.params.device)
+    arrays = {"loss": np.array([loss.detach().double().item()], dtype=np.float64)}
+    for name, slab in (("params", f.params), ("ema", opt.ema), ("grads", f.grads), ("adam_m", opt.m), ("adam_v", opt.v)):
+        arrays[name] = slab[idx].float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def bench_dit(args, world, rank, device, lib, backend):
     from ldmae_amd import ops
+    torch.manual_seed(0)                         # the default init of the weights not re-drawn in build(): the same model every run
     model, opt, reducer, transport = build(device, args.batch)
     # world > 1: one tile per workgroup or persistent, a per-call flag of the C ABI (LDMAE_DP_GEMM_LAUNCH; default = what --dp-config measured)
     ops.set_gemm_launch_mode(os.environ.get("LDMAE_DP_GEMM_LAUNCH", reducer.recommended_gemm_launch_mode()) if world > 1 else "persistent")
@@ -496,8 +522,10 @@ def bench_dit(args, world, rank, device, lib, backend):
     for _ in range(min(2, args.warmup)):
         step()
     reducer.exposed_comm_ms()                                  # drop warm-up samples
-    with PowerSampler(enabled=rank == 0 and not args.no_power, device_index=device.index or 0) as ps:
+    with PowerSampler(enabled=args.full and rank == 0 and not args.no_power, device_index=device.index or 0) as ps:
         elapsed, loss = timed_loop(step, args.steps, max(0, args.warmup - 2), world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, opt)             # before anything below runs another step on the same model
     exposed = reducer.exposed_comm_ms() / max(1, args.steps + max(0, args.warmup - 2))
     if world > 1:
         tt = torch.tensor([elapsed], device=device if backend == "nccl" else "cpu", dtype=torch.float64)
@@ -506,28 +534,29 @@ def bench_dit(args, world, rank, device, lib, backend):
     final_loss = float(loss.item())
     if not np.isfinite(final_loss):
         raise RuntimeError("non-finite loss in bench")
-    # SURVEY 8(d) defines the step from the H2D of the batch: a second, short loop hands every step a FRESH batch from pinned host memory
-    # (16.8 MB per 256 latents, async copy on the compute stream).  Reported beside `value`, which keeps its inputs resident in HBM.
-    hsteps = max(2, min(10, args.steps))
-    xh = [torch.randn(args.batch, 16, 32, 32).pin_memory() for _ in range(2)]
-    yh = [torch.randint(0, 1000, (args.batch,)).pin_memory() for _ in range(2)]
-    cnt = [0]
-
-    def step_h2d():
-        i = cnt[0] & 1
-        cnt[0] += 1
-        return train_step(model, opt, reducer, transport, xh[i].to(device, non_blocking=True), yh[i].to(device, non_blocking=True))
-    el_h, _ = timed_loop(step_h2d, hsteps, 1, world)
-    reducer.exposed_comm_ms()
     timeline = None
-    if world > 1 and reducer.overlap:
-        # one more step with per-bucket events: when backward released each bucket, how long its all-reduce took, how much ran past backward
-        reducer.measure_timeline = True
-        step()
-        torch.cuda.synchronize()
-        timeline = reducer.bucket_timeline()
-        reducer.measure_timeline = False
-    roof = gemm_roofline(lib, step)
+    if args.full:
+        # SURVEY 8(d) defines the step from the H2D of the batch: a second, short loop hands every step a FRESH batch from pinned host memory
+        # (16.8 MB per 256 latents, async copy on the compute stream).  Reported beside `value`, which keeps its inputs resident in HBM.
+        hsteps = max(2, min(10, args.steps))
+        xh = [torch.randn(args.batch, 16, 32, 32).pin_memory() for _ in range(2)]
+        yh = [torch.randint(0, 1000, (args.batch,)).pin_memory() for _ in range(2)]
+        cnt = [0]
+
+        def step_h2d():
+            i = cnt[0] & 1
+            cnt[0] += 1
+            return train_step(model, opt, reducer, transport, xh[i].to(device, non_blocking=True), yh[i].to(device, non_blocking=True))
+        el_h, _ = timed_loop(step_h2d, hsteps, 1, world)
+        reducer.exposed_comm_ms()
+        if world > 1 and reducer.overlap:
+            # one more step with per-bucket events: when backward released each bucket, how long its all-reduce took, how much ran past backward
+            reducer.measure_timeline = True
+            step()
+            torch.cuda.synchronize()
+            timeline = reducer.bucket_timeline()
+            reducer.measure_timeline = False
+        roof = gemm_roofline(lib, step)
     if rank != 0:
         return None
     ips = args.batch * world * args.steps / elapsed
@@ -539,21 +568,24 @@ def bench_dit(args, world, rank, device, lib, backend):
                                "latents 32x32x16", "per_gpu_batch": args.batch, "global_batch": args.batch * world,
                    "parallelism": f"dp{world}", "loss": round(final_loss, 5)},
         "step_mfma_frac": round(FLOPS_PER_IMAGE * ips / world / (PEAK_BF16_TFLOPS * 1e12), 4),
-        "roofline": roof,
-        "hbm": hbm_block(args.batch),
-        "h2d_inclusive": {"ms_per_step": round(el_h / hsteps * 1e3, 3), "images_per_s": round(args.batch * world * hsteps / el_h, 2), "steps": hsteps,
-                          "note": "same step with a fresh pinned-host batch copied H2D (non_blocking) every step, SURVEY 8(d); rank 0 clock"},
-        "power": ps.summary(),
     }
-    # the whole step against the peak at the clock it held: the mean shader clock sampled in process during the timed loop when the sensor is
-    # readable, else the committed PMC run's clock of the dominant kernel (labelled either way)
-    held, src = None, None
-    if out["power"] and out["power"].get("sclk_mhz_mean"):
-        held, src = out["power"]["sclk_mhz_mean"] / 1e3, "power.sclk_mhz_mean (sysfs, this run's timed loop)"
-    elif roof.get("clock_ghz"):
-        held, src = roof["clock_ghz"], "roofline.clock_ghz (committed PMC run, NT GEMM)"
-    out["step_mfma_frac_at_held_clock"] = round(out["step_mfma_frac"] * NOMINAL_CLOCK_GHZ / held, 4) if held else None
-    out["held_clock_ghz"], out["held_clock_source"] = (round(held, 3), src) if held else (None, None)
+    if args.full:
+        out.update({
+            "roofline": roof,
+            "hbm": hbm_block(args.batch),
+            "h2d_inclusive": {"ms_per_step": round(el_h / hsteps * 1e3, 3), "images_per_s": round(args.batch * world * hsteps / el_h, 2), "steps": hsteps,
+                              "note": "same step with a fresh pinned-host batch copied H2D (non_blocking) every step, SURVEY 8(d); rank 0 clock"},
+            "power": ps.summary(),
+        })
+        # the whole step against the peak at the clock it held: the mean shader clock sampled in process during the timed loop when the sensor is
+        # readable, else the committed PMC run's clock of the dominant kernel (labelled either way)
+        held, src = None, None
+        if out["power"] and out["power"].get("sclk_mhz_mean"):
+            held, src = out["power"]["sclk_mhz_mean"] / 1e3, "power.sclk_mhz_mean (sysfs, this run's timed loop)"
+        elif roof.get("clock_ghz"):
+            held, src = roof["clock_ghz"], "roofline.clock_ghz (committed PMC run, NT GEMM)"
+        out["step_mfma_frac_at_held_clock"] = round(out["step_mfma_frac"] * NOMINAL_CLOCK_GHZ / held, 4) if held else None
+        out["held_clock_ghz"], out["held_clock_source"] = (round(held, 3), src) if held else (None, None)
     if world > 1:
         out["comm"] = {"backend": "rccl" if backend == "nccl" else backend, "rccl_ranks": world if backend == "nccl" else 0,
                        "grad_bytes_per_step": int(opt.flat.n_trainable) * 4, "buckets": len(reducer.buckets),
@@ -561,7 +593,7 @@ def bench_dit(args, world, rank, device, lib, backend):
                        "gemm_launch_mode": "one tile per workgroup" if ops.gemm_launch_mode() == "tile" else "persistent",
                        "batched_adaln": bool(model._use_batched_adaln()) if hasattr(model, "_use_batched_adaln") else None,
                        "bucket_timeline_rank0": timeline}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     return out
 
@@ -848,7 +880,15 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="dit workload at N=1: skip the vmae / xl_sample / dp_config lines under extra_workloads")
     ap.add_argument("--dropin-config", action="store_true", help="N=1: time the drop-in mode (stock AdamW, the reference's EMA loop, autograd-delivered gradients) and print that line")
     ap.add_argument("--dp-config", action="store_true", help="N=1: time the data-parallel program (world-1 RCCL group, reducer hooks + side stream live) and print that line")
+    ap.add_argument("--full", action="store_true",
+                    help="dit workload: also measure what the headline figure does not need (roofline / hbm, h2d_inclusive, power, cpu_baseline, "
+                         "extra_workloads); off = setup, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="dit workload: write what the last timed step computed (loss; seeded samples of the parameter, EMA, gradient and AdamW "
+                         "moment slabs) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "dit" or args.dropin_config or args.dp_config):
+        ap.error("--dump-outputs is for the headline dit workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
@@ -899,7 +939,7 @@ def main():
         out = {"metric": "DiT-B train step in the data-parallel configuration on one MI355X (ms per step)", "dp_config": bench_dp_config(args, device)}
     elif args.workload == "dit":
         out = bench_dit(args, world, rank, device, lib, backend)
-        if world == 1 and not args.no_extra and args.batch == 256:
+        if args.full and world == 1 and not args.no_extra and args.batch == 256:
             # BASELINE configs 4 and 5 on the same box, AFTER the timed headline region (its model and activations are freed first), so
             # that the driver's one record carries them; each is the line `--workload vmae` / `--workload xl_sample` prints on its own
             free_gpu_memory()

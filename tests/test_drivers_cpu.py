@@ -56,7 +56,10 @@ def test_latent_dataset_roundtrip(tmp_path):
 def test_latent_dataset_matches_reference_golden(tmp_path):
     """SURVEY 8(f)3 pinned: shards rebuilt from the golden inputs, then our ImgLatentDataset under the same numpy / torch seeds must
     reproduce what the reference's class returned (tests/golden/make_golden.py:gen_dataset imports it): cached stats (np.random.choice
-    pick + posterior sample), the per-item flip pick (np.random.uniform), posterior sample (torch.randn), normalisation, multiplier."""
+    pick + posterior sample), the per-item flip pick (np.random.uniform), posterior sample (torch.randn), normalisation, multiplier.
+    Bitwise, except where the posterior sample's torch.exp enters (tag "a"): on the CPU that call goes through MKL, whose code path depends on
+    the host's CPU vendor and ISA, and MKL's paths differ in the last bits (up to ~1e-6 in these values).  A wrong flip pick, noise draw or
+    normalisation moves values by O(0.1-1), far above the 1e-5 allowed there."""
     from safetensors.torch import save_file
     sys.path.insert(0, os.path.join(ROOT, "ldmae_amd"))
     from ldmae_amd.datasets.img_latent_dataset import ImgLatentDataset
@@ -72,10 +75,11 @@ def test_latent_dataset_matches_reference_golden(tmp_path):
         torch.manual_seed(7)
         ds = ImgLatentDataset(str(d), **kw)
         assert len(ds) == 8
+        same = (lambda a, b: np.allclose(a, b, rtol=1e-5, atol=1e-5)) if kw["sample"] else np.array_equal     # host libm exp: see above
         if kw["latent_norm"]:
-            assert np.array_equal(ds._latent_mean.numpy(), g[f"ds_{tag}_mean"]) and np.array_equal(ds._latent_std.numpy(), g[f"ds_{tag}_std"])
+            assert same(ds._latent_mean.numpy(), g[f"ds_{tag}_mean"]) and same(ds._latent_std.numpy(), g[f"ds_{tag}_std"])
         items = [ds[int(i)] for i in g[f"ds_{tag}_order"]]
-        assert np.array_equal(torch.stack([x for x, _ in items]).numpy(), g[f"ds_{tag}_feat"])
+        assert same(torch.stack([x for x, _ in items]).numpy(), g[f"ds_{tag}_feat"])
         assert np.array_equal(torch.stack([y for _, y in items]).numpy(), g[f"ds_{tag}_label"])
 
 
