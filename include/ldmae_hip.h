@@ -336,6 +336,23 @@ int ldmae_mae_loss_fwd(const float* pred_img, const float* imgs, const float* ma
 int ldmae_mae_loss_bwd(const float* pred_img, const float* imgs, const float* mask, const float* coef, float* dpred_img, int B, int C, int H, int W,
                        int p, void* stream);
 
+/* ---- FID evaluation: pytorch-fid's Inception-v3 (reference tools/calculate_fid.py:64-425), NHWC f32 -------------------------------
+ * conv2d: implicit-GEMM convolution on the exact-f32 MFMA.  x [B, H, W, ldx] read at channels [xoff, xoff + Cin); w [Cout, kh, kw, Cin]
+ * (K = kh*kw*Cin contiguous per output channel); out [B, Ho, Wo, ldo] written at channels [ooff, ooff + Cout), Ho = (H + 2 ph - kh) / sh + 1;
+ * zero padding ph / pw; epilogue out = bias (may be NULL) + x (*) w, then max(., 0) when relu != 0 (BatchNorm folded into w and b).
+ * pool2d: mode 0 = max over the in-image taps of a k x k window, mode 1 = average over them (count_include_pad=False); same channel-slice
+ * conventions, C channels.  global_avgpool: out [B, C] = mean over HW pixels of x [B, HW, ldx] at channels [xoff, xoff + C).
+ * fid_preprocess: uint8 [B, H, W, 3] RGB -> out [B, Ho, Wo, 3] = F.interpolate(img / 255, (Ho, Wo), bilinear, align_corners=False) * 2 - 1.
+ * fid_stats_accumulate: sum[d] += sum_r (f[r, d] - shift[d]); cross[i, j] += sum_r (f[r, i] - shift[i]) (f[r, j] - shift[j]); f [n, D] f32,
+ * sum / cross f64 on the device, accumulated across calls (the caller zeroes them once). */
+int ldmae_conv2d_nhwc_f32(const float* x, int ldx, int xoff, const float* w, const float* bias, float* out, int ldo, int ooff, int B, int H, int W,
+                          int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int relu, void* stream);
+int ldmae_pool2d_nhwc_f32(int mode, const float* x, int ldx, int xoff, float* out, int ldo, int ooff, int B, int H, int W, int C, int k, int stride,
+                          int pad, void* stream);
+int ldmae_global_avgpool_nhwc_f32(const float* x, int ldx, int xoff, float* out, int B, int HW, int C, void* stream);
+int ldmae_fid_preprocess(const unsigned char* img, float* out, int B, int H, int W, int Ho, int Wo, void* stream);
+int ldmae_fid_stats_accumulate(const float* feats, int n, int D, const float* shift, double* sum, double* cross, void* stream);
+
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */
 int ldmae_prof_enable(int on);

@@ -103,6 +103,11 @@ SIGNATURES = {
     "ldmae_conv3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ldmae_conv3x3_bwd_workspace_bytes": (_l, [_i]),
     "ldmae_conv3x3_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ldmae_conv2d_nhwc_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_pool2d_nhwc_f32": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_global_avgpool_nhwc_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
+    "ldmae_fid_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_fid_stats_accumulate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

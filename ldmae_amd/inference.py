@@ -248,9 +248,25 @@ def main(argv=None):
         raise SystemExit(f"PRECISION={precision!r}: the sampler runs in bf16 or fp32")
     folder = do_sample(c, a.ckpt or c['ckpt_path'], a.out, demo=a.demo, precision=precision)
     if not a.demo and int(os.environ.get("RANK", 0)) == 0:
-        # inference.py:352-367 goes on to an Inception FID against data.fid_reference_file (tools/calculate_fid.py); that needs the Inception
-        # weights, which this package does not carry (evaluation tools are out of scope)
-        print(f"samples written to {folder}; FID (tools/calculate_fid.py in the reference) is not part of this package")
+        # inference.py:352-367: an Inception FID of the samples against data.fid_reference_file (tools/calculate_fid.py -> ldmae_amd.fid), run
+        # when that file exists (a relative path is taken from the working directory) and the user's Inception weights resolve
+        from . import fid as fid_mod
+        ref = c['data'].get('fid_reference_file')
+        missing = []
+        if not ref or not os.path.exists(ref):
+            missing.append(f"data.fid_reference_file {ref!r} does not exist")
+        try:
+            fid_mod.resolve_weights()
+        except FileNotFoundError as e:
+            missing.append(str(e))
+        if missing:
+            print(f"samples written to {folder}; FID (tools/calculate_fid.py in the reference) is not part of this package")
+            print("FID skipped: " + "; ".join(missing))
+        else:
+            print(f"Calculating FID with {c['sample']['fid_num']} number of samples")
+            fid = fid_mod.calculate_fid_given_paths([ref, folder], batch_size=50, device='cuda', dims=2048, num_workers=8,
+                                                    sp_len=c['sample']['fid_num'])
+            print('fid=', fid)
     return folder
 
 

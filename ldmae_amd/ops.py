@@ -880,3 +880,82 @@ def gelu_tanh_bwd(dout, pre):
     dx = torch.empty_like(pre)
     call("ldmae_gelu_tanh_bwd", dt(pre.dtype), ptr(_c(dout)), ptr(pre), ptr(dx), pre.numel(), stream())
     return dx
+
+
+# ----------------------------------------------------------------------------- FID evaluation (csrc/inception.hip), NHWC f32
+# A channel slice is (tensor [B, H, W, Ctot], offset, C): the kernels read / write channels [offset, offset + C) of every pixel.
+
+def _nhwc(t, what):
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: need a contiguous f32 NHWC tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def conv2d_nhwc(x, w, bias=None, stride=(1, 1), padding=(0, 0), relu=True, xoff=0, cin=None, out=None, ooff=0):
+    """Implicit-GEMM convolution on the exact-f32 MFMA.  x [B, H, W, ldx] read at channels [xoff, xoff + cin); w [Cout, kh, kw, Cin] f32;
+    out [B, Ho, Wo, ldo] written at channels [ooff, ooff + Cout) (allocated as [B, Ho, Wo, Cout] when None); bias + ReLU epilogue."""
+    _nhwc(x, "conv2d_nhwc")
+    B, H, W, ldx = x.shape
+    Cout, kh, kw, Cin = w.shape
+    cin = Cin if cin is None else cin
+    if cin != Cin or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError(f"conv2d_nhwc: weight {tuple(w.shape)} {w.dtype} does not match {cin} input channels")
+    sh, sw = stride
+    ph, pw = padding
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    if out is None:
+        out = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+    _nhwc(out, "conv2d_nhwc")
+    if tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise RuntimeError(f"conv2d_nhwc: output {tuple(out.shape)} is not [{B}, {Ho}, {Wo}, *]")
+    call("ldmae_conv2d_nhwc_f32", ptr(x), ldx, xoff, ptr(w), ptr(bias), ptr(out), out.shape[3], ooff, B, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw,
+         1 if relu else 0, stream())
+    return out
+
+
+def pool2d_nhwc(x, mode, k=3, stride=1, pad=0, xoff=0, c=None, out=None, ooff=0):
+    """3x3-style pooling of channel slices: mode "max" (padding never wins) or "avg" (count_include_pad=False)."""
+    _nhwc(x, "pool2d_nhwc")
+    B, H, W, ldx = x.shape
+    c = ldx - xoff if c is None else c
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if out is None:
+        out = torch.empty(B, Ho, Wo, c, dtype=torch.float32, device=x.device)
+    _nhwc(out, "pool2d_nhwc")
+    if tuple(out.shape[:3]) != (B, Ho, Wo):
+        raise RuntimeError(f"pool2d_nhwc: output {tuple(out.shape)} is not [{B}, {Ho}, {Wo}, *]")
+    call("ldmae_pool2d_nhwc_f32", {"max": 0, "avg": 1}[mode], ptr(x), ldx, xoff, ptr(out), out.shape[3], ooff, B, H, W, c, k, stride, pad, stream())
+    return out
+
+
+def global_avgpool_nhwc(x, xoff=0, c=None):
+    """[B, H, W, ldx] (or [B, HW, ldx]) -> [B, c]: the mean over all pixels of channels [xoff, xoff + c)."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() not in (3, 4):
+        raise RuntimeError(f"global_avgpool_nhwc: need a contiguous f32 [B, H, W, C] or [B, HW, C] tensor, got {tuple(x.shape)} {x.dtype}")
+    B, ldx = x.shape[0], x.shape[-1]
+    HW = x[0, ..., 0].numel()
+    c = ldx - xoff if c is None else c
+    out = torch.empty(B, c, dtype=torch.float32, device=x.device)
+    call("ldmae_global_avgpool_nhwc_f32", ptr(x), ldx, xoff, ptr(out), B, HW, c, stream())
+    return out
+
+
+def fid_preprocess(img, size=299):
+    """uint8 [B, H, W, 3] RGB -> f32 [B, size, size, 3] = F.interpolate(img / 255, (size, size), bilinear, align_corners=False) * 2 - 1."""
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
+        raise RuntimeError(f"fid_preprocess: need a contiguous uint8 [B, H, W, 3] tensor, got {tuple(img.shape)} {img.dtype}")
+    B, H, W, _ = img.shape
+    out = torch.empty(B, size, size, 3, dtype=torch.float32, device=img.device)
+    call("ldmae_fid_preprocess", ptr(img), ptr(out), B, H, W, size, size, stream())
+    return out
+
+
+def fid_stats_accumulate(feats, shift, s1, s2):
+    """s1 [D] += sum_r (f_r - shift); s2 [D, D] += sum_r (f_r - shift)(f_r - shift)^T, f64 accumulators on the device."""
+    if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
+        raise RuntimeError(f"fid_stats_accumulate: need contiguous f32 [n, D] features, got {tuple(feats.shape)} {feats.dtype}")
+    n, D = feats.shape
+    if shift.shape != (D,) or shift.dtype != torch.float32 or s1.shape != (D,) or s2.shape != (D, D) or s1.dtype != torch.float64 \
+            or s2.dtype != torch.float64 or not s2.is_contiguous():
+        raise RuntimeError("fid_stats_accumulate: shift must be f32 [D], the accumulators f64 [D] and [D, D]")
+    call("ldmae_fid_stats_accumulate", ptr(feats), n, D, ptr(shift), ptr(s1), ptr(s2), stream())
