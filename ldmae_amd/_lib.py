@@ -166,7 +166,8 @@ def call(name, *args):
 
 
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL).  Tensors must be CUDA/HIP and contiguous."""
+    """Device pointer of a tensor (None -> NULL); raises for a tensor off the HIP device.  The LAYOUT is not checked here: the address
+    is that of the first element, and the strides the kernel assumes are the caller's to guarantee (ops.py checks them per argument)."""
     if t is None:
         return None
     if not t.is_cuda:

@@ -35,6 +35,44 @@ def _c(t):
     return t if t is None or t.is_contiguous() else t.contiguous()
 
 
+def _arg(t, what, dtype=None, shape=None, rows=False, out=False, numel=None):
+    """Layout check of one tensor handed to a GEMM-family entry point (attributes only: no synchronisation, no device work).
+    rows=True: the kernel reads it row by row with a leading dimension (t.stride(0)): elements of a row must be adjacent, rows may be
+    further apart (a row slice of a wider buffer stays zero-copy).  rows=False: the kernel reads it densely.  An input of another layout
+    is copied; an output (out=True) must already have the layout, else RuntimeError.  dtype / shape mismatches always raise; numel= checks
+    the element count of a dense operand the kernel addresses as a flat [rows, N] block whatever its torch shape."""
+    if t is None:
+        return None
+    if dtype is not None and t.dtype != dtype:
+        raise RuntimeError(f"{what}: dtype {t.dtype}, expected {dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if numel is not None and t.numel() != numel:
+        raise RuntimeError(f"{what}: {t.numel()} elements (shape {tuple(t.shape)}), expected {numel}")
+    if rows:
+        ok = t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+    else:
+        ok = t.is_contiguous()
+    if ok:
+        return t
+    if out:
+        form = "rows with adjacent elements (stride(1) == 1, stride(0) >= columns)" if rows else "a contiguous tensor"
+        raise RuntimeError(f"{what}: the kernel writes {form}; got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _ld(t):
+    """Leading dimension of a 2-D tensor that passed _arg(rows=True) (a single row: its length)."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _pair(a, b, what):
+    """The two operands of an NT product: same dtype, same K; both read as rows."""
+    if b.dtype != a.dtype or a.dim() != 2 or b.dim() != 2 or b.shape[1] != a.shape[1]:
+        raise RuntimeError(f"{what}: operands {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype} must be [M,K] and [N,K] of one dtype")
+    return _arg(a, what + " a", rows=True), _arg(b, what + " b", rows=True)
+
+
 # ----------------------------------------------------------------------------- side stream for weight gradients
 _side = {}
 
@@ -123,12 +161,15 @@ def _grad_flag(dtype, grad) -> int:
 
 def gemm_nt(a, b, bias=None, out_dtype=None, out=None, beta=0.0, grad=False):
     """out[M,N] = a[M,K] @ b[N,K]^T + bias (+ beta*out)."""
+    a, b = _pair(a, b, "gemm_nt")
     M, K = a.shape
     N = b.shape[0]
-    out_dtype = out_dtype or a.dtype
+    bias = _arg(bias, "gemm_nt bias", torch.float32, (N,))
     if out is None:
-        out = torch.empty(M, N, dtype=out_dtype, device=a.device)
-    call("ldmae_gemm_nt", dt(a.dtype), dt(out.dtype), EPI_BIAS | _launch_flag() | _grad_flag(out.dtype, grad), ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0),
+        out = torch.empty(M, N, dtype=out_dtype or a.dtype, device=a.device)
+    else:
+        _arg(out, "gemm_nt out", out_dtype, (M, N), rows=True, out=True)
+    call("ldmae_gemm_nt", dt(a.dtype), dt(out.dtype), EPI_BIAS | _launch_flag() | _grad_flag(out.dtype, grad), ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), _ld(out),
          M, N, K, ptr(bias), float(beta), None, None, None, 0, 0, stream())
     return out
 
@@ -137,34 +178,47 @@ def gemm_nt_gate_res(a, b, bias, xin, gate, rows_per_batch, save_y=True, xout=No
     """y = a @ b^T + bias ; xout = xin + gate[batch] * y.  Returns (xout, y or None).  gate: [B, D] view (any row stride).
     The residual adds y ROUNDED to `y_dtype` (default: the activation type -- what the reference's autocast Linear hands to
     `x + gate * branch`, lightningdit.py:248-249); y_dtype=float32 with save_y=False adds the unrounded product."""
+    a, b = _pair(a, b, "gemm_nt_gate_res")
     M, K = a.shape
     N = b.shape[0]
+    if rows_per_batch <= 0 or M % rows_per_batch:
+        raise RuntimeError(f"gemm_nt_gate_res: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
+    bias = _arg(bias, "gemm_nt_gate_res bias", torch.float32, (N,))
+    xin = _arg(xin, "gemm_nt_gate_res xin", torch.float32, numel=M * N)
+    gate = _arg(gate, "gemm_nt_gate_res gate", torch.float32, (M // rows_per_batch, N), rows=True)
     y_dtype = y_dtype or a.dtype
     y = torch.empty(M, N, dtype=y_dtype, device=a.device) if save_y else None
     if xout is None:
-        xout = torch.empty_like(xin)
-    call("ldmae_gemm_nt", dt(a.dtype), dt(y_dtype), EPI_GATE_RES | _launch_flag(), ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(y), N,
-         M, N, K, ptr(bias), 0.0, ptr(xin), ptr(xout), ptr(gate), gate.stride(0) if gate is not None else 0, rows_per_batch, stream())
+        xout = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    else:
+        _arg(xout, "gemm_nt_gate_res xout", torch.float32, out=True, numel=M * N)
+    call("ldmae_gemm_nt", dt(a.dtype), dt(y_dtype), EPI_GATE_RES | _launch_flag(), ptr(a), _ld(a), ptr(b), _ld(b), ptr(y), N,
+         M, N, K, ptr(bias), 0.0, ptr(xin), ptr(xout), ptr(gate), _ld(gate) if gate is not None else 0, rows_per_batch, stream())
     return xout, y
 
 
 def gemm_nt_pos(a, b, bias, pos, rows_per_batch):
     """out = a @ b^T + bias + pos[row % rows_per_batch]   (f32 out; patch embed)."""
+    a, b = _pair(a, b, "gemm_nt_pos")
     M, K = a.shape
     N = b.shape[0]
+    bias = _arg(bias, "gemm_nt_pos bias", torch.float32, (N,))
+    pos = _arg(pos, "gemm_nt_pos pos", torch.float32, numel=rows_per_batch * N)
     out = torch.empty(M, N, dtype=torch.float32, device=a.device)
-    call("ldmae_gemm_nt", dt(a.dtype), F32, EPI_BIAS_POS | _launch_flag(), ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), N,
+    call("ldmae_gemm_nt", dt(a.dtype), F32, EPI_BIAS_POS | _launch_flag(), ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), N,
          M, N, K, ptr(bias), 0.0, ptr(pos), None, None, 0, rows_per_batch, stream())
     return out
 
 
 def gemm_nt_gelu(a, b, bias, save_pre=True):
     """(gelu(a @ b^T + bias), pre-activation or None)."""
+    a, b = _pair(a, b, "gemm_nt_gelu")
     M, K = a.shape
     N = b.shape[0]
+    bias = _arg(bias, "gemm_nt_gelu bias", torch.float32, (N,))
     out = torch.empty(M, N, dtype=a.dtype, device=a.device)
     pre = torch.empty_like(out) if save_pre else None
-    call("ldmae_gemm_nt", dt(a.dtype), dt(a.dtype), EPI_BIAS_GELU | _launch_flag(), ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), N,
+    call("ldmae_gemm_nt", dt(a.dtype), dt(a.dtype), EPI_BIAS_GELU | _launch_flag(), ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), N,
          M, N, K, ptr(bias), 0.0, None, ptr(pre), None, 0, 0, stream())
     return out, pre
 
@@ -172,10 +226,12 @@ def gemm_nt_gelu(a, b, bias, save_pre=True):
 def gemm_nt_gelu_bwd(dy, w2t, pre):
     """dpre = gelu_bwd(dy @ w2t^T, pre): the input gradient of fc2 with the GELU backward in the GEMM's epilogue (w2t = [hidden, D] transposed
     copy of fc2's weight; pre = fc1's pre-activation as gemm_nt_gelu saved it).  Same bits as gelu_bwd(gemm_nt(dy, w2t), pre)."""
+    dy, w2t = _pair(dy, w2t, "gemm_nt_gelu_bwd")
     M, K = dy.shape
     N = w2t.shape[0]
+    pre = _arg(pre, "gemm_nt_gelu_bwd pre", dy.dtype, numel=M * N)          # read with C's row stride N
     out = torch.empty(M, N, dtype=dy.dtype, device=dy.device)
-    call("ldmae_gemm_nt", dt(dy.dtype), dt(dy.dtype), EPI_GELU_BWD | _launch_flag() | _grad_flag(dy.dtype, True), ptr(dy), dy.stride(0), ptr(w2t), w2t.stride(0), ptr(out), N,
+    call("ldmae_gemm_nt", dt(dy.dtype), dt(dy.dtype), EPI_GELU_BWD | _launch_flag() | _grad_flag(dy.dtype, True), ptr(dy), _ld(dy), ptr(w2t), _ld(w2t), ptr(out), N,
          M, N, K, None, 0.0, ptr(pre), None, None, 0, 0, stream())
     return out
 
@@ -184,12 +240,14 @@ def gemm_nt_swiglu(a, w12, b12, save_h12=True):
     """(h12, hid): h12 = a @ w12^T + b12 ([x1 | x2]), hid = silu(x1) * x2.  bf16: one GEMM with the SwiGLU epilogue;
     otherwise the GEMM followed by ldmae_swiglu_fwd (same numbers: the epilogue rounds to bf16 before the activation).
     save_h12=False (forward-only; bf16 path): h12, which only the backward pass reads, is not stored and None is returned for it."""
+    a, w12 = _pair(a, w12, "gemm_nt_swiglu")
     M, K = a.shape
     N = w12.shape[0]
+    b12 = _arg(b12, "gemm_nt_swiglu bias", torch.float32, (N,))
     if a.dtype == torch.bfloat16 and N % 256 == 0 and K % 64 == 0:
         h12 = torch.empty(M, N, dtype=a.dtype, device=a.device) if save_h12 else None
         hid = torch.empty(M, N // 2, dtype=a.dtype, device=a.device)
-        call("ldmae_gemm_nt", BF16, BF16, EPI_SWIGLU | _launch_flag(), ptr(a), a.stride(0), ptr(w12), w12.stride(0), ptr(h12), N, M, N, K, ptr(b12), 0.0,
+        call("ldmae_gemm_nt", BF16, BF16, EPI_SWIGLU | _launch_flag(), ptr(a), _ld(a), ptr(w12), _ld(w12), ptr(h12), N, M, N, K, ptr(b12), 0.0,
              None, ptr(hid), None, 0, 0, stream())
         return h12, hid
     h12 = gemm_nt(a, w12, b12)
@@ -204,7 +262,7 @@ def gemm_nt_qkv_rope_ok(a, w, B, N, H, hd):
     LDMAE_FUSED_QKV=0 keeps the GEMM + ldmae_qknorm_rope_fwd pair (A/B runs; bitwise the same q2 / k2)."""
     if a.dtype != torch.bfloat16 or not FUSED_QKV or _HALF_LINES:
         return False
-    if a.data_ptr() % 128 or w.data_ptr() % 128 or w.shape[0] != 3 * H * hd:
+    if a.data_ptr() % 128 or w.data_ptr() % 128 or w.shape[0] != 3 * H * hd or a.stride(1) != 1 or w.stride(1) != 1:
         return False
     return bool(L.load().ldmae_gemm_nt_qkv_rope_ok(B, N, H, hd, a.shape[1], a.stride(0), w.stride(0)))
 
@@ -213,11 +271,13 @@ def gemm_nt_qkv_rope(a, w, bias, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, store_
     """(qkv, q2, k2): the qkv Linear with q_norm / k_norm / RoPE applied in its epilogue (lightningdit.py:68-74 in one kernel).  qkv [B*N, 3*H*hd] as
     gemm_nt writes it (store_raw_qk=False -- forward-only: only the v third is written, the q / k thirds stay uninitialised), q2 / k2 [B, H, N, hd] bitwise
     what qknorm_rope_fwd makes of the stored q / k.  wq = wk = None: RoPE only.  Call gemm_nt_qkv_rope_ok first."""
+    a, w = _pair(a, w, "gemm_nt_qkv_rope")
     M, K = a.shape
+    bias = _arg(bias, "gemm_nt_qkv_rope bias", torch.float32, (3 * H * hd,))
     qkv = torch.empty(M, 3 * H * hd, dtype=a.dtype, device=a.device)
     q2 = torch.empty(B, H, N, hd, dtype=a.dtype, device=a.device)
     k2 = torch.empty_like(q2)
-    call("ldmae_gemm_nt_qkv_rope", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), ptr(qkv), ptr(q2), ptr(k2), ptr(wq), ptr(wk), ptr(cos), ptr(sin),
+    call("ldmae_gemm_nt_qkv_rope", ptr(a), _ld(a), ptr(w), _ld(w), ptr(bias), ptr(qkv), ptr(q2), ptr(k2), ptr(wq), ptr(wk), ptr(cos), ptr(sin),
          B, N, H, hd, K, eps, 1 if store_raw_qk else 0, 1 if (_launch_flag() & EPI_TILE_LAUNCH) else 0, stream())
     return qkv, q2, k2
 
@@ -225,14 +285,16 @@ def gemm_nt_qkv_rope(a, w, bias, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, store_
 def gemm_nt_swiglu_bwd(dy, w3t, h12, with_bias=False):
     """dh12 = swiglu_bwd(dy @ w3t^T, h12)   (w3t = [Hs, D] transposed copy of w3).  with_bias: also the column sums of dh12 (the
     bias gradient of w12), formed in the GEMM epilogue as per-128-row partials and summed here."""
+    dy, w3t = _pair(dy, w3t, "gemm_nt_swiglu_bwd")
     M, K = dy.shape
     Hs = w3t.shape[0]
+    h12 = _arg(h12, "gemm_nt_swiglu_bwd h12", dy.dtype, numel=M * 2 * Hs)
     if dy.dtype == torch.bfloat16 and Hs % 8 == 0 and K % 64 == 0:
-        dh12 = torch.empty_like(h12)
+        dh12 = torch.empty(h12.shape, dtype=dy.dtype, device=dy.device)
         # every (128-row group, column) of the partial-sum matrix is written by exactly one wave when the tile grid is whole: no 33 MB fill
         whole = M % 128 == 0 and Hs % 64 == 0
         part = (torch.empty if whole else torch.zeros)((M + 127) // 128, 2 * Hs, dtype=torch.float32, device=dy.device) if with_bias else None
-        call("ldmae_gemm_nt", BF16, BF16, EPI_SWIGLU_BWD | _launch_flag(), ptr(dy), dy.stride(0), ptr(w3t), w3t.stride(0), ptr(dh12), 2 * Hs, M, Hs, K, None, 0.0,
+        call("ldmae_gemm_nt", BF16, BF16, EPI_SWIGLU_BWD | _launch_flag(), ptr(dy), _ld(dy), ptr(w3t), _ld(w3t), ptr(dh12), 2 * Hs, M, Hs, K, None, 0.0,
              ptr(h12), ptr(part), None, 0, 0, stream())
         return (dh12, colsum(part)) if with_bias else dh12
     dh12 = swiglu_bwd(gemm_nt(dy, w3t), h12)
@@ -243,38 +305,47 @@ def gemm_tn(a, b, out=None, beta=0.0, with_bias=False, ws_slot="tn", dbias_out=N
     """out[N,K] (f32) = beta*out + a[M,N]^T @ b[M,K]   (weight gradient).  with_bias: also return the column sums of `a`
     (the bias gradient of the same Linear), fused into the same kernel on the bf16 path.  dbias_out (f32 [N], contiguous): the bias gradient
     is accumulated THERE under the same beta as `out` (a .grad slab view: no fresh zero-filled buffer, no add afterwards)."""
+    if b.dtype != a.dtype or a.dim() != 2 or b.dim() != 2 or b.shape[0] != a.shape[0]:
+        raise RuntimeError(f"gemm_tn: operands {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype} must be [M,N] and [M,K] of one dtype")
+    a, b = _arg(a, "gemm_tn a", rows=True), _arg(b, "gemm_tn b", rows=True)
     M, N = a.shape
     K = b.shape[1]
     if out is None:
         out = torch.empty(N, K, dtype=torch.float32, device=a.device)
         beta = 0.0
+    else:
+        _arg(out, "gemm_tn out", torch.float32, (N, K), out=True)
     if dbias_out is not None:
-        if not with_bias or dbias_out.dtype != torch.float32 or dbias_out.numel() != N or not dbias_out.is_contiguous():
+        if not with_bias:
             raise RuntimeError("gemm_tn: dbias_out must be a contiguous f32 [N] buffer and needs with_bias=True")
-        dbias = dbias_out
+        dbias = _arg(dbias_out, "gemm_tn dbias_out", torch.float32, (N,), out=True)
     else:
         # the C entry applies ONE beta to C and to dbias: a fresh bias-gradient buffer must be zero when the caller accumulates into `out`
         dbias = (torch.zeros if beta != 0.0 else torch.empty)(N, dtype=torch.float32, device=a.device) if with_bias else None
     d = dt(a.dtype)
     nb = max(L.load().ldmae_gemm_tn_workspace_bytes(d, M, N, K), L.load().ldmae_colsum_workspace_bytes(M, N) if with_bias else 0)
     ws = workspace(nb, a.device, ws_slot)
-    call("ldmae_gemm_tn", d, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), ptr(dbias), M, N, K, float(beta), ptr(ws), ws.numel() * 4,
+    call("ldmae_gemm_tn", d, ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), ptr(dbias), M, N, K, float(beta), ptr(ws), ws.numel() * 4,
          stream())
     return (out, dbias) if with_bias else out
 
 
 def colsum(x, out=None, beta=0.0):
+    x = _arg(x, "colsum x", rows=True)
     M, N = x.shape
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=x.device)
         beta = 0.0
+    else:
+        _arg(out, "colsum out", torch.float32, (N,), out=True)
     ws = workspace(L.load().ldmae_colsum_workspace_bytes(M, N), x.device, "colsum")
-    call("ldmae_colsum", dt(x.dtype), ptr(x), x.stride(0), M, N, ptr(out), float(beta), ptr(ws), stream())
+    call("ldmae_colsum", dt(x.dtype), ptr(x), _ld(x), M, N, ptr(out), float(beta), ptr(ws), stream())
     return out
 
 
 def cast_weight(w, dtype, transposed=True, straight=True):
     """f32 master weight [R,C] -> (copy in `dtype` or None, [C,R] transposed copy or None)."""
+    w = _arg(w, "cast_weight w", torch.float32)
     R, C = w.shape
     dst = torch.empty(R, C, dtype=dtype, device=w.device) if straight else None
     dstT = torch.empty(C, R, dtype=dtype, device=w.device) if transposed else None
@@ -302,8 +373,11 @@ def thin_nt(t, w, bias=None, pos=None, rows_per_batch=0, out_dtype=torch.float32
     """out[M,N] = t[M,K] @ w[N,K]^T + bias (+ pos[row % rows_per_batch]) for K = 16 / 32, f32 inputs; one streaming pass."""
     M, K = t.shape
     N = w.shape[0]
+    t, w = _arg(t, "thin_nt t", torch.float32), _arg(w, "thin_nt w", torch.float32, (N, K))
+    bias = _arg(bias, "thin_nt bias", torch.float32, (N,))
+    pos = _arg(pos, "thin_nt pos", torch.float32, numel=rows_per_batch * N)
     out = torch.empty(M, N, dtype=out_dtype, device=t.device)
-    call("ldmae_thin_nt", dt(out_dtype), ptr(_c(t)), ptr(_c(w)), ptr(bias), ptr(_c(pos)) if pos is not None else None, ptr(out), M, N, K,
+    call("ldmae_thin_nt", dt(out_dtype), ptr(t), ptr(w), ptr(bias), ptr(pos), ptr(out), M, N, K,
          int(rows_per_batch), stream())
     return out
 
@@ -312,10 +386,11 @@ def thin_tn(g, t, with_bias=True):
     """(dW[N,K] = g[M,N]^T @ t[M,K], column sums of g or None) for K = 16 / 32, f32; one pass over g."""
     M, N = g.shape
     K = t.shape[1]
+    g, t = _arg(g, "thin_tn g", torch.float32), _arg(t, "thin_tn t", torch.float32, (M, K))
     dW = torch.empty(N, K, dtype=torch.float32, device=g.device)
     db = torch.empty(N, dtype=torch.float32, device=g.device) if with_bias else None
     ws = workspace(L.load().ldmae_thin_tn_workspace_bytes(M, N, K), g.device)
-    call("ldmae_thin_tn", ptr(_c(g)), ptr(_c(t)), ptr(dW), ptr(db), M, N, K, 0.0, ptr(ws), ws.numel() * 4, stream())
+    call("ldmae_thin_tn", ptr(g), ptr(t), ptr(dW), ptr(db), M, N, K, 0.0, ptr(ws), ws.numel() * 4, stream())
     return dW, db
 
 
