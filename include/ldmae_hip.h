@@ -353,6 +353,31 @@ int ldmae_global_avgpool_nhwc_f32(const float* x, int ldx, int xoff, float* out,
 int ldmae_fid_preprocess(const unsigned char* img, float* out, int B, int H, int W, int Ho, int Wo, void* stream);
 int ldmae_fid_stats_accumulate(const float* feats, int n, int D, const float* shift, double* sum, double* cross, void* stream);
 
+/* ---- ADM evaluator: Inception Score, sFID, precision and recall (reference tools/evaluator.py), f32 --------------------------------
+ * adm_preprocess: uint8 [B, H, W, 3] -> out [B, Ho, Wo, 3] = (TF1 legacy ResizeBilinear(img) - 128) / 128 (align_corners = False, no
+ * half-pixel centres: src = dst * in / out, hi = min(lo + 1, in - 1); the rule is written out in csrc/adm_eval.hip).
+ * adm_spatial_tap: out [B, HW * C] = x [B, HW, ldx] at channels [xoff, xoff + C), flattened (pixel, channel) = TF's NHWC reshape.
+ * row_sqnorms_f32: out [M] = sum_d x[m, d]^2 of x [M, D], accumulated in f64, rounded to f32 once.
+ * pairwise_logits: out [M, N] = u [M, D] . w [N, D]^T (no bias) on the exact-f32 MFMA.
+ * knn_radii: d(i, j) = max(|x_i|^2 - 2 x_i.x_j + |x_j|^2, 0) over x [N, D] with norms [N]; radii [N, nk] = the value at sorted index
+ * nhood[t] (0..7, self-distance included) of row i.  Columns are cut into nsplit ranges of whole 64-column tiles; partials (float,
+ * knn_partials_bytes(N, nsplit) bytes) hold per-range lists.  The result does not depend on nsplit, bit for bit.
+ * pr_flags: the same d between u [M, D] and v [N, D]; u_in [M, nk] = 1 where some j has d(i, j) <= rv[j, k], v_in [N, nk] = 1 where some
+ * i has d(i, j) <= ru[i, k]; the caller zeroes u_in / v_in; only 1s are stored.
+ * adm_softmax_is: p = softmax(logits [M, C]) in f32; h [M] = sum_c p log p (f64, 0 log 0 = 0); S [ceil(M / split), C] = sum of p over
+ * each split of `split` consecutive rows (f64, fixed order).  workspace: adm_is_workspace_bytes(M, C, split) bytes. */
+int ldmae_adm_preprocess(const unsigned char* img, float* out, int B, int H, int W, int Ho, int Wo, void* stream);
+int ldmae_adm_spatial_tap(const float* x, int ldx, int xoff, float* out, int B, int HW, int C, void* stream);
+int ldmae_row_sqnorms_f32(const float* x, int M, int D, float* out, void* stream);
+int ldmae_pairwise_logits(const float* u, int M, int D, const float* w, int N, float* out, void* stream);
+long ldmae_knn_partials_bytes(int M, int nsplit);
+int ldmae_knn_radii(const float* x, const float* norms, int N, int D, const int* nhood, int nk, int nsplit, float* partials, float* radii,
+                    void* stream);
+int ldmae_pr_flags(const float* u, const float* nu, const float* ru, int M, const float* v, const float* nv, const float* rv, int N, int D, int nk,
+                   int nsplit, int* u_in, int* v_in, void* stream);
+long ldmae_adm_is_workspace_bytes(int M, int C, int split);
+int ldmae_adm_softmax_is(const float* logits, int M, int C, int split, void* workspace, double* h, double* S, void* stream);
+
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */
 int ldmae_prof_enable(int on);

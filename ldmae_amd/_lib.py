@@ -108,6 +108,15 @@ SIGNATURES = {
     "ldmae_global_avgpool_nhwc_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
     "ldmae_fid_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ldmae_fid_stats_accumulate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "ldmae_adm_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_adm_spatial_tap": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
+    "ldmae_row_sqnorms_f32": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ldmae_pairwise_logits": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "ldmae_knn_partials_bytes": (_l, [_i, _i]),
+    "ldmae_knn_radii": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "ldmae_pr_flags": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ldmae_adm_is_workspace_bytes": (_l, [_i, _i, _i]),
+    "ldmae_adm_softmax_is": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

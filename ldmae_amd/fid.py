@@ -211,6 +211,8 @@ class InceptionFID:
             for blk, (a, b) in FUSED_1X1.items():
                 folded[f"{blk}.fused_1x1"] = (torch.cat([folded[a][0], folded[b][0]]), torch.cat([folded[a][1], folded[b][1]]))
         self.params = {k: (w.to(self.device), b.to(self.device)) for k, (w, b) in folded.items()}
+        self._fc_weight_src = state_dict.get("fc.weight")      # the ADM softmax graph's weight (adm_logits_weight); not used by features()
+        self._fc_weight = None
 
     # ---------------------------------------------------------------- building blocks
     def _conv(self, name, x, xoff=0, out=None, ooff=0):
@@ -300,15 +302,45 @@ class InceptionFID:
         return out
 
     # ---------------------------------------------------------------- forward
-    @torch.no_grad()
-    def features(self, images):
-        """uint8 [B, H, W, 3] RGB (host or device) -> f32 [B, dims] on the device."""
+    def _uint8_images(self, images, what):
         if not isinstance(images, torch.Tensor):
             images = torch.from_numpy(np.ascontiguousarray(images))
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
-            raise ValueError(f"features() takes uint8 [B, H, W, 3] RGB images, got {tuple(images.shape)} {images.dtype}")
+            raise ValueError(f"{what}() takes uint8 [B, H, W, 3] RGB images, got {tuple(images.shape)} {images.dtype}")
+        return images.to(self.device, non_blocking=True).contiguous()
+
+    @torch.no_grad()
+    def features(self, images):
+        """uint8 [B, H, W, 3] RGB (host or device) -> f32 [B, dims] on the device."""
+        return self._forward(self._ops.fid_preprocess(self._uint8_images(images, "features")))
+
+    @torch.no_grad()
+    def adm_features(self, images):
+        """The ADM evaluator's two tensors in one forward (reference tools/evaluator.py:24,601-615): uint8 [B, H, W, 3] RGB ->
+        (pool f32 [B, 2048], spatial f32 [B, 2023]) on the device.  Pre-processing is the TF graph's (ops.adm_preprocess), not
+        pytorch-fid's; pool is TF pool_3 (the global average of Mixed_7c); spatial is TF mixed_6/conv[..., :7] = channels 0..6 of Mixed_6d's
+        branch1x1 after BatchNorm + ReLU (TF mixed_4..mixed_7 are Mixed_6b..6e), flattened in NHWC order: index (h * 17 + w) * 7 + c."""
+        if self.block != 3:
+            raise ValueError(f"adm_features() needs the full network (dims=2048), this model has dims={self.dims}")
+        taps = []
+        pool = self._forward(self._ops.adm_preprocess(self._uint8_images(images, "adm_features")), taps)
+        return pool, taps[0]
+
+    def adm_logits_weight(self):
+        """fc.weight [1008, 2048] f32 on the device: the ADM softmax graph's MatMul weight (softmax/logits/MatMul; no bias is added).
+        KeyError if the state dict had no fc.weight, ValueError on a wrong shape."""
+        if self._fc_weight is None:
+            w = self._fc_weight_src
+            if w is None:
+                raise KeyError("Inception state dict lacks fc.weight [1008, 2048], which the Inception Score needs")
+            if tuple(w.shape) != (1008, 2048):
+                raise ValueError(f"Inception state dict: fc.weight has shape {tuple(w.shape)}, expected (1008, 2048)")
+            self._fc_weight = w.detach().float().contiguous().to(self.device)
+        return self._fc_weight
+
+    def _forward(self, x, taps=None):
+        """Pre-processed f32 [B, 299, 299, 3] -> f32 [B, dims]; taps (a list) receives Mixed_6d's sFID tap [B, 17 * 17 * 7]."""
         ops = self._ops
-        x = ops.fid_preprocess(images.to(self.device, non_blocking=True).contiguous())
         x = self._conv("Conv2d_1a_3x3", x)
         x = self._conv("Conv2d_2a_3x3", x)
         x = self._conv("Conv2d_2b_3x3", x)
@@ -325,6 +357,8 @@ class InceptionFID:
         x = self._block_b(x)
         for blk in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
             x = self._block_c(blk, x)
+            if taps is not None and blk == "Mixed_6d":
+                taps.append(ops.adm_spatial_tap(x, 0, 7))      # branch1x1 is written at channel offset 0 of the block output
         if self.block == 2:
             return ops.global_avgpool_nhwc(x)
         x = self._block_d(x)

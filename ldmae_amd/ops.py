@@ -6,6 +6,7 @@ PyTorch: if the library is missing, or a tensor is on the CPU, they raise.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import weakref
 
@@ -1034,3 +1035,130 @@ def fid_stats_accumulate(feats, shift, s1, s2):
             or s2.dtype != torch.float64 or not s2.is_contiguous():
         raise RuntimeError("fid_stats_accumulate: shift must be f32 [D], the accumulators f64 [D] and [D, D]")
     call("ldmae_fid_stats_accumulate", ptr(feats), n, D, ptr(shift), ptr(s1), ptr(s2), stream())
+
+
+# ----------------------------------------------------------------------------- ADM evaluator (csrc/adm_eval.hip), f32
+def _rows_f32(t, what, cols=None):
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
+        want = f"[*, {cols}]" if cols is not None else "[rows, D]"
+        raise RuntimeError(f"{what}: need a contiguous f32 {want} tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def adm_preprocess(img, size=299):
+    """uint8 [B, H, W, 3] RGB -> f32 [B, size, size, 3] = (TF1 legacy ResizeBilinear(img) - 128) / 128: the ADM Inception graph's
+    pre-processing (src = dst * in / out, no half-pixel centres)."""
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
+        raise RuntimeError(f"adm_preprocess: need a contiguous uint8 [B, H, W, 3] tensor, got {tuple(img.shape)} {img.dtype}")
+    B, H, W, _ = img.shape
+    out = torch.empty(B, size, size, 3, dtype=torch.float32, device=img.device)
+    call("ldmae_adm_preprocess", ptr(img), ptr(out), B, H, W, size, size, stream())
+    return out
+
+
+def adm_spatial_tap(x, xoff=0, c=7):
+    """[B, H, W, ldx] -> f32 [B, H * W * c]: channels [xoff, xoff + c) of every pixel, flattened in (h, w, c) order (TF's NHWC reshape)."""
+    _nhwc(x, "adm_spatial_tap")
+    B, H, W, ldx = x.shape
+    if xoff < 0 or c <= 0 or xoff + c > ldx:
+        raise RuntimeError(f"adm_spatial_tap: channel slice [{xoff}, {xoff + c}) of {ldx}")
+    out = torch.empty(B, H * W * c, dtype=torch.float32, device=x.device)
+    call("ldmae_adm_spatial_tap", ptr(x), ldx, xoff, ptr(out), B, H * W, c, stream())
+    return out
+
+
+def row_sqnorms(x):
+    """f32 [M, D] -> f32 [M]: |x_m|^2 accumulated in f64, rounded once."""
+    _rows_f32(x, "row_sqnorms")
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    call("ldmae_row_sqnorms_f32", ptr(x), x.shape[0], x.shape[1], ptr(out), stream())
+    return out
+
+
+def pairwise_logits(u, w):
+    """u [M, D] . w [N, D]^T -> f32 [M, N] on the exact-f32 MFMA, no bias (the ADM softmax graph's MatMul)."""
+    _rows_f32(u, "pairwise_logits u")
+    _rows_f32(w, "pairwise_logits w", u.shape[1])
+    out = torch.empty(u.shape[0], w.shape[0], dtype=torch.float32, device=u.device)
+    call("ldmae_pairwise_logits", ptr(u), u.shape[0], u.shape[1], ptr(w), w.shape[0], ptr(out), stream())
+    return out
+
+
+def _pair_tiles(n):
+    return (n + 127) // 128, (n + 63) // 64
+
+
+def default_col_splits(m, n):
+    """Column splits of a pairwise pass: enough (row tile, split) workgroups to fill the chip (~2048), at most one per 64-column tile."""
+    row_tiles, col_tiles = _pair_tiles(m)[0], _pair_tiles(n)[1]
+    return max(1, min(col_tiles, -(-2048 // row_tiles)))
+
+
+def _nhood(nhood_sizes):
+    nh = [int(k) for k in nhood_sizes]
+    if not nh or len(nh) > 8 or min(nh) < 0 or max(nh) > 7:
+        raise RuntimeError(f"nhood_sizes {tuple(nhood_sizes)}: 1..8 sizes, each in [0, 7]")
+    return nh
+
+
+def knn_radii(x, nhood_sizes=(3,), norms=None, nsplit=None):
+    """f32 [N, D] -> f32 [N, len(nhood_sizes)]: column t is the value at sorted index nhood_sizes[t] of the row's squared distances
+    max(|x_i|^2 - 2 x_i.x_j + |x_j|^2, 0) to every row (itself included), as np.partition(d, seq)[:, k].  nsplit: column splits of the
+    pass (default default_col_splits); the result is bitwise the same for every nsplit."""
+    _rows_f32(x, "knn_radii")
+    N, D = x.shape
+    nh = _nhood(nhood_sizes)
+    if N <= max(nh):
+        raise RuntimeError(f"knn_radii: {N} rows hold no neighbour at sorted index {max(nh)}")
+    norms = row_sqnorms(x) if norms is None else norms
+    if norms.dtype != torch.float32 or tuple(norms.shape) != (N,) or not norms.is_contiguous():
+        raise RuntimeError(f"knn_radii: norms must be contiguous f32 [{N}], got {tuple(norms.shape)} {norms.dtype}")
+    nsplit = default_col_splits(N, N) if nsplit is None else int(nsplit)
+    if nsplit < 1:
+        raise RuntimeError(f"knn_radii: nsplit {nsplit} (>= 1)")
+    nbytes = L.load().ldmae_knn_partials_bytes(N, nsplit)
+    part = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    radii = torch.empty(N, len(nh), dtype=torch.float32, device=x.device)
+    arr = (ctypes.c_int * len(nh))(*nh)
+    call("ldmae_knn_radii", ptr(x), ptr(norms), N, D, arr, len(nh), nsplit, ptr(part), ptr(radii), stream())
+    return radii
+
+
+def pr_flags(u, ru, v, rv, nu=None, nv=None, nsplit=None):
+    """Manifold membership between u [M, D] (radii ru [M, K]) and v [N, D] (radii rv [N, K]): (u_in [M, K], v_in [N, K]) int32, with
+    u_in[i, k] = any_j d(i, j) <= rv[j, k] and v_in[j, k] = any_i d(i, j) <= ru[i, k] (evaluator.py DistanceBlock.less_thans)."""
+    _rows_f32(u, "pr_flags u")
+    _rows_f32(v, "pr_flags v", u.shape[1])
+    M, D = u.shape
+    N = v.shape[0]
+    K = ru.shape[1] if ru.dim() == 2 else -1
+    _rows_f32(ru, "pr_flags ru")
+    _rows_f32(rv, "pr_flags rv", K)
+    if ru.shape[0] != M or rv.shape[0] != N or not 1 <= K <= 8:
+        raise RuntimeError(f"pr_flags: radii {tuple(ru.shape)} / {tuple(rv.shape)} do not match {M} / {N} rows (1..8 columns)")
+    nu = row_sqnorms(u) if nu is None else nu
+    nv = row_sqnorms(v) if nv is None else nv
+    for t, n, what in ((nu, M, "nu"), (nv, N, "nv")):
+        if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise RuntimeError(f"pr_flags: {what} must be contiguous f32 [{n}], got {tuple(t.shape)} {t.dtype}")
+    nsplit = default_col_splits(M, N) if nsplit is None else int(nsplit)
+    if nsplit < 1:
+        raise RuntimeError(f"pr_flags: nsplit {nsplit} (>= 1)")
+    u_in = torch.zeros(M, K, dtype=torch.int32, device=u.device)
+    v_in = torch.zeros(N, K, dtype=torch.int32, device=u.device)
+    call("ldmae_pr_flags", ptr(u), ptr(nu), ptr(ru), M, ptr(v), ptr(nv), ptr(rv), N, D, K, nsplit, ptr(u_in), ptr(v_in), stream())
+    return u_in, v_in
+
+
+def adm_softmax_is(logits, split=5000):
+    """logits f32 [M, C] -> (h f64 [M], S f64 [ceil(M / split), C]): h[i] = sum_c p log p (0 log 0 = 0), S[s] = sum of p over rows
+    [s * split, (s + 1) * split), p = softmax(logits) in f32; fixed-order sums (bitwise reproducible)."""
+    _rows_f32(logits, "adm_softmax_is")
+    M, Cc = logits.shape
+    if split < 1:
+        raise RuntimeError(f"adm_softmax_is: split {split} (>= 1)")
+    ws = workspace(L.load().ldmae_adm_is_workspace_bytes(M, Cc, split), logits.device, "adm_is")
+    h = torch.empty(M, dtype=torch.float64, device=logits.device)
+    S = torch.empty(-(-M // split), Cc, dtype=torch.float64, device=logits.device)
+    call("ldmae_adm_softmax_is", ptr(logits), M, Cc, split, ptr(ws), ptr(h), ptr(S), stream())
+    return h, S

@@ -1,0 +1,114 @@
+"""Timings of the ADM evaluator's metric arithmetic on one MI355X, on synthetic features (no Inception weights needed):
+  - manifold_radii (k-NN radii, nhood (3,)) at N = 10 000 and 50 000, D = 2048: ms and TF/s at 2 N^2 D FLOP per pass;
+  - evaluate_pr for 10 000 reference x 50 000 sample features: ms and TF/s at 2 N1 N2 D FLOP;
+  - the softmax / Inception Score path for 50 000 rows (logits GEMM against a [1008, 2048] weight + softmax sums);
+  - images/s of InceptionFID.adm_features at batch 250 (random weights in the real layout, 256 x 256 uint8 images);
+  - as a YARDSTICK ONLY (not part of the package): the same radii with torch.cdist + kthvalue on the GPU, in row blocks.
+
+    python tools/bench_adm_eval.py [--iters 3] [--no-torch] [--json OUT]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from ldmae_amd import evaluator as ev, fid, ops  # noqa: E402
+
+
+def timed(fn, iters, warmup=1):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters
+
+
+def features(n, d, seed):
+    """Post-ReLU-like clustered features on the device; every set shares the same 256 cluster centres."""
+    centers = torch.rand(256, d, device="cuda", generator=torch.Generator(device="cuda").manual_seed(12345))
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    idx = torch.randint(0, 256, (n,), device="cuda", generator=g)
+    return (centers[idx] + 0.3 * torch.rand(n, d, device="cuda", generator=g)).contiguous()
+
+
+def torch_radii(x, k=3, rows=2048):
+    out = torch.empty(x.shape[0], device=x.device)
+    for i in range(0, x.shape[0], rows):
+        d = torch.cdist(x[i:i + rows], x).square_()
+        out[i:i + rows] = d.kthvalue(k + 1, dim=1).values
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    D = 2048
+    res = {"device": torch.cuda.get_device_name(0)}
+
+    def say(s):
+        print(s, flush=True)
+
+    f10, f50 = features(10_000, D, 0), features(50_000, D, 1)
+    for name, x in (("10k", f10), ("50k", f50)):
+        n = x.shape[0]
+        t = timed(lambda: ops.knn_radii(x, (3,)), a.iters)
+        tf = 2.0 * n * n * D / t / 1e12
+        res[f"radii_{name}_ms"], res[f"radii_{name}_tflops"] = t * 1e3, tf
+        say(f"manifold_radii N={n:6d} D={D}: {t * 1e3:9.2f} ms  {tf:6.1f} TF/s  (nsplit {ops.default_col_splits(n, n)})")
+    r10, r50 = ops.knn_radii(f10, (3,)), ops.knn_radii(f50, (3,))
+    t = timed(lambda: ops.pr_flags(f10, r10, f50, r50), a.iters)
+    tf = 2.0 * 10_000 * 50_000 * D / t / 1e12
+    res["pr_10k_50k_ms"], res["pr_10k_50k_tflops"] = t * 1e3, tf
+    say(f"evaluate_pr 10000 x 50000 D={D}: {t * 1e3:9.2f} ms  {tf:6.1f} TF/s")
+    in1, in2 = ops.pr_flags(f10, r10, f50, r50)
+    say(f"  (synthetic precision {float(in2.float().mean()):.4f}, recall {float(in1.float().mean()):.4f})")
+
+    w = (torch.randn(1008, D, device="cuda") * 0.02).contiguous()
+
+    def is_path():
+        h, S = ops.adm_softmax_is(ops.pairwise_logits(f50, w), 5000)
+        return ev.inception_score_from_sums(h.cpu().numpy(), S.cpu().numpy(), f50.shape[0], 5000)
+    t = timed(is_path, a.iters)
+    tl = timed(lambda: ops.pairwise_logits(f50, w), a.iters)
+    res["is_50k_ms"], res["logits_50k_ms"] = t * 1e3, tl * 1e3
+    say(f"softmax / IS path 50000 rows: {t * 1e3:9.2f} ms  (logits GEMM {tl * 1e3:.2f} ms, {2.0 * 50_000 * 1008 * D / tl / 1e12:.1f} TF/s)")
+
+    sd = fid.random_state_dict(0)
+    sd["fc.weight"] = torch.randn(1008, D) * 0.02
+    model = fid.InceptionFID(dims=2048, state_dict=sd)
+    imgs = torch.randint(0, 256, (250, 256, 256, 3), dtype=torch.uint8, device="cuda")
+    t = timed(lambda: model.adm_features(imgs), a.iters)
+    res["adm_features_img_s"] = 250 / t
+    say(f"adm_features batch 250 (256x256 -> 299): {250 / t:8.0f} images/s")
+
+    total = res["radii_10k_ms"] + res["radii_50k_ms"] + res["pr_10k_50k_ms"] + res["is_50k_ms"]
+    res["metrics_50k_vs_10k_ms"] = total
+    say(f"metric arithmetic of a 50k-sample / 10k-reference evaluation (2 radii passes + PR + IS): {total:.1f} ms")
+
+    if not a.no_torch:
+        try:
+            t = timed(lambda: torch_radii(f10), a.iters)
+            ok = bool(torch.allclose(torch_radii(f10), ops.knn_radii(f10, (3,))[:, 0], rtol=1e-3, atol=1e-3))
+            res["yardstick_torch_cdist_kthvalue_10k_ms"] = t * 1e3
+            say(f"[yardstick only] torch.cdist + kthvalue radii N=10000: {t * 1e3:9.2f} ms  (agrees to 1e-3: {ok})")
+        except RuntimeError as e:          # the yardstick is optional: torch's own kernels may be missing on this machine
+            say(f"[yardstick only] torch.cdist + kthvalue not run: {e}")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
