@@ -378,6 +378,30 @@ int ldmae_pr_flags(const float* u, const float* nu, const float* ru, int M, cons
 long ldmae_adm_is_workspace_bytes(int M, int C, int split);
 int ldmae_adm_softmax_is(const float* logits, int M, int C, int split, void* workspace, double* h, double* S, void* stream);
 
+/* ---- tokenizer evaluation: rFID, PSNR, SSIM and LPIPS (reference evaluate_tokenizer.py, models/lpips.py), f32 ----------------------
+ * lpips_prep: input / target NCHW [B, 3, H, W] -> out NHWC [2B, H, W, 4] = (x - shift) / scale of LPIPS' ScalingLayer (shift -0.030, -0.088,
+ * -0.188; scale 0.458, 0.448, 0.450); images 0..B-1 from input, B..2B-1 from target, channel 3 = 0.  out 16-byte aligned.
+ * lpips_layer: f NHWC [2B, h, w, C] (C = 64, 128, 256 or 512), lin_w [C]; per pixel f^ = f / (sqrt(sum_c f^2) + 1e-10) of both halves and
+ * d = sum_c lin_w[c] (f^_b - f^_(B+b))^2; out[b] += mean over the h * w pixels of d.  workspace: lpips_workspace_bytes(B, h, w) bytes.
+ * ssim: per-image SSIM [B] of preds / target NCHW [B, C, H, W] as torchmetrics' StructuralSimilarityIndexMeasure with its defaults: inputs
+ * clamped to [lo, hi], c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2, separable 11-tap Gaussian (sigma 1.5) of x, y, x^2, y^2, xy,
+ * variances clamped at 0, the map cropped by 5 on every side and averaged over C (H - 10) (W - 10).  H, W >= 11.
+ * workspace: ssim_workspace_bytes(B, C, H, W) bytes.
+ * recon_quantize_psnr: decoded / ref NCHW [B, 3, H, W] -> dec8 / ref8 NHWC uint8 [B, H, W, 3] = (uint8) clamp(127.5 x + 128, 0, 255)
+ * (truncation; multiply and add rounded separately) and sse[B] = exact sum over the 3 H W values of (dec8 - ref8)^2.
+ * sse_u8: sse[B] = exact sum of (a - b)^2 over n uint8 values per image.  workspace of both: sse_workspace_bytes(B, pixels) bytes, 8-byte
+ * aligned, pixels = H W (recon_quantize_psnr) or n (sse_u8).  Every per-image sum is two-stage and fixed-order: bitwise reproducible. */
+int ldmae_lpips_prep(const float* input, const float* target, float* out, int B, int H, int W, void* stream);
+long ldmae_lpips_workspace_bytes(int B, int h, int w);
+int ldmae_lpips_layer(const float* f, const float* lin_w, float* out, int B, int h, int w, int C, void* workspace, void* stream);
+long ldmae_ssim_workspace_bytes(int B, int C, int H, int W);
+int ldmae_ssim(const float* preds, const float* target, float* out, int B, int C, int H, int W, float lo, float hi, float data_range,
+               void* workspace, void* stream);
+long ldmae_sse_workspace_bytes(int B, long pixels);
+int ldmae_recon_quantize_psnr(const float* decoded, const float* ref, unsigned char* dec8, unsigned char* ref8, long long* sse, int B, int H,
+                              int W, void* workspace, void* stream);
+int ldmae_sse_u8(const unsigned char* a, const unsigned char* b, long long* sse, int B, long n, void* workspace, void* stream);
+
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */
 int ldmae_prof_enable(int on);

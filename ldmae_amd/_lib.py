@@ -117,6 +117,14 @@ SIGNATURES = {
     "ldmae_pr_flags": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ldmae_adm_is_workspace_bytes": (_l, [_i, _i, _i]),
     "ldmae_adm_softmax_is": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ldmae_lpips_prep": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ldmae_lpips_workspace_bytes": (_l, [_i, _i, _i]),
+    "ldmae_lpips_layer": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ldmae_ssim_workspace_bytes": (_l, [_i, _i, _i, _i]),
+    "ldmae_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "ldmae_sse_workspace_bytes": (_l, [_i, _l]),
+    "ldmae_recon_quantize_psnr": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ldmae_sse_u8": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

@@ -1162,3 +1162,86 @@ def adm_softmax_is(logits, split=5000):
     S = torch.empty(-(-M // split), Cc, dtype=torch.float64, device=logits.device)
     call("ldmae_adm_softmax_is", ptr(logits), M, Cc, split, ptr(ws), ptr(h), ptr(S), stream())
     return h, S
+
+
+# ----------------------------------------------------------------------------- tokenizer evaluation (csrc/tokenizer_eval.hip), f32
+def _nchw(t, what, channels=None):
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or (channels is not None and t.shape[1] != channels):
+        want = f"[B, {channels}, H, W]" if channels is not None else "[B, C, H, W]"
+        raise RuntimeError(f"{what}: need a contiguous f32 NCHW {want} tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _same(a, b, what):
+    if tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise RuntimeError(f"{what}: {tuple(a.shape)} on {a.device} and {tuple(b.shape)} on {b.device} must match")
+
+
+def lpips_prep(input, target):
+    """LPIPS' ScalingLayer on both images: NCHW f32 [B, 3, H, W] x 2 -> NHWC f32 [2B, H, W, 4] = (x - shift) / scale, input first, channel 3
+    zero (the Cin-4 VEC path of conv2d_nhwc)."""
+    _nchw(input, "lpips_prep input", 3)
+    _nchw(target, "lpips_prep target", 3)
+    _same(input, target, "lpips_prep")
+    B, _, H, W = input.shape
+    out = torch.empty(2 * B, H, W, 4, dtype=torch.float32, device=input.device)
+    call("ldmae_lpips_prep", ptr(input), ptr(target), ptr(out), B, H, W, stream())
+    return out
+
+
+def lpips_layer(f, lin_w, out):
+    """One VGG tap f [2B, h, w, C] (C = 64, 128, 256, 512) and its lin weight [C]: out [B] += mean_hw sum_c w_c (f^_b - f^_(B+b))^2, f^ the
+    channel-normalised features (f / (|f| + 1e-10)).  out is accumulated in place (f32 [B])."""
+    _nhwc(f, "lpips_layer")
+    n, h, w, C = f.shape
+    if n % 2 or C not in (64, 128, 256, 512):
+        raise RuntimeError(f"lpips_layer: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
+    B = n // 2
+    lin_w = _arg(lin_w, "lpips_layer lin_w", torch.float32, numel=C)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous() or lin_w.device != f.device or out.device != f.device:
+        raise RuntimeError(f"lpips_layer: out must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(out.shape)} {out.dtype}")
+    ws = workspace(L.load().ldmae_lpips_workspace_bytes(B, h, w), f.device, "lpips")
+    call("ldmae_lpips_layer", ptr(f), ptr(lin_w), ptr(out), B, h, w, C, ptr(ws), stream())
+    return out
+
+
+def ssim(preds, target, lo=-1.0, hi=1.0, data_range=2.0):
+    """Per-image SSIM f32 [B] of NCHW f32 [B, C, H, W] (H, W >= 11): torchmetrics' default Gaussian SSIM of the inputs clamped to [lo, hi]
+    (+-inf: no clamp) with c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2."""
+    _nchw(preds, "ssim preds")
+    _nchw(target, "ssim target")
+    _same(preds, target, "ssim")
+    B, C, H, W = preds.shape
+    if H < 11 or W < 11:
+        raise RuntimeError(f"ssim: {H} x {W} images are smaller than the 11 x 11 Gaussian window")
+    out = torch.empty(B, dtype=torch.float32, device=preds.device)
+    ws = workspace(L.load().ldmae_ssim_workspace_bytes(B, C, H, W), preds.device, "ssim")
+    call("ldmae_ssim", ptr(preds), ptr(target), ptr(out), B, C, H, W, float(lo), float(hi), float(data_range), ptr(ws), stream())
+    return out
+
+
+def recon_quantize_sse(decoded, ref):
+    """What the reference writes as PNG, for both images, and their exact squared error: NCHW f32 [B, 3, H, W] x 2 ->
+    (dec8, ref8) uint8 NHWC [B, H, W, 3] = (uint8) clamp(127.5 x + 128, 0, 255), sse int64 [B] = sum of (dec8 - ref8)^2."""
+    _nchw(decoded, "recon_quantize decoded", 3)
+    _nchw(ref, "recon_quantize ref", 3)
+    _same(decoded, ref, "recon_quantize")
+    B, _, H, W = decoded.shape
+    dec8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=decoded.device)
+    ref8 = torch.empty_like(dec8)
+    sse = torch.empty(B, dtype=torch.int64, device=decoded.device)
+    ws = workspace(L.load().ldmae_sse_workspace_bytes(B, H * W), decoded.device, "sse")
+    call("ldmae_recon_quantize_psnr", ptr(decoded), ptr(ref), ptr(dec8), ptr(ref8), ptr(sse), B, H, W, ptr(ws), stream())
+    return dec8, ref8, sse
+
+
+def sse_u8(a, b):
+    """int64 [B]: exact sum of (a - b)^2 over each image of two uint8 tensors [B, ...] of one shape."""
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() < 2 or not a.is_contiguous() or not b.is_contiguous():
+        raise RuntimeError(f"sse_u8: need contiguous uint8 [B, ...] tensors, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    _same(a, b, "sse_u8")
+    B, n = a.shape[0], a[0].numel()
+    sse = torch.empty(B, dtype=torch.int64, device=a.device)
+    ws = workspace(L.load().ldmae_sse_workspace_bytes(B, n), a.device, "sse")
+    call("ldmae_sse_u8", ptr(a), ptr(b), ptr(sse), B, n, ptr(ws), stream())
+    return sse
