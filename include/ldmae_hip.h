@@ -402,6 +402,23 @@ int ldmae_recon_quantize_psnr(const float* decoded, const float* ref, unsigned c
                               int W, void* workspace, void* stream);
 int ldmae_sse_u8(const unsigned char* a, const unsigned char* b, long long* sse, int B, long n, void* workspace, void* stream);
 
+/* ---- LPIPS backward (stage 3 of train_ae.sh: decoder tuning with the perceptual loss), f32 NHWC, no atomics: bitwise reproducible ----
+ * conv3x3_relu_dgrad_nhwc_f32: data gradient of y = relu(conv3x3(x, w) + b), stride 1, pad 1.  dy, y [B, H, W, Cy] (Cy % 4 == 0), w_rot
+ * [Cx, 3, 3, Cy] with w_rot[ci][ky][kx][co] = w[co][2 - ky][2 - kx][ci]; dx [B, H, W, Cx] = conv3x3(dy * [y > 0], w_rot), overwritten.  The
+ * mask is applied while the operand is gathered; the main loop is the forward conv's exact-f32 MFMA loop.
+ * maxpool2x2_bwd_nhwc_f32: dx [B, H, W, C] from dy [B, H/2, W/2, C] and the pooled input x [B, H, W, C] (C % 4 == 0): dy goes to the window's
+ * maximum, the first in row-major order on a tie; rows / columns past 2 floor(H/2), 2 floor(W/2) get 0; every element of dx is written.
+ * lpips_layer_bwd: f [2B, h, w, C] and lin_w [C] as lpips_layer takes them, g [B] the gradient of the per-pair value; d_input / d_target
+ * [B, h, w, C] receive the gradient to f's first / second half (null: not wanted; at least one).  accumulate != 0 adds into them (the tap's
+ * buffer already holds the pool backward's gradient), else overwrites.  A pixel that is all zero in a half gets exactly 0 in that half.
+ * lpips_prep_bwd: g NHWC [B, H, W, 4] -> out NCHW [B, 3, H, W] = g[..., c] / scale[c] (the ScalingLayer's backward). */
+int ldmae_conv3x3_relu_dgrad_nhwc_f32(const float* dy, const float* y, const float* w_rot, float* dx, int B, int H, int W, int Cy, int Cx,
+                                      void* stream);
+int ldmae_maxpool2x2_bwd_nhwc_f32(const float* dy, const float* x, float* dx, int B, int H, int W, int C, void* stream);
+int ldmae_lpips_layer_bwd(const float* f, const float* lin_w, const float* g, float* d_input, float* d_target, int B, int h, int w, int C,
+                          int accumulate, void* stream);
+int ldmae_lpips_prep_bwd(const float* g, float* out, int B, int H, int W, void* stream);
+
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */
 int ldmae_prof_enable(int on);

@@ -125,6 +125,10 @@ SIGNATURES = {
     "ldmae_sse_workspace_bytes": (_l, [_i, _l]),
     "ldmae_recon_quantize_psnr": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ldmae_sse_u8": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "ldmae_conv3x3_relu_dgrad_nhwc_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_maxpool2x2_bwd_nhwc_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ldmae_lpips_layer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_lpips_prep_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

@@ -6,13 +6,10 @@
 //   - uint8 HWC RGB -> bilinear 299x299 (align_corners=False) -> 2x - 1;
 //   - f64 feature statistics: sum(x - s) and sum((x - s)(x - s)^T) accumulated over batches, s a fixed shift.
 #include "common.h"
+#include "conv_igemm_f32.h"
 
 // ------------------------------------------------------------------------------------------------ convolution
-// 128 (M) x 64 (N) output tile, 256 threads = 2 x 2 waves of 64 x 32 (4 x 2 MFMA blocks of 16 x 16), BK = 16, register-staged double-
-// buffered LDS.  K order inside a BK step is permuted the same way for both operands: MFMA kk of lane group q = lane >> 4 takes k = 4 q + kk,
-// so each lane fetches its four A (B) values of a step with ONE ds_read_b128 instead of four ds_read_b32.  The sum is over the same products,
-// in a different order (f32 rounding only).  Row stride 20 floats: the eight 16-B reads of a ds_read_b128 phase hit disjoint banks.
-constexpr int CV_BM = 128, CV_BN = 64, CV_BK = 16, CV_LD = 20, CV_NT = 256;
+// The tile shape and the MFMA main loop are conv_igemm_f32.h (shared with the LPIPS data gradient of lpips_bwd.hip).
 
 struct ConvGeom {
   int B, H, W, Cin, ldx, xoff;        // input [B, H, W, ldx], channels [xoff, xoff + Cin)
@@ -87,48 +84,8 @@ __global__ __launch_bounds__(CV_NT) void conv_igemm_f32_kernel(const float* __re
   };
 
   f32x4 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int nk = (g.K + CV_BK - 1) / CV_BK;
-  float4 ra0 = fetch_a(0, 0), ra1 = fetch_a(1, 0), rb = fetch_b(0);
-  advance();
-  *(float4*)&As[0][lr * CV_LD + lc] = ra0;
-  *(float4*)&As[0][(lr + 64) * CV_LD + lc] = ra1;
-  *(float4*)&Bs[0][lr * CV_LD + lc] = rb;
-  __syncthreads();
+  conv_igemm_f32_mainloop(As, Bs, (g.K + CV_BK - 1) / CV_BK, fetch_a, fetch_b, advance, acc);
   const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-  int cur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) {
-      ra0 = fetch_a(0, (kt + 1) * CV_BK);
-      ra1 = fetch_a(1, (kt + 1) * CV_BK);
-      rb = fetch_b((kt + 1) * CV_BK);
-      advance();
-    }
-    float4 af[4], bf[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = *(const float4*)&As[cur][(wm * 64 + i * 16 + r16) * CV_LD + q4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bf[j] = *(const float4*)&Bs[cur][(wn * 32 + j * 16 + r16) * CV_LD + q4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i].x, bf[j].x, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i].y, bf[j].y, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i].z, bf[j].z, acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
-      }
-    if (kt + 1 < nk) {
-      *(float4*)&As[cur ^ 1][lr * CV_LD + lc] = ra0;
-      *(float4*)&As[cur ^ 1][(lr + 64) * CV_LD + lc] = ra1;
-      *(float4*)&Bs[cur ^ 1][lr * CV_LD + lc] = rb;
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
   // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block
 #pragma unroll
   for (int j = 0; j < 2; ++j) {

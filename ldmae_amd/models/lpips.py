@@ -1,10 +1,21 @@
-"""LPIPS (VGG16 + learned linear heads) with the interface of the reference's models/lpips.py, forward only, on this package's kernels.
+"""LPIPS (VGG16 + learned linear heads) with the interface of the reference's models/lpips.py on this package's kernels: forward only by default,
+differentiable on request (`LPIPS(..., differentiable=True)`: the perceptual loss of the stage-3 decoder tuning, VMAE/train_ae.sh:84-106).
 
     d(x, y) = sum_k mean_hw sum_c w_k[c] (f^_k(x) - f^_k(y))^2,   f^ = f / (sqrt(sum_c f^2) + 1e-10)
 
 with f_k the VGG16 taps relu1_2, relu2_2, relu3_3, relu4_3 and relu5_3 of the ScalingLayer'd image.  The 13 convolutions (3x3, padding 1,
 ReLU fused) run on conv2d_nhwc (the exact-f32 MFMA implicit GEMM), the four 2x2 / 2 max pools on pool2d_nhwc, the ScalingLayer and the
 heads on csrc/tokenizer_eval.hip.  Input and target run as ONE batch of 2B images, so every conv is one launch.
+
+Backward (csrc/lpips_bwd.hip; only with differentiable=True, only for the halves that require grad -- stage 3 needs the second argument alone:
+perceptual_loss(imgs, unpatchify(pred))): per tap the head backward, per pool the max-pool backward (the two sum into one buffer: the pool backward
+writes it, the head backward adds to it -- always in this order), per conv the data gradient with the ReLU mask taken from the saved output inside
+the operand gather, on weights rotated once per object (rotate_weight); no weight gradients (the network is frozen), no atomics: two backward runs
+give the same bits.  Activation memory: the forward keeps the 13 conv outputs of each half that requires grad (17.7 M floats = 71 MB per 256 x 256
+image; 1.13 GB at the recipe's batch of 16) and only the five taps (the first of them is the largest: 16.8 MB per image) of a half that does not.
+Nothing is copied to keep them: when one half requires grad every layer runs as two launches of B images (LPIPS._run).
+One deliberate difference from torch: at a pixel whose channels are all zero in a half, that half's gradient is exactly 0 (torch: NaN, from sqrt's
+backward at 0).  The value is bitwise the forward-only value.
 
 Weights are the user's files, never downloaded:
   - torchvision's vgg16-397923af.pth (keys features.{0,2,5,...,28}.weight|bias): the `vgg_weights` argument, then $LDMAE_LPIPS_VGG, then
@@ -155,10 +166,68 @@ def conv_flops_per_image(H, W):
     return flops
 
 
-class LPIPS:
-    """forward(input, target): NCHW f32 [B, 3, H, W] in [-1, 1] -> f32 [B, 1, 1, 1], as the reference's LPIPS().eval().  Forward only."""
+def rotate_weight(w):
+    """Channels-last forward weight [Cout, 3, 3, Cin] -> the data gradient's weight [Cin, 3, 3, Cout] in the conv kernel's K order (ky, kx, channel):
+    w_rot[ci][ky][kx][co] = w[co][2 - ky][2 - kx][ci], so that dx = conv3x3(dy, w_rot) with padding 1 (conv_transpose2d of a stride-1 conv)."""
+    if w.dim() != 4 or tuple(w.shape[1:3]) != (3, 3):
+        raise ValueError(f"rotate_weight: weight {tuple(w.shape)} is not [Cout, 3, 3, Cin]")
+    return w.flip(1, 2).permute(3, 1, 2, 0).contiguous()
 
-    def __init__(self, vgg_weights=None, lin_weights=None, state_dict=None, device="cuda"):
+
+def _last_of_slice(i):
+    return i + 1 == len(CONVS) or CONVS[i + 1][1] != CONVS[i][1]
+
+
+class _LPIPSFn(torch.autograd.Function):
+    """LPIPS.forward with a backward (see the module docstring).  Saved: the five taps [2B, ...] and, per half that requires grad, the other eight
+    conv outputs of that half [B, ...] (tensors of their own when one half requires grad, views of the [2B, ...] outputs when both do; the tap
+    entries of a half are views of the saved taps)."""
+
+    @staticmethod
+    def forward(ctx, mod, input, target):
+        need = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        out, taps, acts = mod._run(input, target, need)
+        ctx.mod, ctx.need, ctx.dtypes, ctx.devices = mod, need, (input.dtype, target.dtype), (input.device, target.device)
+        ctx.save_for_backward(*taps, *[a for half in acts if half is not None for a in half if a is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        mod, ops = ctx.mod, ctx.mod._ops
+        saved = list(ctx.saved_tensors)
+        taps, rest = saved[:len(CHANNELS)], saved[len(CHANNELS):]
+        B = taps[0].shape[0] // 2
+        g = gout.detach().reshape(B).to(torch.float32).contiguous()
+        per_half = len(CONVS) - len(CHANNELS)          # saved per half besides the taps, in execution order, the input half's first
+        grads = [None, None]
+        for half in (0, 1):
+            if not ctx.need[half]:
+                continue
+            inner, rest = rest[:per_half], rest[per_half:]
+            d = None
+            for i in reversed(range(len(CONVS))):
+                k = CONVS[i][1] - 1
+                if _last_of_slice(i):
+                    y = taps[k][half * B:(half + 1) * B]
+                    # gradient of tap k: the following pool's backward writes the buffer, the head backward adds to it (fixed order)
+                    buf = ops.maxpool2x2_bwd_nhwc(d, y) if d is not None else torch.empty_like(y)
+                    ops.lpips_layer_bwd(taps[k], mod.lins[k], g, d_input=buf if half == 0 else None, d_target=buf if half == 1 else None,
+                                        accumulate=d is not None)
+                    d = buf
+                else:
+                    y = inner.pop()
+                d = ops.conv3x3_relu_dgrad_nhwc(d, y, mod.wrot[i])
+            grads[half] = ops.lpips_prep_bwd(d).to(ctx.devices[half], ctx.dtypes[half])
+        return None, grads[0], grads[1]
+
+
+class LPIPS:
+    """forward(input, target): NCHW f32 [B, 3, H, W] in [-1, 1] -> f32 [B, 1, 1, 1], as the reference's LPIPS().eval().  Forward only unless built with
+    differentiable=True (then a torch.autograd.Function with the same value, bit for bit; activation memory: module docstring)."""
+
+    differentiable = False
+
+    def __init__(self, vgg_weights=None, lin_weights=None, state_dict=None, device="cuda", differentiable=False):
         from .. import ops
         self._ops = ops
         self.device = torch.device(device)
@@ -168,6 +237,9 @@ class LPIPS:
             state_dict = load_state_dict_from_files(vgg_weights, lin_weights)
         self.convs = [(w.to(self.device), b.to(self.device), s) for w, b, s in conv_weights(state_dict)]
         self.lins = [state_dict[f"lin{k}.model.1.weight"].float().reshape(-1).contiguous().to(self.device) for k in range(len(CHANNELS))]
+        if differentiable:
+            self.differentiable = True
+            self.wrot = [rotate_weight(w) for w, _, _ in self.convs]          # once per object; conv1_1's padded 4th row is zero
 
     def to(self, device):
         if torch.device(device) != self.device:
@@ -180,22 +252,46 @@ class LPIPS:
     def __call__(self, input, target):
         return self.forward(input, target)
 
-    def forward(self, input, target):
-        if torch.is_grad_enabled() and (input.requires_grad or target.requires_grad):
-            raise RuntimeError("LPIPS here is forward-only: its kernels have no backward, so it cannot serve as a perceptual training loss. "
-                               "Call it under torch.no_grad() or on tensors that do not require grad.")
+    def _run(self, input, target, keep=(False, False)):
+        """-> (value [B, 1, 1, 1], the five taps [2B, ...], per half in `keep` its other conv outputs in execution order (None at the taps))."""
         if input.dim() != 4 or input.shape[1] != 3 or tuple(input.shape) != tuple(target.shape):
             raise RuntimeError(f"LPIPS: input {tuple(input.shape)} and target {tuple(target.shape)} must both be [B, 3, H, W]")
         x = input.detach().to(self.device, torch.float32).contiguous()
         y = target.detach().to(self.device, torch.float32).contiguous()
-        h = self._ops.lpips_prep(x, y)
-        out = torch.zeros(x.shape[0], dtype=torch.float32, device=self.device)
+        B = x.shape[0]
+        ops = self._ops
+        h = ops.lpips_prep(x, y)
+        out = torch.zeros(B, dtype=torch.float32, device=self.device)
+        taps, acts = [], [[] if k else None for k in keep]
+        # ONE half kept: each layer runs as two launches of B images, so the kept half's outputs are tensors of their own (kept without a copy)
+        # and the other half's are freed layer by layer; the taps are still one [2B, ...] tensor, written half by half.  Both or none: one launch
+        # of 2B images per layer, the kept entries are views of it.  Every output element is the same sum either way: the value is bitwise one.
+        split = keep[0] != keep[1]
+        hs = [h[:B], h[B:]] if split else [h]
         prev = 1
-        for w, b, s in self.convs:
+        for i, (w, b, s) in enumerate(self.convs):
             if s != prev:                              # end of slice prev: its last ReLU output is tap prev - 1; then the 2x2 / 2 max pool
-                self._ops.lpips_layer(h, self.lins[prev - 1], out)
-                h = self._ops.pool2d_nhwc(h, "max", k=2, stride=2, pad=0)
+                ops.lpips_layer(h, self.lins[prev - 1], out)
+                taps.append(h)
+                hs = [ops.pool2d_nhwc(t, "max", k=2, stride=2, pad=0) for t in hs]
                 prev = s
-            h = self._ops.conv2d_nhwc(h, w, b, (1, 1), (1, 1), True)
-        self._ops.lpips_layer(h, self.lins[prev - 1], out)
-        return out.view(-1, 1, 1, 1)
+            if split and _last_of_slice(i):            # a tap: both halves into one tensor
+                h = torch.empty(2 * B, hs[0].shape[1], hs[0].shape[2], w.shape[0], dtype=torch.float32, device=self.device)
+                hs = [ops.conv2d_nhwc(t, w, b, (1, 1), (1, 1), True, out=h[j * B:(j + 1) * B]) for j, t in enumerate(hs)]
+            else:
+                hs = [ops.conv2d_nhwc(t, w, b, (1, 1), (1, 1), True) for t in hs]
+                h = hs[0]                              # (read only where it is the whole batch: not split)
+            for half, a in enumerate(acts):
+                if a is not None:
+                    a.append(None if _last_of_slice(i) else (hs[half] if split else h[half * B:(half + 1) * B]))
+        ops.lpips_layer(h, self.lins[prev - 1], out)
+        taps.append(h)
+        return out.view(-1, 1, 1, 1), taps, acts
+
+    def forward(self, input, target):
+        if torch.is_grad_enabled() and (input.requires_grad or target.requires_grad):
+            if not self.differentiable:
+                raise RuntimeError("LPIPS here is forward-only: its kernels have no backward, so it cannot serve as a perceptual training loss. "
+                                   "Call it under torch.no_grad() or on tensors that do not require grad -- or build it with differentiable=True.")
+            return _LPIPSFn.apply(self, input, target)
+        return self._run(input, target)[0]

@@ -1205,6 +1205,81 @@ def lpips_layer(f, lin_w, out):
     return out
 
 
+# ----------------------------------------------------------------------------- LPIPS backward (csrc/lpips_bwd.hip), f32 NHWC, no atomics
+def conv3x3_relu_dgrad_nhwc(dy, y, w_rot, out=None):
+    """Data gradient of y = relu(conv3x3(x, w) + b) (stride 1, pad 1): dx [B, H, W, Cx] = conv3x3(dy * [y > 0], w_rot) with dy, y [B, H, W, Cy] and
+    w_rot [Cx, 3, 3, Cy] (models.lpips.rotate_weight of the forward weight).  The ReLU mask is taken from y inside the operand gather."""
+    _nhwc(dy, "conv3x3_relu_dgrad_nhwc dy")
+    _nhwc(y, "conv3x3_relu_dgrad_nhwc y")
+    _same(dy, y, "conv3x3_relu_dgrad_nhwc")
+    B, H, W, Cy = dy.shape
+    if w_rot.dtype != torch.float32 or w_rot.dim() != 4 or tuple(w_rot.shape[1:]) != (3, 3, Cy) or not w_rot.is_contiguous() or w_rot.device != dy.device:
+        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc: rotated weight {tuple(w_rot.shape)} {w_rot.dtype} on {w_rot.device} is not a contiguous f32 "
+                           f"[Cx, 3, 3, {Cy}] tensor on {dy.device}")
+    if Cy % 4:
+        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc: {Cy} gradient channels (a multiple of 4)")
+    Cx = w_rot.shape[0]
+    if out is None:
+        out = torch.empty(B, H, W, Cx, dtype=torch.float32, device=dy.device)
+    _nhwc(out, "conv3x3_relu_dgrad_nhwc out")
+    if tuple(out.shape) != (B, H, W, Cx) or out.device != dy.device:
+        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc: out {tuple(out.shape)} on {out.device} is not [{B}, {H}, {W}, {Cx}] on {dy.device}")
+    call("ldmae_conv3x3_relu_dgrad_nhwc_f32", ptr(dy), ptr(y), ptr(w_rot), ptr(out), B, H, W, Cy, Cx, stream())
+    return out
+
+
+def maxpool2x2_bwd_nhwc(dy, x, out=None):
+    """Backward of pool2d_nhwc(x, "max", k=2, stride=2): dx [B, H, W, C] from dy [B, H // 2, W // 2, C] and the pooled input x.  dy goes to the
+    window's maximum (the first in row-major order on a tie, as torch); odd last rows / columns get 0; every element of dx is written."""
+    _nhwc(x, "maxpool2x2_bwd_nhwc x")
+    _nhwc(dy, "maxpool2x2_bwd_nhwc dy")
+    B, H, W, C = x.shape
+    if tuple(dy.shape) != (B, H // 2, W // 2, C) or dy.device != x.device:
+        raise RuntimeError(f"maxpool2x2_bwd_nhwc: dy {tuple(dy.shape)} on {dy.device} is not [{B}, {H // 2}, {W // 2}, {C}] on {x.device}")
+    if C % 4 or x.numel() == 0:
+        raise RuntimeError(f"maxpool2x2_bwd_nhwc: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 4 channels")
+    if out is None:
+        out = torch.empty_like(x)
+    _nhwc(out, "maxpool2x2_bwd_nhwc out")
+    if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
+        raise RuntimeError(f"maxpool2x2_bwd_nhwc: out {tuple(out.shape)} on {out.device} does not match x {tuple(x.shape)} on {x.device}")
+    call("ldmae_maxpool2x2_bwd_nhwc_f32", ptr(dy) if dy.numel() else None, ptr(x), ptr(out), B, H, W, C, stream())
+    return out
+
+
+def lpips_layer_bwd(f, lin_w, g, d_input=None, d_target=None, accumulate=False):
+    """Backward of lpips_layer for one tap f [2B, h, w, C]: with g [B] the gradient of the per-pair value, the gradient to f's first (input) /
+    second (target) half is written into d_input / d_target [B, h, w, C]; None = that half is not wanted (at least one is).  accumulate=True adds
+    into the buffers (which then hold the following pool's backward), else they are overwritten.  A pixel whose channels are all zero in a half
+    gets exactly 0 there (torch gives NaN).  -> (d_input, d_target)."""
+    _nhwc(f, "lpips_layer_bwd")
+    n, h, w, C = f.shape
+    if n % 2 or C not in (64, 128, 256, 512):
+        raise RuntimeError(f"lpips_layer_bwd: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
+    B = n // 2
+    lin_w = _arg(lin_w, "lpips_layer_bwd lin_w", torch.float32, numel=C)
+    if g.dtype != torch.float32 or tuple(g.shape) != (B,) or not g.is_contiguous() or g.device != f.device or lin_w.device != f.device:
+        raise RuntimeError(f"lpips_layer_bwd: g must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(g.shape)} {g.dtype} on {g.device}")
+    if d_input is None and d_target is None:
+        raise RuntimeError("lpips_layer_bwd: neither d_input nor d_target given: nothing to compute")
+    for d, what in ((d_input, "d_input"), (d_target, "d_target")):
+        if d is not None and (d.dtype != torch.float32 or tuple(d.shape) != (B, h, w, C) or not d.is_contiguous() or d.device != f.device):
+            raise RuntimeError(f"lpips_layer_bwd: {what} must be a contiguous f32 [{B}, {h}, {w}, {C}] tensor on {f.device}, got {tuple(d.shape)} {d.dtype}")
+    call("ldmae_lpips_layer_bwd", ptr(f), ptr(lin_w), ptr(g), ptr(d_input), ptr(d_target), B, h, w, C, 1 if accumulate else 0, stream())
+    return d_input, d_target
+
+
+def lpips_prep_bwd(g):
+    """Backward of lpips_prep for one half: g NHWC f32 [B, H, W, 4] (the data gradient of conv1_1) -> NCHW f32 [B, 3, H, W] = g[..., c] / scale[c]."""
+    _nhwc(g, "lpips_prep_bwd")
+    B, H, W, C = g.shape
+    if C != 4:
+        raise RuntimeError(f"lpips_prep_bwd: gradient {tuple(g.shape)}: need [B, H, W, 4]")
+    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=g.device)
+    call("ldmae_lpips_prep_bwd", ptr(g), ptr(out), B, H, W, stream())
+    return out
+
+
 def ssim(preds, target, lo=-1.0, hi=1.0, data_range=2.0):
     """Per-image SSIM f32 [B] of NCHW f32 [B, C, H, W] (H, W >= 11): torchmetrics' default Gaussian SSIM of the inputs clamped to [lo, hi]
     (+-inf: no clamp) with c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2."""

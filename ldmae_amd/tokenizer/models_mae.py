@@ -7,8 +7,10 @@ fc1 GEMM + exact GELU, fc2 GEMM + residual) -> LayerNorm.  Each block is one aut
 kernel sequences).  head_dim is 16: under bf16 autocast the attention core is the bf16 flash kernel with the K/V images and
 fragments zero-padded to 32 columns in LDS / registers (attention.hip); in f32 mode everything runs on the exact-f32 MFMA path.
 The decoder / ``encode`` / ``decode`` / ``decode_to_images`` docking functions re-use the same block kernels
-(inference only for the RGB smoothing conv).  Unshipped variants (gradual_resol, cls token, pred_with_conv, perceptual loss) raise
-NotImplementedError; `down_nonlinear` (MLP latent maps of the f8d16 / f8d16_flexible archs) is implemented.
+(inference only for the RGB smoothing conv).  `ldmae_mode` is the stage-3 decoder tuning of VMAE/train_ae.sh:84-106: `forward` is the pre-training
+tree's forward_ldmae (pixel MSE + the LPIPS perceptual loss, ldmae_amd.models.lpips.LPIPS(differentiable=True)), trainable on the same Functions.
+Unshipped variants (gradual_resol, cls token, pred_with_conv, a perceptual loss inside forward_vanilla) raise NotImplementedError;
+`down_nonlinear` (MLP latent maps of the f8d16 / f8d16_flexible archs) is implemented.
 """
 from __future__ import annotations
 
@@ -446,10 +448,16 @@ class MaskedAutoencoderViT(nn.Module):
         uses -- they differ (tokenizer/util/misc.DiagonalGaussianDistribution); passing `fixed_std` selects "vmae", ldmae_amd/vmae_pretrain.py sets it."""
         super().__init__()
         self.fixed_std, self.kl_form = fixed_std, ("vmae" if fixed_std is not None else "tokenizer")
-        if gradual_resol or not no_cls or perceptual_loss is not None:
-            raise NotImplementedError("ldmae_amd MaskedAutoencoderViT: gradual_resol / cls token / perceptual loss are "
+        if gradual_resol or not no_cls:
+            raise NotImplementedError("ldmae_amd MaskedAutoencoderViT: gradual_resol / cls token are "
                                       "not used by the shipped tokenizer (mae_for_ldmae_f8d16_prev, inference.py:133-137)")
-        self.perceptual_loss, self.smooth_output, self.gradual_resol, self.kl_loss_weight = None, smooth_output, False, kl_loss_weight
+        if perceptual_loss is not None and not ldmae_mode:
+            raise NotImplementedError("ldmae_amd MaskedAutoencoderViT: a perceptual loss inside forward_vanilla (VMAE/models_mae.py:761-767) is used by no "
+                                      "shipped script; it is the loss of ldmae_mode=True (stage 3 of train_ae.sh)")
+        # the perceptual loss is a frozen callable (models.lpips.LPIPS), not a submodule: its weights are the user's files and stay out of state_dict()
+        object.__setattr__(self, "perceptual_loss", perceptual_loss)
+        self.perceptual_loss_ratio = perceptual_loss_ratio
+        self.smooth_output, self.gradual_resol, self.kl_loss_weight = smooth_output, False, kl_loss_weight
         enc_lat = 2 * latent_dim if kl_loss_weight is not None else latent_dim
         if down_nonlinear:                                   # :311-314 (from_latent ends at EMBED_dim; decoder_embed then maps it to the decoder width)
             self.to_latent = MLP_dim_resize(embed_dim, latent_dim * 4, enc_lat)
@@ -641,7 +649,7 @@ class MaskedAutoencoderViT(nn.Module):
         masked / visible reconstruction loss.  `_noise` [B, L] / `_eps` [B, latent, kept] (tests): host-drawn masking noise and
         posterior-sample noise instead of the device RNG draws the reference makes at the same two places."""
         if self.ldmae_mode:
-            raise NotImplementedError("ldmae_amd: ldmae_mode (decoder fine-tuning with LPIPS) is out of scope")
+            return self.forward_ldmae(imgs, mask_ratio=mask_ratio, _eps=_eps)
         dtype = _act_dtype(self.precision, allow_f16=True)           # read before autocast is switched off below
         latent, mask, ids_restore = self.forward_encoder(imgs, mask_ratio, noise=_noise)
         with torch.autocast(device_type="cuda", enabled=False):
@@ -742,13 +750,66 @@ class MaskedAutoencoderViT(nn.Module):
         z = x.permute(0, 2, 1).reshape(x.shape[0], x.shape[2], g, g)
         return self.patchify(self.decode(z, return_dict=False)[0])
 
-    def reconstruct(self, imgs, use_mode=True, return_kl=False):
-        """:693-703."""
+    def reconstruct(self, imgs, use_mode=True, return_kl=False, mask_ratio=0.75):
+        """:693-703, with the pre-training tree's `mask_ratio` argument (VMAE/models_mae.py:697-710): 0.0 = the posterior MODE, no KL value (a
+        quirk of that tree: with return_kl it fails there too) with the encoder in the CALLER's grad mode; any other value, the default included:
+        the encoder under no_grad.  The training step uses forward_ldmae, the same computation without the layout round trips."""
+        if mask_ratio == 0.0:
+            if return_kl:
+                raise RuntimeError("reconstruct: mask_ratio 0.0 computes no KL value (VMAE/models_mae.py:699-700)")
+            return self.ldmae_decoding(self.ldmae_encoding(imgs, use_mode=True))
         with torch.no_grad():
             enc = self.ldmae_encoding(imgs, use_mode=use_mode, return_kl=return_kl)
         x, kl_val = enc if return_kl else (enc, None)
         x = self.ldmae_decoding(x)
         return (x, kl_val) if return_kl else x
+
+    def forward_ldmae(self, imgs, mask_ratio=0.75, _eps=None):
+        """The pre-training tree's forward_ldmae (VMAE/models_mae.py:809-826) over reconstruct(imgs, use_mode=False, mask_ratio=...) (:697-710): the
+        stage-3 step of train_ae.sh, trainable on the kernels.  There is no mask token and no masking; `mask_ratio` only selects the encoder's role:
+          - mask_ratio == 0.0 (what the shipped script passes): the encoder runs WITH grad and the posterior MODE is decoded;
+          - otherwise: the encoder runs under no_grad and the posterior is SAMPLED (`_eps` [B, latent, N] (tests): that draw, host-made).
+        loss = mean((img_pred - imgs)^2) + perceptual_loss_ratio * mean(LPIPS(imgs, img_pred)); -> the reference's 6-tuple
+        (loss, pred, None, vis_loss.mean(), p_loss.mean(), None).  The loss terms and LPIPS run in f32 outside autocast.  One difference in
+        arithmetic: the reference's VGG runs under the caller's fp16 autocast; LPIPS here is exact f32 (models/lpips.py)."""
+        dtype = _act_dtype(self.precision, allow_f16=True)           # read before autocast is switched off below
+        use_mode = mask_ratio == 0.0
+
+        def posterior_tokens(lat):                                   # [B, N, (2) latent] -> [B, N, latent]
+            if self.kl_loss_weight is None:
+                return lat
+            post = DiagonalGaussianDistribution(lat.permute(0, 2, 1))
+            z = post.mode() if use_mode else (post.sample() if _eps is None else post.mean + post.std * _eps)
+            return z.permute(0, 2, 1)
+        if use_mode:
+            with torch.autocast(device_type="cuda", enabled=False):
+                x = self._embed(imgs, dtype)
+                x = self._run(self.blocks, x, dtype)
+                x = _LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps)
+                latent = posterior_tokens(_latent_map(self.to_latent, x))
+        else:
+            with torch.no_grad():
+                mom = self._encode(imgs)                             # [B, (2) latent, g, g]: the docking path (fused kernels where they apply)
+                latent = posterior_tokens(mom.reshape(mom.shape[0], mom.shape[1], -1).permute(0, 2, 1).float())
+        with torch.autocast(device_type="cuda", enabled=False):
+            x = _latent_map(self.from_latent, latent.contiguous())
+            x = _LinearFn.apply(x, self.decoder_embed.weight, self.decoder_embed.bias) + self.decoder_pos_embed
+            x = self._run(self.decoder_blocks, x, dtype)
+            x = _LayerNormFn.apply(x, self.decoder_norm.weight, self.decoder_norm.bias, self.decoder_norm.eps)
+            if isinstance(self.decoder_pred, conv_decoder_pred):
+                pred, pimg = self.decoder_pred(x, return_image=True)     # pimg IS unpatchify(pred): the head patchifies its image output
+            else:
+                pred = _linear(x, self.decoder_pred.weight, self.decoder_pred.bias)
+                pimg = self.unpatchify(pred)
+            target = imgs.float()
+            vis_loss = ((pimg - target) ** 2).mean()
+            if self.perceptual_loss is not None:
+                p_loss = self.perceptual_loss(target.contiguous(), pimg.contiguous()).mean()
+                loss = vis_loss + self.perceptual_loss_ratio * p_loss
+            else:
+                p_loss = torch.zeros_like(vis_loss)
+                loss = vis_loss
+        return loss, pred, None, vis_loss, p_loss, None
 
     def forward_vanilla(self, imgs, mask_ratio=0.75, visible_loss_ratio=0.5):
         """:756-790 -- the training forward under its reference name."""

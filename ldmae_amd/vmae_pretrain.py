@@ -1,15 +1,30 @@
 #!/usr/bin/env python3
 """VMAE pre-training driver on the HIP kernels -- counterpart of the reference's VMAE/main_pretrain.py:74-300 + VMAE/engine_pretrain.py:21-110
 (SURVEY 8f rank 4): image-folder input (main_pretrain.py:111-192), DistributedSampler + data-parallel gradient exchange (:204-215, 254-256),
-checkpoint save / resume with the position-embedding resize (VMAE/util/misc.py:468-531).  No LPIPS (`ldmae_mode`), no TensorBoard.
+checkpoint save / resume with the position-embedding resize (VMAE/util/misc.py:468-531).  No TensorBoard.
 
     python ldmae_amd/vmae_pretrain.py --data_path /data/imagenet --output_dir out --batch_size 64          # <data_path>/train/<class>/*.JPEG
     python ldmae_amd/vmae_pretrain.py --data_path /data/my_pngs --output_dir out                          # any tree of images
     python -m torch.distributed.run --nproc-per-node 8 ldmae_amd/vmae_pretrain.py --data_path ...          # one rank per GPU over RCCL
     python ldmae_amd/vmae_pretrain.py --synthetic --epochs 1 --steps-per-epoch 10 --batch_size 64
+    python ldmae_amd/vmae_pretrain.py --tune_decoder --perceptual_loss_ratio 10.0 --mask_ratio 0.0 --input_size 256 --batch_size 16 --accum_iter 16 \
+        --kl_loss_weight 0.0 --resume out/checkpoint-90.pth --lpips_vgg vgg16-397923af.pth --lpips_lin vgg.pth --data_path ...     # stage 3
 
-The command line takes main_pretrain.py:37-91's flag set (VMAE/train_ae.sh:26-46 parses; `--perceptual_loss_ratio`, `--tune_decoder`, `--pred_with_conv`,
-`--gradual_resol` are refused by name).  The posterior KL is the PRE-TRAINING tree's (round 6): VMAE/util/misc.py:103-125 differs from the tokenizer copy the
+The command line takes main_pretrain.py:37-91's flag set (VMAE/train_ae.sh:26-46 parses; `--pred_with_conv` and `--gradual_resol` are refused by name).
+
+STAGE 3 (train_ae.sh:84-106, decoder tuning at 256 x 256) is `--tune_decoder` TOGETHER WITH `--perceptual_loss_ratio R`: the model is built with
+ldmae_mode=True and perceptual_loss=LPIPS(differentiable=True) (models/lpips.py: the VGG16 / lin weights are the user's files -- `--lpips_vgg`, `--lpips_lin`,
+resolved as evaluate_tokenizer.py resolves them; a missing file is exit code 2 by name, nothing is downloaded), `--resume` restores the MODEL only (no
+optimizer, epoch or scaler: misc.py:525), and the epoch loop logs vis_loss and p_loss (mask_loss and kl_loss as 0, engine_pretrain.py:51-66).  Either flag alone
+is refused (exit 2): `--perceptual_loss_ratio` without `--tune_decoder` is the LPIPS term inside forward_vanilla, `--tune_decoder` alone has no loss to tune on
+here; neither is a shipped recipe of this package.  A quirk of the reference that is KEPT: the freeze (misc.py:148-157 set_for_tuning_decoder: mask_ratio := 0,
+every parameter whose name has neither `decoder` nor `from_latent` frozen) is applied only when `--mask_ratio` > 0 (main_pretrain.py:266-269).  The shipped
+script passes `--mask_ratio 0.0`, so with ITS flags nothing is frozen and the encoder is tuned along with the decoder, through the posterior mode; pass a
+positive mask ratio to tune the decoder alone.  Since the freeze itself resets mask_ratio to 0, every step of this driver calls the model with
+mask_ratio 0.0: the posterior MODE is decoded either way, and after a freeze the encoder still runs grad-enabled with frozen parameters (nothing upstream
+of from_latent requires grad, so no backward work is done there).  forward_ldmae's other branch (encoder under no_grad, posterior SAMPLED) is reached only
+by calling the model with a positive mask_ratio directly, as the reference's is.  The reference runs VGG under its fp16
+autocast; LPIPS here is exact f32.  The posterior KL is the PRE-TRAINING tree's (round 6): VMAE/util/misc.py:103-125 differs from the tokenizer copy the
 LDMAE drivers import -- no mean^2 term, and `--fixed_std s` (train_ae.sh:33 passes 1e-3) = KL against N(mean, s^2); `--kl_form tokenizer` restores the other.
 One deliberate difference: the reference parses `--visible_loss_ratio` and never passes it on (engine_pretrain.py:57 calls model(samples, mask_ratio=...): its
 runs train with the model's default 0.5); here the flag takes effect -- pass 0.5 (the default) to reproduce the reference's runs.
@@ -57,7 +72,7 @@ def no_decay(name, param):
 
 
 def build_optimizer(model, lr, weight_decay):
-    flat = FlatParams(model, group_fn=no_decay)
+    flat = FlatParams(model, group_fn=no_decay)        # frozen parameters (stage 3 with the freeze) sit behind the trainable slab: no gradient, no update
     if hasattr(model, "set_direct_param_grads") and os.environ.get("LDMAE_DIRECT_GRADS", "1") != "0":
         model.set_direct_param_grads(True)        # every .grad is a slab view from here on: the blocks add their gradients into it themselves
     return AdamWEMA(model, lr=lr, betas=(0.9, 0.95), weight_decay=weight_decay, ema_decay=0.0, flat=flat,
@@ -135,6 +150,9 @@ def train_one_epoch(model, loader, opt, epoch, args, log=print, scaler=None, red
         samples = samples.cuda(non_blocking=True)
         with torch.autocast("cuda", dtype=torch.float16 if args.precision == "fp16" else torch.bfloat16, enabled=args.precision in ("bf16", "fp16")):
             loss, _, _, vis_loss, mask_loss, kl_loss = model(samples, mask_ratio=args.mask_ratio, visible_loss_ratio=args.visible_loss_ratio)
+        p_loss = None
+        if getattr(model, "ldmae_mode", False):      # forward_ldmae's tuple: (loss, pred, None, vis_loss, p_loss, None)
+            p_loss, mask_loss = mask_loss, None
         bad.clamp_(min=(~torch.isfinite(loss.detach())).float())
         last = (it + 1) % args.accum_iter == 0
         if reducer is not None:
@@ -144,8 +162,10 @@ def train_one_epoch(model, loader, opt, epoch, args, log=print, scaler=None, red
             gscale = reducer.finish() if reducer is not None else 1.0          # 1 / world: the mean over the ranks, as DDP
             scaler.step(opt, gscale)
             opt.zero_grad()
-        stats = dict(loss=loss.detach(), vis_loss=vis_loss.detach(), mask_loss=mask_loss.detach(),
+        stats = dict(loss=loss.detach(), vis_loss=vis_loss.detach(), mask_loss=mask_loss.detach() if mask_loss is not None else 0.0,
                      kl_loss=kl_loss.detach() if kl_loss is not None else 0.0, lr=opt.lr)
+        if p_loss is not None:
+            stats["p_loss"] = p_loss.detach()
         if it % args.print_freq == 0:
             log(f"Epoch: [{epoch}] [{it}/{n}] " + "  ".join(f"{k}: {v:.6f}" for k, v in read(stats).items()))
     out = read(stats) if stats is not None else None
@@ -301,7 +321,8 @@ def save_model(args, epoch, model, opt, scaler, rank=0):
 
 def load_model(args, model, opt, scaler, log=print):
     """--resume (misc.py:501-531): state dict with strict=False, both position embeddings resized when the grid differs, optimizer / epoch /
-    scaler restored when present.  Returns the epoch to start from."""
+    scaler restored when present -- except for the decoder tuning (`--tune_decoder`: the model alone, misc.py:525; `opt` may be None then).  Returns the
+    epoch to start from."""
     if not args.resume:
         return args.start_epoch
     ck = torch.load(args.resume, map_location="cpu", weights_only=False)
@@ -319,7 +340,7 @@ def load_model(args, model, opt, scaler, log=print):
     ops.invalidate_weight_cache()
     log(f"Resume checkpoint {args.resume}")
     start = args.start_epoch
-    if "optimizer" in ck and "epoch" in ck:
+    if "optimizer" in ck and "epoch" in ck and not getattr(args, "tune_decoder", False):
         if not resized:                     # (a resized grid changes the slab: the moments of the old layout do not apply)
             # the reference's save_model (misc.py:474-481) and ours both write torch.optim.AdamW.state_dict(): its moments are mapped by parameter
             # order (AdamWEMA.load_torch_adamw_state); checkpoints of earlier rounds carry the slab state with its layout record.  A state that
@@ -334,6 +355,18 @@ def load_model(args, model, opt, scaler, log=print):
             scaler.load_state_dict(ck["scaler"])
         log("With optim & sched!")
     return start
+
+
+def set_for_tuning_decoder(args, model, log=print):
+    """misc.py:148-157: mask_ratio := 0 and every parameter whose name has neither `decoder` nor `from_latent` frozen.  Returns the frozen names."""
+    args.mask_ratio = 0.0
+    frozen = []
+    for name, p in model.named_parameters():
+        p.requires_grad = "decoder" in name or "from_latent" in name
+        if not p.requires_grad:
+            frozen.append(name)
+    log(f"decoder tuning: {len(frozen)} parameters frozen (names without 'decoder' / 'from_latent')")
+    return frozen
 
 
 def main(argv=None):
@@ -373,8 +406,10 @@ def main(argv=None):
     ap.add_argument("--no_cls", action="store_true", help="accepted (train_ae.sh passes it): this driver always builds the tokenizer without a class token")
     ap.add_argument("--smooth_output", action="store_true", help="accepted (train_ae.sh passes it): the RGB smoothing convolution is always on")
     ap.add_argument("--norm_pix_loss", action="store_true")
-    ap.add_argument("--perceptual_loss_ratio", type=float, default=None, help="LPIPS term (main_pretrain.py:189-203): NOT available (needs the VGG weights); refused if given")
-    ap.add_argument("--tune_decoder", action="store_true", help="stage 3 of train_ae.sh (decoder fine-tuning with LPIPS): out of scope, refused")
+    ap.add_argument("--perceptual_loss_ratio", type=float, default=None, help="weight of the LPIPS term; only together with --tune_decoder (stage 3 of train_ae.sh), refused alone")
+    ap.add_argument("--tune_decoder", action="store_true", help="stage 3 of train_ae.sh (decoder tuning with LPIPS); only together with --perceptual_loss_ratio, refused alone")
+    ap.add_argument("--lpips_vgg", type=str, default=None, help="stage 3: torchvision vgg16-397923af.pth (default: $LDMAE_LPIPS_VGG, torch.hub)")
+    ap.add_argument("--lpips_lin", type=str, default=None, help="stage 3: taming's LPIPS vgg.pth (default: $LDMAE_LPIPS_LIN, the reference's path)")
     ap.add_argument("--pred_with_conv", action="store_true", help="refused: not a shipped form")
     ap.add_argument("--gradual_resol", action="store_true", help="refused: not a shipped form")
     ap.add_argument("--log_dir", default=None, help="accepted and ignored (TensorBoard is out of scope)")
@@ -387,10 +422,19 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not args.synthetic and not args.data_path:
         ap.error("--data_path (an image folder) or --synthetic")
-    refused = [n for n in ("tune_decoder", "pred_with_conv", "gradual_resol") if getattr(args, n)] + (["perceptual_loss_ratio"] if args.perceptual_loss_ratio is not None else [])
+    stage3 = args.tune_decoder and args.perceptual_loss_ratio is not None
+    refused = [n for n in ("pred_with_conv", "gradual_resol") if getattr(args, n)]
+    if not stage3:
+        refused += (["tune_decoder"] if args.tune_decoder else []) + (["perceptual_loss_ratio"] if args.perceptual_loss_ratio is not None else [])
     if refused or args.device != "cuda":
-        ap.error(f"not available in ldmae_amd/vmae_pretrain.py: {refused or args.device} (LPIPS needs the VGG weights -- SURVEY 2.1 #18 marks the LPIPS "
-                 "decoder fine-tuning OUT; pred_with_conv / gradual_resol are not shipped forms)")
+        ap.error(f"not available in ldmae_amd/vmae_pretrain.py: {refused or args.device} (--tune_decoder and --perceptual_loss_ratio only TOGETHER: stage 3 of "
+                 "train_ae.sh; pred_with_conv / gradual_resol are not shipped forms)")
+    if stage3:
+        from ldmae_amd.models import lpips as lpips_mod
+        try:                                                                  # before anything touches the GPU; never downloads
+            lpips_mod.resolve_weights(args.lpips_vgg, args.lpips_lin)
+        except FileNotFoundError as ex:
+            ap.error(str(ex))
     import torch.distributed as dist
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     # LDMAE_DIST_BACKEND=gloo + LDMAE_DEVICE=0: several ranks share ONE GPU (rehearsal of the multi-rank launch on a 1-GPU box), as train_accum.py
@@ -419,13 +463,27 @@ def main(argv=None):
         loader = torch.utils.data.DataLoader(dataset, sampler=sampler, batch_size=args.batch_size, num_workers=args.num_workers, pin_memory=args.pin_mem,
                                              drop_last=True, multiprocessing_context="forkserver" if args.num_workers > 0 else None)
     torch.manual_seed(args.seed)                                              # every rank builds the same initial weights
-    model = getattr(models_mae, args.model)(ldmae_mode=False, no_cls=True, kl_loss_weight=args.kl_loss_weight, smooth_output=True, norm_pix_loss=args.norm_pix_loss,
-                                            img_size=args.input_size, fixed_std=args.fixed_std).cuda()          # main_pretrain.py:193-205
+    extra = {}
+    if stage3:
+        log(f"Using Perceptual loss with ratio = {args.perceptual_loss_ratio}")
+        extra = dict(perceptual_loss=lpips_mod.LPIPS(args.lpips_vgg, args.lpips_lin, device=torch.device("cuda", local), differentiable=True),
+                     perceptual_loss_ratio=args.perceptual_loss_ratio)
+    model = getattr(models_mae, args.model)(ldmae_mode=stage3, no_cls=True, kl_loss_weight=args.kl_loss_weight, smooth_output=True, norm_pix_loss=args.norm_pix_loss,
+                                            img_size=args.input_size, fixed_std=args.fixed_std, **extra).cuda()  # main_pretrain.py:193-205
     model.kl_form = args.kl_form          # the pre-training tree's posterior KL (VMAE/util/misc.py) unless asked otherwise
     torch.manual_seed(args.seed + rank)
-    opt = build_optimizer(model, args.lr, args.weight_decay)
     scaler = LossScaler(enabled=args.precision in ("bf16", "fp16"))           # main_pretrain.py:260: loss_scaler = NativeScaler()
-    start = load_model(args, model, opt, scaler, log)
+    if stage3:
+        # the model alone is restored, then frozen (only with --mask_ratio > 0: main_pretrain.py:266-269), then laid out: the optimizer's slab holds what trains
+        start = load_model(args, model, None, None, log)
+        if args.mask_ratio > 0.0:
+            set_for_tuning_decoder(args, model, log)
+        else:
+            log("No layers are frozen; training the entire model.")
+        opt = build_optimizer(model, args.lr, args.weight_decay)
+    else:
+        opt = build_optimizer(model, args.lr, args.weight_decay)
+        start = load_model(args, model, opt, scaler, log)
     reducer = GradBucketReducer(opt.flat) if world > 1 else None
     if reducer is not None:
         from ldmae_amd import ops
