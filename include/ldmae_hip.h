@@ -419,6 +419,31 @@ int ldmae_lpips_layer_bwd(const float* f, const float* lin_w, const float* g, fl
                           int accumulate, void* stream);
 int ldmae_lpips_prep_bwd(const float* g, float* out, int B, int H, int W, void* stream);
 
+/* ---- convolutional KL-VAE tokenizers (tokenizer/autoencoder.py: the LDM Encoder / Decoder), f32 NHWC, forward only -----------------------
+ * groupnorm_stats: mean / rstd [B, G] of x [B, HW, C]: per (image, group) mean and rstd = 1 / sqrt(var + eps), biased variance over the
+ * HW * (C / G) elements of the group; two passes (mean, then the mean of (x - mean)^2), blocked summation (csrc/conv_vae.hip).
+ * groupnorm_apply: out = gamma (x - mean) rstd + beta, then y * sigmoid(y) when silu != 0.
+ * conv3x3_vae: 3x3 implicit-GEMM convolution on the exact-f32 MFMA; x [B, H, W, Cin] (Cin % 4 == 0), w [Cout, 3, 3, Cin], out [B, Ho, Wo, Cout]
+ * = conv + bias (may be NULL) + res (may be NULL; the output's shape).  mode PLAIN: stride 1, pad 1.  NORM_ACT: the operand is
+ * groupnorm_apply(x) computed while it is gathered (mean / rstd [B, G], gamma / beta [Cin], silu as above), stride 1, pad 1; taps outside
+ * the image contribute exactly 0.  DOWN: stride 2, zero pad right and bottom only, Ho = (H + 1 - 3) / 2 + 1.  UP: the operand is the
+ * nearest-neighbour 2x enlargement of x, read at (y >> 1, x >> 1) and never stored; stride 1, pad 1, Ho = 2 H.  mean, rstd, gamma, beta, G
+ * and silu are read in NORM_ACT only.
+ * conv1x1_res: out [M, Cout] = x [M, Cin] w [Cout, Cin]^T + bias + res, the same epilogue on a 1x1 convolution.
+ * softmax_rows: in place, s[r, :cols] = softmax(scale * s[r, :cols]) and s[r, cols:ld] = 0 (rows padded for the GEMM that follows). */
+#define LDMAE_VAE_PLAIN 0
+#define LDMAE_VAE_NORM_ACT 1
+#define LDMAE_VAE_DOWN 2
+#define LDMAE_VAE_UP 3
+int ldmae_groupnorm_stats_nhwc_f32(const float* x, float* mean, float* rstd, int B, int HW, int C, int G, float eps, void* stream);
+int ldmae_groupnorm_apply_nhwc_f32(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* out, int B,
+                                   int HW, int C, int G, int silu, void* stream);
+int ldmae_conv3x3_vae_nhwc_f32(int mode, const float* x, const float* w, const float* bias, const float* res, const float* mean, const float* rstd,
+                               const float* gamma, const float* beta, int G, int silu, float* out, int B, int H, int W, int Cin, int Cout,
+                               void* stream);
+int ldmae_conv1x1_res_nhwc_f32(const float* x, const float* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout, void* stream);
+int ldmae_softmax_rows_f32(float* s, int ld, int rows, int cols, float scale, void* stream);
+
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */
 int ldmae_prof_enable(int on);

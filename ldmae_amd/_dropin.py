@@ -30,6 +30,9 @@ import os
 import sys
 
 MIRRORED = ("models", "transport", "tokenizer", "datasets")
+# Present in this tree (the convolutional KL-VAE tokenizers) but NOT aliased: the drivers refuse the SD-VAE model types by name, so a reference
+# driver that imports these names keeps getting the reference's own files, as before they existed here.  They are reached as ldmae_amd.tokenizer.*.
+REFERENCE_SERVED = ("tokenizer.autoencoder", "tokenizer.vavae", "tokenizer.marvae", "tokenizer.sdvae")
 _PKG = "ldmae_amd"
 
 
@@ -57,7 +60,7 @@ class _Finder(importlib.abc.MetaPathFinder):
             return None
         tgt = f"{_PKG}.{fullname}"
         try:
-            ours = importlib.util.find_spec(tgt)
+            ours = None if fullname in REFERENCE_SERVED else importlib.util.find_spec(tgt)
         except (ImportError, ValueError):
             ours = None
         if ours is not None:

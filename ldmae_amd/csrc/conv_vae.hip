@@ -1,0 +1,311 @@
+// The convolutional KL-VAE tokenizers (tokenizer/autoencoder.py of the reference: the LDM Encoder / Decoder), NHWC f32, forward only.
+//   - GroupNorm statistics per (image, group) and a plain normalise(+SiLU) pass;
+//   - 3x3 implicit-GEMM convolution on conv_igemm_f32_mainloop whose operand gather does the work of the passes around it: norm-act
+//     (silu(gamma (x - mean) rstd + beta), the conv1 / conv2 of ResnetBlock and conv_out), down (stride 2, zero pad right and bottom only) and
+//     up (the operand is read at (y >> 1, x >> 1) of the half-size tensor: nearest 2x upsampling that is never written); epilogue bias +
+//     residual;
+//   - the same epilogue on a 1x1 convolution (proj_out of AttnBlock);
+//   - the row softmax between the two f32 GEMMs of the single-head attention of AttnBlock.
+#include "common.h"
+#include "conv_igemm_f32.h"
+
+// One definition of the normalised operand for the fused gather and the stand-alone pass.
+template <bool SILU>
+__device__ __forceinline__ float gn_act(float x, float mu, float rs, float ga, float be) {
+  const float y = fmaf((x - mu) * rs, ga, be);
+  return SILU ? y * fast_sigmoid(y) : y;
+}
+
+// ------------------------------------------------------------------------------------------------ GroupNorm statistics
+// One block of 256 threads per (image, group); a group is HW pixels x cpg adjacent channels.  Two passes over the group (the second one hits
+// the L2): mean first, then the biased variance as the mean of (x - mean)^2, so no cancellation of large sums.  Summation order of either
+// pass (blocked, never one serial chain over the group): the cpg channels of a pixel are added first; a thread adds the pixel sums of pixels
+// tid, tid + 256, ... serially (at most HW / 256 terms); the 64 lanes of a wave are joined by a butterfly tree, the four waves pairwise.
+__device__ __forceinline__ float block_sum_256(float v, float* sh) {
+  v = wave_sum(v);
+  const int tid = threadIdx.x;
+  __syncthreads();                                         // sh may still be read from the previous reduction
+  if ((tid & 63) == 0) sh[tid >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ mean, float* __restrict__ rstd, int HW, int C,
+                                                       int G, float eps) {
+  __shared__ float sh[4];
+  const int cpg = C / G, b = blockIdx.x / G, g = blockIdx.x % G, tid = threadIdx.x;
+  const float* xb = x + (size_t)b * HW * C + (size_t)g * cpg;
+  const float inv_n = 1.f / ((float)HW * (float)cpg);
+  float s = 0.f;
+  for (int p = tid; p < HW; p += 256) {
+    const float* px = xb + (size_t)p * C;
+    float t = 0.f;
+    if (VEC) {
+      for (int j = 0; j < cpg; j += 4) { const float4 v = *(const float4*)(px + j); t += (v.x + v.y) + (v.z + v.w); }
+    } else {
+      for (int j = 0; j < cpg; ++j) t += px[j];
+    }
+    s += t;
+  }
+  const float mu = block_sum_256(s, sh) * inv_n;
+  float q = 0.f;
+  for (int p = tid; p < HW; p += 256) {
+    const float* px = xb + (size_t)p * C;
+    float t = 0.f;
+    if (VEC) {
+      for (int j = 0; j < cpg; j += 4) {
+        const float4 v = *(const float4*)(px + j);
+        const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
+        t += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+      }
+    } else {
+      for (int j = 0; j < cpg; ++j) { const float d = px[j] - mu; t += d * d; }
+    }
+    q += t;
+  }
+  const float var = block_sum_256(q, sh) * inv_n;
+  if (tid == 0) {
+    mean[blockIdx.x] = mu;
+    rstd[blockIdx.x] = 1.f / sqrtf(var + eps);
+  }
+}
+
+extern "C" int ldmae_groupnorm_stats_nhwc_f32(const float* x, float* mean, float* rstd, int B, int HW, int C, int G, float eps, void* stream) {
+  LDMAE_REQUIRE(x && mean && rstd, "groupnorm_stats_nhwc_f32: null pointer");
+  LDMAE_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0 && eps > 0.f, "groupnorm_stats_nhwc_f32: B=%d HW=%d C=%d G=%d eps=%g must be positive", B, HW, C, G, eps);
+  LDMAE_REQUIRE(C % G == 0, "groupnorm_stats_nhwc_f32: %d channels are not divisible into %d groups", C, G);
+  LDMAE_REQUIRE((long)B * G < (1L << 31) && (long)HW * (C / G) < (1L << 31), "groupnorm_stats_nhwc_f32: problem too large");
+  const bool vec = (C / G) % 4 == 0 && ((uintptr_t)x & 15) == 0;
+  if (vec) hipLaunchKernelGGL(gn_stats_kernel<true>, dim3(B * G), dim3(256), 0, as_stream(stream), x, mean, rstd, HW, C, G, eps);
+  else hipLaunchKernelGGL(gn_stats_kernel<false>, dim3(B * G), dim3(256), 0, as_stream(stream), x, mean, rstd, HW, C, G, eps);
+  LDMAE_CHECK_LAUNCH("groupnorm_stats_nhwc_f32");
+  return 0;
+}
+
+// out = gamma (x - mean) rstd + beta, then SiLU when asked: the GroupNorm in front of q / k / v (no SiLU), and the two-pass form of norm-act.
+template <bool SILU>
+__global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ out, long n,
+                                                       int HW, int C, int G) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % C), cpg = C / G;
+  const long b = i / ((long)HW * C);
+  const int s = (int)b * G + c / cpg;
+  out[i] = gn_act<SILU>(x[i], mean[s], rstd[s], gamma[c], beta[c]);
+}
+
+extern "C" int ldmae_groupnorm_apply_nhwc_f32(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* out,
+                                              int B, int HW, int C, int G, int silu, void* stream) {
+  LDMAE_REQUIRE(x && mean && rstd && gamma && beta && out, "groupnorm_apply_nhwc_f32: null pointer");
+  LDMAE_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0, "groupnorm_apply_nhwc_f32: B=%d HW=%d C=%d G=%d must be positive", B, HW, C, G);
+  LDMAE_REQUIRE(C % G == 0, "groupnorm_apply_nhwc_f32: %d channels are not divisible into %d groups", C, G);
+  const long n = (long)B * HW * C;
+  LDMAE_REQUIRE((n + 255) / 256 < (1L << 31) && (long)B * G < (1L << 31), "groupnorm_apply_nhwc_f32: problem too large");
+  if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, mean, rstd, gamma, beta, out, n, HW, C, G);
+  else hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, mean, rstd, gamma, beta, out, n, HW, C, G);
+  LDMAE_CHECK_LAUNCH("groupnorm_apply_nhwc_f32");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ convolution
+// M = B*Ho*Wo output pixels, N = Cout, K = ks*ks*Cin (ks = 3, or 1 for the residual 1x1).  The gather works in a VIRTUAL input frame of
+// Hv x Wv pixels: the stored tensor [B, H, W, Cin] itself, or (up) its nearest-neighbour 2x enlargement, read at (iy >> 1, ix >> 1).  A tap
+// outside the virtual frame contributes exactly 0 in every mode: under norm-act the reference pads the ACTIVATED tensor, so the zero is
+// returned without going through gn_act.
+struct VaeGeom {
+  int B, H, W, Cin;                   // stored input
+  int Hv, Wv, up;                     // virtual frame; up = 1: Hv = 2 H, Wv = 2 W
+  int Ho, Wo, Cout, ks, stride, pad;
+  int M, K, G, cpg;
+};
+
+// NORM 0: raw operand; 1: norm-act with cpg % 4 == 0 (the four channels of a float4 share a group); 2: norm-act, any cpg.
+template <int NORM, bool SILU>
+__global__ __launch_bounds__(CV_NT) void conv_vae_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                         const float* __restrict__ res, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ out,
+                                                         VaeGeom g) {
+  __shared__ __attribute__((aligned(16))) float As[2][CV_BM * CV_LD];
+  __shared__ __attribute__((aligned(16))) float Bs[2][CV_BN * CV_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int tiles_n = (g.Cout + CV_BN - 1) / CV_BN;
+  const int m0 = (int)(blockIdx.x / tiles_n) * CV_BM, n0 = (int)(blockIdx.x % tiles_n) * CV_BN;
+  const int lr = tid >> 2, lc = (tid & 3) * 4;
+  int iy0[2], ix0[2], sb[2];
+  const float* xb[2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
+    const int ox = m % g.Wo, t = m / g.Wo, oy = t % g.Ho, b = t / g.Ho;
+    iy0[p] = oy * g.stride - g.pad;
+    ix0[p] = ox * g.stride - g.pad;
+    xb[p] = x + (size_t)b * g.H * g.W * g.Cin;
+    sb[p] = b * g.G;
+  }
+  const float* wrow = w + (size_t)min(n0 + lr, g.Cout - 1) * g.K;
+  // (tap, channel) of this thread's first k, advanced by BK per step without divisions; Cin % 4 == 0, so a float4 never straddles taps
+  int ci = lc, kx = 0, ky = 0;
+  while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+  // norm-act: gamma / beta of the four channels and their group, the same for both A rows of a step
+  float4 ga = make_float4(0.f, 0.f, 0.f, 0.f), be = ga;
+  int gi[4] = {0, 0, 0, 0};
+  auto coef = [&]() {
+    if (NORM != 0 && ky < g.ks) {
+      ga = *(const float4*)(gamma + ci);
+      be = *(const float4*)(beta + ci);
+      if (NORM == 1) {
+        gi[0] = ci / g.cpg;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gi[j] = (ci + j) / g.cpg;
+      }
+    }
+  };
+  coef();
+  auto fetch_a = [&](int p, int) -> float4 {
+    const int iy = iy0[p] + ky, ix = ix0[p] + kx;
+    if (ky < g.ks && (unsigned)iy < (unsigned)g.Hv && (unsigned)ix < (unsigned)g.Wv) {
+      float4 v = *(const float4*)(xb[p] + ((size_t)(iy >> g.up) * g.W + (ix >> g.up)) * g.Cin + ci);
+      if (NORM == 1) {
+        const float mu = mean[sb[p] + gi[0]], rs = rstd[sb[p] + gi[0]];
+        v = make_float4(gn_act<SILU>(v.x, mu, rs, ga.x, be.x), gn_act<SILU>(v.y, mu, rs, ga.y, be.y), gn_act<SILU>(v.z, mu, rs, ga.z, be.z),
+                        gn_act<SILU>(v.w, mu, rs, ga.w, be.w));
+      } else if (NORM == 2) {
+        v = make_float4(gn_act<SILU>(v.x, mean[sb[p] + gi[0]], rstd[sb[p] + gi[0]], ga.x, be.x),
+                        gn_act<SILU>(v.y, mean[sb[p] + gi[1]], rstd[sb[p] + gi[1]], ga.y, be.y),
+                        gn_act<SILU>(v.z, mean[sb[p] + gi[2]], rstd[sb[p] + gi[2]], ga.z, be.z),
+                        gn_act<SILU>(v.w, mean[sb[p] + gi[3]], rstd[sb[p] + gi[3]], ga.w, be.w));
+      }
+      return v;
+    }
+    return make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto fetch_b = [&](int k0) -> float4 {
+    const int k = k0 + lc;                                 // K % 4 == 0
+    if (k < g.K) return *(const float4*)(wrow + k);
+    return make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto advance = [&]() {
+    ci += CV_BK;
+    while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+    coef();
+  };
+
+  f32x4 acc[4][2];
+  conv_igemm_f32_mainloop(As, Bs, (g.K + CV_BK - 1) / CV_BK, fetch_a, fetch_b, advance, acc);
+  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
+  // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block; out = acc + bias + res
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = n0 + wn * 32 + j * 16 + r16;
+    if (n >= g.Cout) continue;
+    const float bn = bias ? bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wm * 64 + i * 16 + q4 + r;
+        if (m < g.M) {
+          float v = acc[i][j][r] + bn;
+          if (res) v += res[(size_t)m * g.Cout + n];
+          out[(size_t)m * g.Cout + n] = v;
+        }
+      }
+  }
+}
+
+static int launch_conv_vae(const char* name, int norm, int silu, const float* x, const float* w, const float* bias, const float* res, const float* mean,
+                           const float* rstd, const float* gamma, const float* beta, float* out, const VaeGeom& g, void* stream) {
+  const unsigned grid = cdiv(g.M, CV_BM) * cdiv(g.Cout, CV_BN);
+  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * g.M * g.Cout * g.K) : -1;
+#define LDMAE_VAE_LAUNCH(NORM, SILU) \
+  hipLaunchKernelGGL((conv_vae_kernel<NORM, SILU>), dim3(grid), dim3(CV_NT), 0, as_stream(stream), x, w, bias, res, mean, rstd, gamma, beta, out, g)
+  if (norm == 0) LDMAE_VAE_LAUNCH(0, false);
+  else if (norm == 1 && silu) LDMAE_VAE_LAUNCH(1, true);
+  else if (norm == 1) LDMAE_VAE_LAUNCH(1, false);
+  else if (silu) LDMAE_VAE_LAUNCH(2, true);
+  else LDMAE_VAE_LAUNCH(2, false);
+#undef LDMAE_VAE_LAUNCH
+  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
+  LDMAE_CHECK_LAUNCH(name);
+  return 0;
+}
+
+extern "C" int ldmae_conv3x3_vae_nhwc_f32(int mode, const float* x, const float* w, const float* bias, const float* res, const float* mean,
+                                          const float* rstd, const float* gamma, const float* beta, int G, int silu, float* out, int B, int H, int W,
+                                          int Cin, int Cout, void* stream) {
+  LDMAE_REQUIRE(mode == LDMAE_VAE_PLAIN || mode == LDMAE_VAE_NORM_ACT || mode == LDMAE_VAE_DOWN || mode == LDMAE_VAE_UP,
+                "conv3x3_vae_nhwc_f32: mode %d (0 plain, 1 norm-act, 2 down, 3 up)", mode);
+  LDMAE_REQUIRE(x && w && out, "conv3x3_vae_nhwc_f32: null pointer (only bias and res may be NULL)");
+  LDMAE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_vae_nhwc_f32: B=%d H=%d W=%d Cin=%d Cout=%d must be positive", B, H, W, Cin, Cout);
+  LDMAE_REQUIRE(Cin % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv3x3_vae_nhwc_f32: Cin=%d must be a multiple of 4 and x, w 16-B aligned",
+                Cin);
+  VaeGeom g{};
+  g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.ks = 3;
+  g.Hv = H; g.Wv = W; g.up = 0; g.stride = 1; g.pad = 1; g.Ho = H; g.Wo = W; g.G = 1; g.cpg = Cin;
+  int norm = 0;
+  if (mode == LDMAE_VAE_NORM_ACT) {
+    LDMAE_REQUIRE(mean && rstd && gamma && beta && G > 0, "conv3x3_vae_nhwc_f32: norm-act needs mean, rstd, gamma, beta and a positive group count");
+    LDMAE_REQUIRE(Cin % G == 0, "conv3x3_vae_nhwc_f32: %d channels are not divisible into %d groups", Cin, G);
+    LDMAE_REQUIRE(((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0, "conv3x3_vae_nhwc_f32: gamma and beta must be 16-B aligned");
+    g.G = G; g.cpg = Cin / G;
+    norm = g.cpg % 4 == 0 ? 1 : 2;
+  } else if (mode == LDMAE_VAE_DOWN) {
+    LDMAE_REQUIRE(H >= 2 && W >= 2, "conv3x3_vae_nhwc_f32: down needs at least 2 x 2 pixels");
+    g.stride = 2; g.pad = 0; g.Ho = (H + 1 - 3) / 2 + 1; g.Wo = (W + 1 - 3) / 2 + 1;      // pad (0, 1, 0, 1): right and bottom only
+  } else if (mode == LDMAE_VAE_UP) {
+    g.up = 1; g.Hv = 2 * H; g.Wv = 2 * W; g.Ho = 2 * H; g.Wo = 2 * W;
+  }
+  const long M = (long)B * g.Ho * g.Wo, K = 9L * Cin;
+  LDMAE_REQUIRE(M < (1L << 31) && M * Cout < (1L << 40) && (long)B * H * W * Cin < (1L << 40) && K < (1L << 24), "conv3x3_vae_nhwc_f32: problem too large");
+  g.M = (int)M; g.K = (int)K;
+  return launch_conv_vae("conv3x3_vae_nhwc_f32", norm, silu, x, w, bias, res, mean, rstd, gamma, beta, out, g, stream);
+}
+
+extern "C" int ldmae_conv1x1_res_nhwc_f32(const float* x, const float* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout,
+                                          void* stream) {
+  LDMAE_REQUIRE(x && w && out, "conv1x1_res_nhwc_f32: null pointer (only bias and res may be NULL)");
+  LDMAE_REQUIRE(M > 0 && Cin > 0 && Cout > 0, "conv1x1_res_nhwc_f32: M=%d Cin=%d Cout=%d must be positive", M, Cin, Cout);
+  LDMAE_REQUIRE(Cin % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv1x1_res_nhwc_f32: Cin=%d must be a multiple of 4 and x, w 16-B aligned",
+                Cin);
+  LDMAE_REQUIRE((long)M * Cout < (1L << 40) && (long)M * Cin < (1L << 40) && Cin < (1 << 24), "conv1x1_res_nhwc_f32: problem too large");
+  VaeGeom g{};
+  g.B = 1; g.H = 1; g.W = M; g.Cin = Cin; g.Cout = Cout; g.ks = 1;                          // M pixels of one row: no tap ever leaves the frame
+  g.Hv = 1; g.Wv = M; g.up = 0; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = M; g.G = 1; g.cpg = Cin;
+  g.M = M; g.K = Cin;
+  return launch_conv_vae("conv1x1_res_nhwc_f32", 0, 0, x, w, bias, res, nullptr, nullptr, nullptr, nullptr, out, g, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ row softmax
+// In place on s [rows, ld]: s[r, :cols] = softmax(scale * s[r, :cols]); columns [cols, ld) are set to 0, so the rows can be the K-padded
+// operand of the f32 GEMM that follows.  One block per row: maximum, sum of exp(v - max) (expf, not the fast unit), one true division.
+__global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ s, int ld, int cols, float scale) {
+  __shared__ float sh[4];
+  float* row = s + (size_t)blockIdx.x * ld;
+  const int tid = threadIdx.x;
+  float mx = -INFINITY;
+  for (int j = tid; j < cols; j += 256) mx = fmaxf(mx, row[j] * scale);
+  mx = wave_max(mx);
+  if ((tid & 63) == 0) sh[tid >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  float sum = 0.f;
+  for (int j = tid; j < cols; j += 256) {
+    const float e = expf(row[j] * scale - mx);
+    row[j] = e;
+    sum += e;
+  }
+  sum = block_sum_256(sum, sh);
+  for (int j = tid; j < ld; j += 256) row[j] = j < cols ? row[j] / sum : 0.f;
+}
+
+extern "C" int ldmae_softmax_rows_f32(float* s, int ld, int rows, int cols, float scale, void* stream) {
+  LDMAE_REQUIRE(s && rows > 0 && cols > 0 && ld >= cols, "softmax_rows_f32: null pointer, empty problem or ld=%d < cols=%d", ld, cols);
+  LDMAE_REQUIRE((long)rows * ld < (1L << 40), "softmax_rows_f32: problem too large");      // rows is the grid's x extent: an int always fits
+  hipLaunchKernelGGL(softmax_rows_kernel, dim3(rows), dim3(256), 0, as_stream(stream), s, ld, cols, scale);
+  LDMAE_CHECK_LAUNCH("softmax_rows_f32");
+  return 0;
+}

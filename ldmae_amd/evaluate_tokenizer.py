@@ -214,6 +214,18 @@ def evaluate_tokenizer(args, cfg, log=print_with_prefix):
         latent_std = None
 
     dataset = SyntheticImages(args.synthetic) if args.synthetic else _image_folder(args.data_path)
+    res, save_dir, ref_path = reconstruct_and_score(args, model_type, lambda images: model.encode(images).latent_dist.mode(),
+                                                    lambda latents: model.decode(latents).sample, dataset, latent_std, lpips, device, rank, world, log)
+    if distributed:
+        dist.destroy_process_group()
+    return res, save_dir, ref_path
+
+
+def reconstruct_and_score(args, model_type, encode, decode, dataset, latent_std, lpips, device, rank=0, world=1, log=print_with_prefix):
+    """The evaluation loop for any tokenizer: encode(images [B, 3, H, W] in [-1, 1]) -> latents, + epsilon * randn * latent_std, decode(latents)
+    -> images; PNGs, LPIPS / SSIM / PSNR, rFID on rank 0 and the JSON line.  Returns (metrics, decoded dir, reference dir)."""
+    from ldmae_amd import fid, ops
+    from ldmae_amd.metrics import psnr_from_sse, ssim
     sampler = DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=False)
     loader = DataLoader(dataset, batch_size=args.batch_size, shuffle=False, sampler=sampler, num_workers=args.num_workers,
                         pin_memory=True, multiprocessing_context="forkserver" if args.num_workers > 0 else None)
@@ -233,11 +245,11 @@ def evaluate_tokenizer(args, cfg, log=print_with_prefix):
     with torch.no_grad(), ThreadPoolExecutor(max_workers=PNG_THREADS) as pool:
         for images, _ in loader:
             images = images.to(device, non_blocking=True).float().contiguous()
-            latents = model.encode(images).latent_dist.mode().to(torch.float32)
+            latents = encode(images).to(torch.float32)
             if args.epsilon != 0:
                 noise = torch.randn(latents.shape, generator=gen, device=device, dtype=torch.float32)
                 latents = latents + args.epsilon * noise * latent_std
-            decoded = model.decode(latents).sample.float().contiguous()
+            decoded = decode(latents).float().contiguous()
             lpips_vals.append(lpips(decoded, images).mean())
             ssim_vals.append(ssim(decoded, images, data_range=(-1.0, 1.0)))
             dec8, ref8, sse = ops.recon_quantize_sse(decoded, images)
@@ -276,8 +288,6 @@ def evaluate_tokenizer(args, cfg, log=print_with_prefix):
         print(json.dumps({"metric": "tokenizer_eval", "model_type": model_type, **res}), flush=True)
     if world > 1:
         dist.barrier()
-    if distributed:
-        dist.destroy_process_group()
     return res, save_dir, ref_path
 
 

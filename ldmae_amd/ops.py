@@ -1320,3 +1320,129 @@ def sse_u8(a, b):
     ws = workspace(L.load().ldmae_sse_workspace_bytes(B, n), a.device, "sse")
     call("ldmae_sse_u8", ptr(a), ptr(b), ptr(sse), B, n, ptr(ws), stream())
     return sse
+
+
+# ----------------------------------------------------------------------------- convolutional KL-VAE tokenizers (csrc/conv_vae.hip), NHWC f32
+VAE_PLAIN, VAE_NORM_ACT, VAE_DOWN, VAE_UP = 0, 1, 2, 3
+VAE_GROUPS, VAE_EPS = 32, 1e-6          # the reference's Normalize: GroupNorm(32, C, eps=1e-6)
+
+
+def _vec(t, what, n):
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise RuntimeError(f"{what}: need a contiguous f32 [{n}] tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def groupnorm_stats_nhwc(x, groups=VAE_GROUPS, eps=VAE_EPS):
+    """(mean, rstd) f32 [B, groups] of x [B, H, W, C]: biased variance over the H * W * (C / groups) elements of every (image, group)."""
+    _nhwc(x, "groupnorm_stats_nhwc")
+    B, H, W, C = x.shape
+    mean = torch.empty(B, groups, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    call("ldmae_groupnorm_stats_nhwc_f32", ptr(x), ptr(mean), ptr(rstd), B, H * W, C, groups, float(eps), stream())
+    return mean, rstd
+
+
+def _stats(stats, B, groups, what):
+    mean, rstd = stats
+    for t in (mean, rstd):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, groups) or not t.is_contiguous():
+            raise RuntimeError(f"{what}: mean / rstd must be contiguous f32 [{B}, {groups}], got {tuple(t.shape)} {t.dtype}")
+    return mean, rstd
+
+
+def groupnorm_apply_nhwc(x, stats, gamma, beta, silu=False, out=None):
+    """gamma (x - mean) rstd + beta of x [B, H, W, C] from groupnorm_stats_nhwc's (mean, rstd); silu=True: y * sigmoid(y) of that."""
+    _nhwc(x, "groupnorm_apply_nhwc")
+    B, H, W, C = x.shape
+    mean, rstd = _stats(stats, B, stats[0].shape[1], "groupnorm_apply_nhwc")
+    if out is None:
+        out = torch.empty_like(x)
+    _nhwc(out, "groupnorm_apply_nhwc out")
+    _same(out, x, "groupnorm_apply_nhwc")
+    call("ldmae_groupnorm_apply_nhwc_f32", ptr(x), ptr(mean), ptr(rstd), ptr(_vec(gamma, "groupnorm_apply_nhwc gamma", C)),
+         ptr(_vec(beta, "groupnorm_apply_nhwc beta", C)), ptr(out), B, H * W, C, mean.shape[1], 1 if silu else 0, stream())
+    return out
+
+
+def conv3x3_vae_nhwc(x, w, bias=None, mode=VAE_PLAIN, res=None, stats=None, gamma=None, beta=None, silu=True):
+    """3x3 convolution of x [B, H, W, Cin] with w [Cout, 3, 3, Cin] -> [B, Ho, Wo, Cout], + bias + res (the output's shape).
+    mode VAE_PLAIN: stride 1, pad 1.  VAE_NORM_ACT: the operand is groupnorm_apply_nhwc(x, stats, gamma, beta, silu), computed while it is
+    gathered; out-of-image taps are 0.  VAE_DOWN: stride 2, zero pad right and bottom only.  VAE_UP: nearest 2x upsampling, then stride 1, pad 1."""
+    _nhwc(x, "conv3x3_vae_nhwc")
+    B, H, W, Cin = x.shape
+    if w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, Cin) or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError(f"conv3x3_vae_nhwc: weight {tuple(w.shape)} {w.dtype} is not a contiguous f32 [Cout, 3, 3, {Cin}]")
+    Cout = w.shape[0]
+    if mode == VAE_DOWN:
+        Ho, Wo = (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
+        if Ho < 1 or Wo < 1:
+            raise RuntimeError(f"conv3x3_vae_nhwc: down needs at least 2 x 2 pixels, got {H} x {W}")
+    elif mode == VAE_UP:
+        Ho, Wo = 2 * H, 2 * W
+    elif mode in (VAE_PLAIN, VAE_NORM_ACT):
+        Ho, Wo = H, W
+    else:
+        raise RuntimeError(f"conv3x3_vae_nhwc: mode {mode}")
+    mean = rstd = None
+    groups = 0
+    if mode == VAE_NORM_ACT:
+        if stats is None or gamma is None or beta is None:
+            raise RuntimeError("conv3x3_vae_nhwc: norm-act needs stats, gamma and beta")
+        groups = stats[0].shape[1]
+        mean, rstd = _stats(stats, B, groups, "conv3x3_vae_nhwc")
+        _vec(gamma, "conv3x3_vae_nhwc gamma", Cin)
+        _vec(beta, "conv3x3_vae_nhwc beta", Cin)
+    out = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+    if res is not None:
+        _nhwc(res, "conv3x3_vae_nhwc res")
+        _same(res, out, "conv3x3_vae_nhwc res")
+    call("ldmae_conv3x3_vae_nhwc_f32", mode, ptr(x), ptr(w), ptr(_vec(bias, "conv3x3_vae_nhwc bias", Cout)), ptr(res), ptr(mean), ptr(rstd),
+         ptr(gamma if mode == VAE_NORM_ACT else None), ptr(beta if mode == VAE_NORM_ACT else None), groups, 1 if silu else 0, ptr(out), B, H, W,
+         Cin, Cout, stream())
+    return out
+
+
+def conv1x1_res_nhwc(x, w, bias=None, res=None):
+    """x [..., Cin] (contiguous f32) times w [Cout, Cin]^T + bias + res [..., Cout]: the 1x1 convolution with a residual epilogue."""
+    if x.dtype != torch.float32 or not x.is_contiguous() or w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 2 or w.shape[1] != x.shape[-1]:
+        raise RuntimeError(f"conv1x1_res_nhwc: x {tuple(x.shape)} {x.dtype} and w {tuple(w.shape)} {w.dtype} must be contiguous f32 [..., Cin] and [Cout, Cin]")
+    Cout, Cin = w.shape
+    out = torch.empty(*x.shape[:-1], Cout, dtype=torch.float32, device=x.device)
+    if res is not None:
+        if res.dtype != torch.float32 or not res.is_contiguous():
+            raise RuntimeError("conv1x1_res_nhwc: res must be a contiguous f32 tensor")
+        _same(res, out, "conv1x1_res_nhwc res")
+    call("ldmae_conv1x1_res_nhwc_f32", ptr(x), ptr(w), ptr(_vec(bias, "conv1x1_res_nhwc bias", Cout)), ptr(res), ptr(out), x.numel() // Cin, Cin, Cout,
+         stream())
+    return out
+
+
+def softmax_rows_(s, cols, scale=1.0):
+    """In place on s [rows, ld] f32 (contiguous): s[:, :cols] = softmax(scale * s[:, :cols], dim=1); s[:, cols:] = 0."""
+    if s.dtype != torch.float32 or s.dim() != 2 or not s.is_contiguous() or not 0 < cols <= s.shape[1]:
+        raise RuntimeError(f"softmax_rows_: need a contiguous f32 [rows, ld >= cols] tensor, got {tuple(s.shape)} {s.dtype}, cols {cols}")
+    call("ldmae_softmax_rows_f32", ptr(s), s.shape[1], s.shape[0], cols, float(scale), stream())
+    return s
+
+
+ATTN_WIDE_KPAD = 16                     # ldmae_gemm_nt in f32 takes K in multiples of 16: the key axis of P and of V^T is padded with zeros
+
+
+def attention_wide(q, k, vt, scale, bias=None):
+    """Single-head attention of any width on the f32 GEMM: out [B, N, C] = softmax(scale q k^T) v (+ bias [C]).  q, k: [B, N, C] f32 views whose
+    rows are dense (the halves of one [B, N, 2C] buffer are fine); vt: [B, C, Np] f32 = v transposed, Np = N rounded up to ATTN_WIDE_KPAD with
+    zeros in the padding.  Per image: S = q k^T (ldmae_gemm_nt), row softmax in place (ldmae_softmax_rows_f32), out = P (v^T)^T + bias."""
+    B, N, C = q.shape
+    Np = -(-N // ATTN_WIDE_KPAD) * ATTN_WIDE_KPAD
+    if tuple(k.shape) != (B, N, C) or tuple(vt.shape) != (B, C, Np):
+        raise RuntimeError(f"attention_wide: q {tuple(q.shape)}, k {tuple(k.shape)}, vt {tuple(vt.shape)} must be [B, N, C] x 2 and [B, C, {Np}]")
+    out = torch.empty(B, N, C, dtype=torch.float32, device=q.device)
+    s = torch.empty(N, Np, dtype=torch.float32, device=q.device)
+    for b in range(B):
+        gemm_nt(q[b], k[b], out=s[:, :N])
+        softmax_rows_(s, N, scale)
+        gemm_nt(s, vt[b], bias=bias, out=out[b])
+    return out
