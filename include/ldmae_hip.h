@@ -443,6 +443,24 @@ int ldmae_conv3x3_vae_nhwc_f32(int mode, const float* x, const float* w, const f
                                void* stream);
 int ldmae_conv1x1_res_nhwc_f32(const float* x, const float* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout, void* stream);
 int ldmae_softmax_rows_f32(float* s, int ld, int rows, int cols, float scale, void* stream);
+/* The TF32-class form of the two convolutions (the rule of LDMAE_F16 above: the reference's drivers run these layers with allow_tf32, 10-bit
+ * mantissa products with f32 accumulation).  The arithmetic contract: both operands of every product are rounded ONCE to fp16, round to nearest
+ * even, saturating at +-65504 as ldmae_cast does; products are accumulated in f32 on the fp16 MFMA; bias and residual are added in f32 and
+ * the output is f32.  The residual stream, the GroupNorm statistics and everything between kernels stay f32.  In NORM_ACT the operand is
+ * fp16(silu(gamma (x - mean) rstd + beta)): normalise and SiLU in f32 exactly as in the f32 kernels, then one rounding; a tap outside the
+ * frame is exactly 0 and bypasses the activation.  Summation order is fixed by the shape: the same bits run to run.
+ * conv3x3_vae_nhwc_f16: modes, virtual-frame gather and epilogue of ldmae_conv3x3_vae_nhwc_f32.  w is fp16 [Cout, 3, 3, Cin], already packed
+ * (ldmae_cast of the f32 pack).  x_dtype LDMAE_F32: x is f32 and is rounded while it is staged; LDMAE_F16: x is fp16 (what
+ * groupnorm_apply_nhwc_f16out wrote), PLAIN mode only -- the two-pass form of norm-act, with results identical to the fused one.
+ * Cin % 8 == 0 (a 16-byte fp16 fragment never straddles a tap); any Cout, any M.  x, w, gamma, beta 16-B aligned.
+ * conv1x1_res_nhwc_f16: the same kernel with a 1x1 window; x f32 [M, Cin], w fp16 [Cout, Cin], Cin % 8 == 0.
+ * groupnorm_apply_nhwc_f16out: ldmae_groupnorm_apply_nhwc_f32 writing fp16 [B, HW, C] (saturating, round to nearest even). */
+int ldmae_conv3x3_vae_nhwc_f16(int mode, int x_dtype, const void* x, const void* w, const float* bias, const float* res, const float* mean,
+                               const float* rstd, const float* gamma, const float* beta, int G, int silu, float* out, int B, int H, int W, int Cin,
+                               int Cout, void* stream);
+int ldmae_conv1x1_res_nhwc_f16(const float* x, const void* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout, void* stream);
+int ldmae_groupnorm_apply_nhwc_f16out(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* out, int B,
+                                      int HW, int C, int G, int silu, void* stream);
 
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */

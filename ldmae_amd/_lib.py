@@ -134,6 +134,9 @@ SIGNATURES = {
     "ldmae_conv3x3_vae_nhwc_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "ldmae_conv1x1_res_nhwc_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ldmae_softmax_rows_f32": (_i, [_vp, _i, _i, _i, _f, _vp]),
+    "ldmae_conv3x3_vae_nhwc_f16": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_conv1x1_res_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ldmae_groupnorm_apply_nhwc_f16out": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

@@ -5,9 +5,12 @@
 //     up (the operand is read at (y >> 1, x >> 1) of the half-size tensor: nearest 2x upsampling that is never written); epilogue bias +
 //     residual;
 //   - the same epilogue on a 1x1 convolution (proj_out of AttnBlock);
-//   - the row softmax between the two f32 GEMMs of the single-head attention of AttnBlock.
+//   - the row softmax between the two f32 GEMMs of the single-head attention of AttnBlock;
+//   - the TF32-class form of the two convolutions (operands rounded once to fp16, f32 accumulation on conv_igemm_f16_mainloop) and the
+//     normalise pass that writes fp16 for it.
 #include "common.h"
 #include "conv_igemm_f32.h"
+#include "conv_igemm_f16.h"
 
 // One definition of the normalised operand for the fused gather and the stand-alone pass.
 template <bool SILU>
@@ -277,6 +280,258 @@ extern "C" int ldmae_conv1x1_res_nhwc_f32(const float* x, const float* w, const 
   g.Hv = 1; g.Wv = M; g.up = 0; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = M; g.G = 1; g.cpg = Cin;
   g.M = M; g.K = Cin;
   return launch_conv_vae("conv1x1_res_nhwc_f32", 0, 0, x, w, bias, res, nullptr, nullptr, nullptr, nullptr, out, g, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ TF32-class convolution (fp16 MFMA)
+// The same convolutions with both operands of every product rounded once to fp16 (round to nearest even, saturating at +-65504) and the
+// products accumulated in f32 on conv_igemm_f16_mainloop; bias and residual are added in f32 and the output is f32.  Under norm-act the
+// operand is fp16(gn_act(x)): normalise and SiLU in f32 by the definition above, then one rounding; a tap outside the frame is exactly 0
+// and bypasses the activation.  The weight comes packed as fp16 [Cout, ks, ks, Cin]; Cin % 8 == 0, so a 16-B fp16 fragment never
+// straddles a tap.  XF16: the input tensor is already fp16 (what groupnorm_apply_nhwc_f16out wrote: the two-pass form), plain gather only.
+__device__ __forceinline__ f16 to_f16_sat(float v) { return (f16)sat_f16(v, 65504.f); }
+
+// NORM 0: raw operand; 1: norm-act, cpg % 8 == 0 (the eight channels of a fragment share a group); 2: cpg % 4 == 0 (each half of a fragment
+// has its own group); 3: norm-act, any cpg.
+template <int NORM, bool SILU, bool XF16>
+__global__ __launch_bounds__(CH_NT) void conv_vae_f16_kernel(const void* __restrict__ xv, const f16* __restrict__ w, const float* __restrict__ bias,
+                                                             const float* __restrict__ res, const float* __restrict__ mean,
+                                                             const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float* __restrict__ out, VaeGeom g) {
+  __shared__ __attribute__((aligned(16))) f16 As[2][CH_BM * CH_LD];
+  __shared__ __attribute__((aligned(16))) f16 Bs[2][CH_BN * CH_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int tiles_n = (g.Cout + CH_BN - 1) / CH_BN;
+  const int m0 = (int)(blockIdx.x / tiles_n) * CH_BM, n0 = (int)(blockIdx.x % tiles_n) * CH_BN;
+  const int lr = tid >> 2, lc = (tid & 3) * 8;
+  int iy0[2], ix0[2], sb[2];
+  size_t xb[2];
+  const f16* wrow[2];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
+    const int ox = m % g.Wo, t = m / g.Wo, oy = t % g.Ho, b = t / g.Ho;
+    iy0[p] = oy * g.stride - g.pad;
+    ix0[p] = ox * g.stride - g.pad;
+    xb[p] = (size_t)b * g.H * g.W * g.Cin;
+    sb[p] = b * g.G;
+    wrow[p] = w + (size_t)min(n0 + lr + p * 64, g.Cout - 1) * g.K;      // rows past Cout fetch the last filter; never stored
+  }
+  // (tap, channel) of this thread's first k, advanced by BK per step without divisions; a BK step may span several taps (Cin < BK)
+  int ci = lc, kx = 0, ky = 0;
+  while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+  // norm-act: gamma / beta of the eight channels and their groups, the same for both A rows of a step
+  float ga[8], be[8];
+  int gi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto coef = [&]() {
+    if (NORM != 0 && ky < g.ks) {
+      const float4 g0 = *(const float4*)(gamma + ci), g1 = *(const float4*)(gamma + ci + 4);
+      const float4 b0 = *(const float4*)(beta + ci), b1 = *(const float4*)(beta + ci + 4);
+      ga[0] = g0.x; ga[1] = g0.y; ga[2] = g0.z; ga[3] = g0.w; ga[4] = g1.x; ga[5] = g1.y; ga[6] = g1.z; ga[7] = g1.w;
+      be[0] = b0.x; be[1] = b0.y; be[2] = b0.z; be[3] = b0.w; be[4] = b1.x; be[5] = b1.y; be[6] = b1.z; be[7] = b1.w;
+      if (NORM == 1) {
+        gi[0] = ci / g.cpg;
+      } else if (NORM == 2) {
+        gi[0] = ci / g.cpg;
+        gi[4] = (ci + 4) / g.cpg;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gi[j] = (ci + j) / g.cpg;
+      }
+    }
+  };
+  coef();
+  auto fetch_a = [&](int p) -> f16x8 {
+    const int iy = iy0[p] + ky, ix = ix0[p] + kx;
+    f16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ky < g.ks && (unsigned)iy < (unsigned)g.Hv && (unsigned)ix < (unsigned)g.Wv) {
+      const size_t off = xb[p] + ((size_t)(iy >> g.up) * g.W + (ix >> g.up)) * g.Cin + ci;
+      if (XF16) return *(const f16x8*)((const f16*)xv + off);
+      const float* px = (const float*)xv + off;
+      const float4 v0 = *(const float4*)px, v1 = *(const float4*)(px + 4);
+      float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+      if (NORM != 0) {
+        float mu[8], rs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int jj = NORM == 1 ? 0 : NORM == 2 ? (j & 4) : j;
+          if (j == jj) { mu[j] = mean[sb[p] + gi[j]]; rs[j] = rstd[sb[p] + gi[j]]; }
+          else { mu[j] = mu[jj]; rs[j] = rs[jj]; }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = gn_act<SILU>(v[j], mu[j], rs[j], ga[j], be[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = to_f16_sat(v[j]);
+    }
+    return r;
+  };
+  auto fetch_b = [&](int p, int k0) -> f16x8 {
+    const int k = k0 + lc;                                 // K % 8 == 0
+    if (k < g.K) return *(const f16x8*)(wrow[p] + k);
+    return (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
+  };
+  auto advance = [&]() {
+    ci += CH_BK;
+    while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+    coef();
+  };
+
+  f32x4 acc[4][4];
+  conv_igemm_f16_mainloop(As, Bs, (g.K + CH_BK - 1) / CH_BK, fetch_a, fetch_b, advance, acc);
+  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
+  // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block; out = acc + bias + res
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int n = n0 + wn * 64 + j * 16 + r16;
+    if (n >= g.Cout) continue;
+    const float bn = bias ? bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wm * 64 + i * 16 + q4 + r;
+        if (m < g.M) {
+          float v = acc[i][j][r] + bn;
+          if (res) v += res[(size_t)m * g.Cout + n];
+          out[(size_t)m * g.Cout + n] = v;
+        }
+      }
+  }
+}
+
+static int launch_conv_vae_f16(const char* name, int norm, int silu, bool xf16, const void* x, const void* w, const float* bias, const float* res,
+                               const float* mean, const float* rstd, const float* gamma, const float* beta, float* out, const VaeGeom& g,
+                               void* stream) {
+  const unsigned grid = cdiv(g.M, CH_BM) * cdiv(g.Cout, CH_BN);
+  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * g.M * g.Cout * g.K) : -1;
+#define LDMAE_VAE16_LAUNCH(NORM, SILU, XF16)                                                                                            \
+  hipLaunchKernelGGL((conv_vae_f16_kernel<NORM, SILU, XF16>), dim3(grid), dim3(CH_NT), 0, as_stream(stream), x, (const f16*)w, bias, res, mean, \
+                     rstd, gamma, beta, out, g)
+  if (norm == 0 && xf16) LDMAE_VAE16_LAUNCH(0, false, true);
+  else if (norm == 0) LDMAE_VAE16_LAUNCH(0, false, false);
+  else if (norm == 1 && silu) LDMAE_VAE16_LAUNCH(1, true, false);
+  else if (norm == 1) LDMAE_VAE16_LAUNCH(1, false, false);
+  else if (norm == 2 && silu) LDMAE_VAE16_LAUNCH(2, true, false);
+  else if (norm == 2) LDMAE_VAE16_LAUNCH(2, false, false);
+  else if (silu) LDMAE_VAE16_LAUNCH(3, true, false);
+  else LDMAE_VAE16_LAUNCH(3, false, false);
+#undef LDMAE_VAE16_LAUNCH
+  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
+  LDMAE_CHECK_LAUNCH(name);
+  return 0;
+}
+
+extern "C" int ldmae_conv3x3_vae_nhwc_f16(int mode, int x_dtype, const void* x, const void* w, const float* bias, const float* res, const float* mean,
+                                          const float* rstd, const float* gamma, const float* beta, int G, int silu, float* out, int B, int H, int W,
+                                          int Cin, int Cout, void* stream) {
+  LDMAE_REQUIRE(mode == LDMAE_VAE_PLAIN || mode == LDMAE_VAE_NORM_ACT || mode == LDMAE_VAE_DOWN || mode == LDMAE_VAE_UP,
+                "conv3x3_vae_nhwc_f16: mode %d (0 plain, 1 norm-act, 2 down, 3 up)", mode);
+  LDMAE_REQUIRE(x_dtype == LDMAE_F32 || x_dtype == LDMAE_F16, "conv3x3_vae_nhwc_f16: x_dtype %d (LDMAE_F32 or LDMAE_F16)", x_dtype);
+  LDMAE_REQUIRE(x_dtype == LDMAE_F32 || mode == LDMAE_VAE_PLAIN, "conv3x3_vae_nhwc_f16: an fp16 input is taken in plain mode only, got mode %d", mode);
+  LDMAE_REQUIRE(x && w && out, "conv3x3_vae_nhwc_f16: null pointer (only bias and res may be NULL)");
+  LDMAE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_vae_nhwc_f16: B=%d H=%d W=%d Cin=%d Cout=%d must be positive", B, H, W, Cin, Cout);
+  LDMAE_REQUIRE(Cin % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv3x3_vae_nhwc_f16: Cin=%d must be a multiple of 8 and x, w 16-B aligned",
+                Cin);
+  VaeGeom g{};
+  g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.ks = 3;
+  g.Hv = H; g.Wv = W; g.up = 0; g.stride = 1; g.pad = 1; g.Ho = H; g.Wo = W; g.G = 1; g.cpg = Cin;
+  int norm = 0;
+  if (mode == LDMAE_VAE_NORM_ACT) {
+    LDMAE_REQUIRE(mean && rstd && gamma && beta && G > 0, "conv3x3_vae_nhwc_f16: norm-act needs mean, rstd, gamma, beta and a positive group count");
+    LDMAE_REQUIRE(Cin % G == 0, "conv3x3_vae_nhwc_f16: %d channels are not divisible into %d groups", Cin, G);
+    LDMAE_REQUIRE(((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0, "conv3x3_vae_nhwc_f16: gamma and beta must be 16-B aligned");
+    g.G = G; g.cpg = Cin / G;
+    norm = g.cpg % 8 == 0 ? 1 : g.cpg % 4 == 0 ? 2 : 3;
+  } else if (mode == LDMAE_VAE_DOWN) {
+    LDMAE_REQUIRE(H >= 2 && W >= 2, "conv3x3_vae_nhwc_f16: down needs at least 2 x 2 pixels");
+    g.stride = 2; g.pad = 0; g.Ho = (H + 1 - 3) / 2 + 1; g.Wo = (W + 1 - 3) / 2 + 1;      // pad (0, 1, 0, 1): right and bottom only
+  } else if (mode == LDMAE_VAE_UP) {
+    g.up = 1; g.Hv = 2 * H; g.Wv = 2 * W; g.Ho = 2 * H; g.Wo = 2 * W;
+  }
+  const long M = (long)B * g.Ho * g.Wo, K = 9L * Cin;
+  LDMAE_REQUIRE(M < (1L << 31) - CH_BM && M * Cout < (1L << 40) && (long)B * H * W * Cin < (1L << 40) && K < (1L << 24), "conv3x3_vae_nhwc_f16: problem too large");
+  g.M = (int)M; g.K = (int)K;
+  LDMAE_REQUIRE((long)cdiv(M, CH_BM) * cdiv(Cout, CH_BN) < (1L << 31), "conv3x3_vae_nhwc_f16: problem too large");
+  return launch_conv_vae_f16("conv3x3_vae_nhwc_f16", norm, silu, x_dtype == LDMAE_F16, x, w, bias, res, mean, rstd, gamma, beta, out, g, stream);
+}
+
+extern "C" int ldmae_conv1x1_res_nhwc_f16(const float* x, const void* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout,
+                                          void* stream) {
+  LDMAE_REQUIRE(x && w && out, "conv1x1_res_nhwc_f16: null pointer (only bias and res may be NULL)");
+  LDMAE_REQUIRE(M > 0 && Cin > 0 && Cout > 0, "conv1x1_res_nhwc_f16: M=%d Cin=%d Cout=%d must be positive", M, Cin, Cout);
+  LDMAE_REQUIRE(Cin % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv1x1_res_nhwc_f16: Cin=%d must be a multiple of 8 and x, w 16-B aligned",
+                Cin);
+  LDMAE_REQUIRE((long)M < (1L << 31) - CH_BM && (long)M * Cout < (1L << 40) && (long)M * Cin < (1L << 40) && Cin < (1 << 24) &&
+                    (long)cdiv(M, CH_BM) * cdiv(Cout, CH_BN) < (1L << 31),
+                "conv1x1_res_nhwc_f16: problem too large");
+  VaeGeom g{};
+  g.B = 1; g.H = 1; g.W = M; g.Cin = Cin; g.Cout = Cout; g.ks = 1;                          // M pixels of one row: no tap ever leaves the frame
+  g.Hv = 1; g.Wv = M; g.up = 0; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = M; g.G = 1; g.cpg = Cin;
+  g.M = M; g.K = Cin;
+  return launch_conv_vae_f16("conv1x1_res_nhwc_f16", 0, 0, false, x, w, bias, res, nullptr, nullptr, nullptr, nullptr, out, g, stream);
+}
+
+// groupnorm_apply writing fp16 (saturating, round to nearest even): the first pass of the two-pass form.  The f32 value is gn_act's, so the
+// stored number is the rounding of what ldmae_groupnorm_apply_nhwc_f32 stores.  VEC: eight channels per thread (C % 8 == 0, 16-B aligned).
+template <bool SILU, bool VEC>
+__global__ __launch_bounds__(256) void gn_apply_f16_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, f16* __restrict__ out, long n,
+                                                           int HW, int C, int G) {
+  const int cpg = C / G;
+  if (VEC) {
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    const int sbase = (int)(i / ((long)HW * C)) * G;
+    const float4 v0 = *(const float4*)(x + i), v1 = *(const float4*)(x + i + 4);
+    const float4 g0 = *(const float4*)(gamma + c), g1 = *(const float4*)(gamma + c + 4);
+    const float4 b0 = *(const float4*)(beta + c), b1 = *(const float4*)(beta + c + 4);
+    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    const float ga[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    const float be[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    f16x8 r;
+    if (cpg % 8 == 0) {
+      const int s = sbase + c / cpg;
+      const float mu = mean[s], rs = rstd[s];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = to_f16_sat(gn_act<SILU>(v[j], mu, rs, ga[j], be[j]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int s = sbase + (c + j) / cpg;
+        r[j] = to_f16_sat(gn_act<SILU>(v[j], mean[s], rstd[s], ga[j], be[j]));
+      }
+    }
+    *(f16x8*)(out + i) = r;
+  } else {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    const int s = (int)(i / ((long)HW * C)) * G + c / cpg;
+    out[i] = to_f16_sat(gn_act<SILU>(x[i], mean[s], rstd[s], gamma[c], beta[c]));
+  }
+}
+
+extern "C" int ldmae_groupnorm_apply_nhwc_f16out(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* out,
+                                                 int B, int HW, int C, int G, int silu, void* stream) {
+  LDMAE_REQUIRE(x && mean && rstd && gamma && beta && out, "groupnorm_apply_nhwc_f16out: null pointer");
+  LDMAE_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0, "groupnorm_apply_nhwc_f16out: B=%d HW=%d C=%d G=%d must be positive", B, HW, C, G);
+  LDMAE_REQUIRE(C % G == 0, "groupnorm_apply_nhwc_f16out: %d channels are not divisible into %d groups", C, G);
+  LDMAE_REQUIRE(((uintptr_t)out & 1) == 0, "groupnorm_apply_nhwc_f16out: out must be 2-B aligned");
+  const long n = (long)B * HW * C;
+  LDMAE_REQUIRE((n + 255) / 256 < (1L << 31) && (long)B * G < (1L << 31), "groupnorm_apply_nhwc_f16out: problem too large");
+  const bool vec = C % 8 == 0 && (((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0;
+  f16* o = (f16*)out;
+#define LDMAE_GN16_LAUNCH(SILU, VEC, items) \
+  hipLaunchKernelGGL((gn_apply_f16_kernel<SILU, VEC>), dim3(cdiv(items, 256)), dim3(256), 0, as_stream(stream), x, mean, rstd, gamma, beta, o, n, HW, C, G)
+  if (vec && silu) LDMAE_GN16_LAUNCH(true, true, n / 8);
+  else if (vec) LDMAE_GN16_LAUNCH(false, true, n / 8);
+  else if (silu) LDMAE_GN16_LAUNCH(true, false, n);
+  else LDMAE_GN16_LAUNCH(false, false, n);
+#undef LDMAE_GN16_LAUNCH
+  LDMAE_CHECK_LAUNCH("groupnorm_apply_nhwc_f16out");
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ row softmax

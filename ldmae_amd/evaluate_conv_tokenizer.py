@@ -10,7 +10,7 @@ baselines the VMAE tokenizer is compared with, through the loop and the metric c
 depth can be changed by flag) and loads ``checkpoint['model']``; ``vavae`` reads ``model.params.embed_dim`` from ``--config_path`` and loads
 ``checkpoint['state_dict']``; ``marvae`` loads ``checkpoint['model']``.  The latent is the posterior mode; ``--epsilon`` adds
 ``epsilon * randn * std`` with the std of ``--latent_stats`` (a latents_stats.pt).  Output layout and the JSON line are those of
-``evaluate_tokenizer.py`` with the family as model type.  Weights are the user's files; nothing is downloaded.
+``evaluate_tokenizer.py`` with the family as model type and the ``--precision`` of the run.  Weights are the user's files; nothing is downloaded.
 """
 from __future__ import annotations
 
@@ -51,6 +51,8 @@ def build_parser():
     ap.add_argument("--lpips_lin", type=str, default=None, help="taming's LPIPS vgg.pth (default: $LDMAE_LPIPS_LIN, the reference's path)")
     ap.add_argument("--fid_weights", type=str, default=None, help="pt_inception-2015-12-05-6726825d.pth (default: $LDMAE_FID_WEIGHTS, torch.hub)")
     ap.add_argument("--synthetic", type=int, default=0, help="N seeded random images instead of an image folder")
+    ap.add_argument("--precision", choices=("f32", "tf32"), default="f32",
+                    help="tf32: the 3x3 convolutions round both operands once to fp16 and accumulate in f32 (what the reference computes under allow_tf32)")
     return ap
 
 
@@ -69,7 +71,7 @@ def build_tokenizer(args, device):
                                       down_block_types=(ENCODER_BLOCK,) * len(boc), up_block_types=(DECODER_BLOCK,) * len(boc))
         if args.weights is not None:
             vae.load_state_dict(torch.load(args.weights, map_location="cpu")["model"], strict=False)
-        vae = vae.to(device).eval()
+        vae = vae.to(device).eval().set_precision(args.precision)
         return (lambda x: vae.encode(x, return_dict=False)[0].mode()), (lambda z: vae.decode(z, return_dict=False)[0])
     from ldmae_amd.tokenizer.autoencoder import AutoencoderKL
     if args.family == "vavae":
@@ -81,7 +83,7 @@ def build_tokenizer(args, device):
         model = AutoencoderKL(embed_dim=embed_dim, ch_mult=(1, 1, 2, 2, 4), ckpt_path=args.weights)
     else:
         model = AutoencoderKL(embed_dim=16, ch_mult=(1, 1, 2, 2, 4), ckpt_path=args.weights, model_type="marvae")
-    model = model.to(device).eval()
+    model = model.to(device).eval().set_precision(args.precision)
     return (lambda x: model.encode(x).mode()), model.decode
 
 
@@ -115,7 +117,8 @@ def evaluate_conv_tokenizer(args, log=et.print_with_prefix):
     else:
         from ldmae_amd.datasets.image_folder import ImageFolder
         dataset = ImageFolder(args.data_path, transform=et.EvalTransform(args.image_size))
-    out = et.reconstruct_and_score(args, args.family, encode, decode, dataset, latent_std, lpips, device, rank, world, log)
+    out = et.reconstruct_and_score(args, args.family, encode, decode, dataset, latent_std, lpips, device, rank, world, log,
+                                   extra={"precision": args.precision})
     if distributed:
         dist.destroy_process_group()
     return out

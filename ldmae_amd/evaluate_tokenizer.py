@@ -221,7 +221,8 @@ def evaluate_tokenizer(args, cfg, log=print_with_prefix):
     return res, save_dir, ref_path
 
 
-def reconstruct_and_score(args, model_type, encode, decode, dataset, latent_std, lpips, device, rank=0, world=1, log=print_with_prefix):
+def reconstruct_and_score(args, model_type, encode, decode, dataset, latent_std, lpips, device, rank=0, world=1, log=print_with_prefix,
+                          extra=None):
     """The evaluation loop for any tokenizer: encode(images [B, 3, H, W] in [-1, 1]) -> latents, + epsilon * randn * latent_std, decode(latents)
     -> images; PNGs, LPIPS / SSIM / PSNR, rFID on rank 0 and the JSON line.  Returns (metrics, decoded dir, reference dir)."""
     from ldmae_amd import fid, ops
@@ -276,6 +277,7 @@ def reconstruct_and_score(args, model_type, encode, decode, dataset, latent_std,
         dist.barrier()
     res = aggregate(torch.stack(lpips_vals), torch.stack(ssim_vals), psnr.sum(), psnr.numel(), world)
     res.update({"epsilon": args.epsilon, "images": len(dataset), "world": world})
+    res.update(extra or {})             # fields a caller adds to the JSON line (evaluate_conv_tokenizer: the precision)
     if rank == 0:
         log("Computing rFID...")
         res["rfid"] = fid.calculate_fid_given_paths([ref_path, save_dir], batch_size=50, device=device, dims=2048, num_workers=16)

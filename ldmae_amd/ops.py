@@ -1353,28 +1353,51 @@ def _stats(stats, B, groups, what):
     return mean, rstd
 
 
-def groupnorm_apply_nhwc(x, stats, gamma, beta, silu=False, out=None):
-    """gamma (x - mean) rstd + beta of x [B, H, W, C] from groupnorm_stats_nhwc's (mean, rstd); silu=True: y * sigmoid(y) of that."""
+def groupnorm_apply_nhwc(x, stats, gamma, beta, silu=False, out=None, out_dtype=torch.float32):
+    """gamma (x - mean) rstd + beta of x [B, H, W, C] from groupnorm_stats_nhwc's (mean, rstd); silu=True: y * sigmoid(y) of that.
+    out_dtype=torch.float16: the same f32 value stored as fp16 (round to nearest even, saturating at +-65504): the operand of the two-pass
+    TF32-class convolution."""
     _nhwc(x, "groupnorm_apply_nhwc")
     B, H, W, C = x.shape
     mean, rstd = _stats(stats, B, stats[0].shape[1], "groupnorm_apply_nhwc")
+    if out_dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"groupnorm_apply_nhwc: out_dtype {out_dtype} (float32 or float16)")
     if out is None:
-        out = torch.empty_like(x)
-    _nhwc(out, "groupnorm_apply_nhwc out")
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    if out.dtype != out_dtype or out.dim() != 4 or not out.is_contiguous():
+        raise RuntimeError(f"groupnorm_apply_nhwc out: need a contiguous {out_dtype} NHWC tensor, got {tuple(out.shape)} {out.dtype}")
     _same(out, x, "groupnorm_apply_nhwc")
-    call("ldmae_groupnorm_apply_nhwc_f32", ptr(x), ptr(mean), ptr(rstd), ptr(_vec(gamma, "groupnorm_apply_nhwc gamma", C)),
-         ptr(_vec(beta, "groupnorm_apply_nhwc beta", C)), ptr(out), B, H * W, C, mean.shape[1], 1 if silu else 0, stream())
+    call("ldmae_groupnorm_apply_nhwc_f32" if out_dtype == torch.float32 else "ldmae_groupnorm_apply_nhwc_f16out", ptr(x), ptr(mean), ptr(rstd),
+         ptr(_vec(gamma, "groupnorm_apply_nhwc gamma", C)), ptr(_vec(beta, "groupnorm_apply_nhwc beta", C)), ptr(out), B, H * W, C, mean.shape[1],
+         1 if silu else 0, stream())
     return out
 
 
-def conv3x3_vae_nhwc(x, w, bias=None, mode=VAE_PLAIN, res=None, stats=None, gamma=None, beta=None, silu=True):
+VAE_PRECISIONS = ("f32", "tf32")
+
+
+def _precision(precision, what):
+    if precision not in VAE_PRECISIONS:
+        raise ValueError(f"{what}: precision {precision!r} (one of {VAE_PRECISIONS})")
+    return precision == "tf32"
+
+
+def conv3x3_vae_nhwc(x, w, bias=None, mode=VAE_PLAIN, res=None, stats=None, gamma=None, beta=None, silu=True, precision="f32"):
     """3x3 convolution of x [B, H, W, Cin] with w [Cout, 3, 3, Cin] -> [B, Ho, Wo, Cout], + bias + res (the output's shape).
     mode VAE_PLAIN: stride 1, pad 1.  VAE_NORM_ACT: the operand is groupnorm_apply_nhwc(x, stats, gamma, beta, silu), computed while it is
-    gathered; out-of-image taps are 0.  VAE_DOWN: stride 2, zero pad right and bottom only.  VAE_UP: nearest 2x upsampling, then stride 1, pad 1."""
-    _nhwc(x, "conv3x3_vae_nhwc")
+    gathered; out-of-image taps are 0.  VAE_DOWN: stride 2, zero pad right and bottom only.  VAE_UP: nearest 2x upsampling, then stride 1, pad 1.
+    precision "tf32": w is the fp16 pack (ops.cast of the f32 one), Cin % 8 == 0; both operands of every product are rounded once to fp16
+    (saturating), accumulation, bias, residual and output are f32.  x may then be fp16 in VAE_PLAIN (groupnorm_apply_nhwc(out_dtype=float16))."""
+    tf32 = _precision(precision, "conv3x3_vae_nhwc")
+    if tf32 and x.dtype == torch.float16:
+        if x.dim() != 4 or not x.is_contiguous():
+            raise RuntimeError(f"conv3x3_vae_nhwc: need a contiguous NHWC tensor, got {tuple(x.shape)}")
+    else:
+        _nhwc(x, "conv3x3_vae_nhwc")
     B, H, W, Cin = x.shape
-    if w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, Cin) or w.dtype != torch.float32 or not w.is_contiguous():
-        raise RuntimeError(f"conv3x3_vae_nhwc: weight {tuple(w.shape)} {w.dtype} is not a contiguous f32 [Cout, 3, 3, {Cin}]")
+    wdt = torch.float16 if tf32 else torch.float32
+    if w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, Cin) or w.dtype != wdt or not w.is_contiguous():
+        raise RuntimeError(f"conv3x3_vae_nhwc: weight {tuple(w.shape)} {w.dtype} is not a contiguous {wdt} [Cout, 3, 3, {Cin}]")
     Cout = w.shape[0]
     if mode == VAE_DOWN:
         Ho, Wo = (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
@@ -1399,24 +1422,32 @@ def conv3x3_vae_nhwc(x, w, bias=None, mode=VAE_PLAIN, res=None, stats=None, gamm
     if res is not None:
         _nhwc(res, "conv3x3_vae_nhwc res")
         _same(res, out, "conv3x3_vae_nhwc res")
-    call("ldmae_conv3x3_vae_nhwc_f32", mode, ptr(x), ptr(w), ptr(_vec(bias, "conv3x3_vae_nhwc bias", Cout)), ptr(res), ptr(mean), ptr(rstd),
-         ptr(gamma if mode == VAE_NORM_ACT else None), ptr(beta if mode == VAE_NORM_ACT else None), groups, 1 if silu else 0, ptr(out), B, H, W,
-         Cin, Cout, stream())
+    tail = (ptr(x), ptr(w), ptr(_vec(bias, "conv3x3_vae_nhwc bias", Cout)), ptr(res), ptr(mean), ptr(rstd),
+            ptr(gamma if mode == VAE_NORM_ACT else None), ptr(beta if mode == VAE_NORM_ACT else None), groups, 1 if silu else 0, ptr(out), B, H, W,
+            Cin, Cout, stream())
+    if tf32:
+        call("ldmae_conv3x3_vae_nhwc_f16", mode, dt(x.dtype), *tail)
+    else:
+        call("ldmae_conv3x3_vae_nhwc_f32", mode, *tail)
     return out
 
 
-def conv1x1_res_nhwc(x, w, bias=None, res=None):
-    """x [..., Cin] (contiguous f32) times w [Cout, Cin]^T + bias + res [..., Cout]: the 1x1 convolution with a residual epilogue."""
-    if x.dtype != torch.float32 or not x.is_contiguous() or w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 2 or w.shape[1] != x.shape[-1]:
-        raise RuntimeError(f"conv1x1_res_nhwc: x {tuple(x.shape)} {x.dtype} and w {tuple(w.shape)} {w.dtype} must be contiguous f32 [..., Cin] and [Cout, Cin]")
+def conv1x1_res_nhwc(x, w, bias=None, res=None, precision="f32"):
+    """x [..., Cin] (contiguous f32) times w [Cout, Cin]^T + bias + res [..., Cout]: the 1x1 convolution with a residual epilogue.
+    precision "tf32": w is the fp16 pack, Cin % 8 == 0; the arithmetic contract of conv3x3_vae_nhwc."""
+    tf32 = _precision(precision, "conv1x1_res_nhwc")
+    wdt = torch.float16 if tf32 else torch.float32
+    if x.dtype != torch.float32 or not x.is_contiguous() or w.dtype != wdt or not w.is_contiguous() or w.dim() != 2 or w.shape[1] != x.shape[-1]:
+        raise RuntimeError(f"conv1x1_res_nhwc: x {tuple(x.shape)} {x.dtype} and w {tuple(w.shape)} {w.dtype} must be contiguous f32 [..., Cin] and "
+                           f"{wdt} [Cout, Cin]")
     Cout, Cin = w.shape
     out = torch.empty(*x.shape[:-1], Cout, dtype=torch.float32, device=x.device)
     if res is not None:
         if res.dtype != torch.float32 or not res.is_contiguous():
             raise RuntimeError("conv1x1_res_nhwc: res must be a contiguous f32 tensor")
         _same(res, out, "conv1x1_res_nhwc res")
-    call("ldmae_conv1x1_res_nhwc_f32", ptr(x), ptr(w), ptr(_vec(bias, "conv1x1_res_nhwc bias", Cout)), ptr(res), ptr(out), x.numel() // Cin, Cin, Cout,
-         stream())
+    call("ldmae_conv1x1_res_nhwc_f16" if tf32 else "ldmae_conv1x1_res_nhwc_f32", ptr(x), ptr(w), ptr(_vec(bias, "conv1x1_res_nhwc bias", Cout)),
+         ptr(res), ptr(out), x.numel() // Cin, Cin, Cout, stream())
     return out
 
 

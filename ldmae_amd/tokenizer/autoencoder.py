@@ -26,15 +26,27 @@ from .util.misc import DiagonalGaussianDistribution  # noqa: F401  (one posterio
 # csrc/conv_vae.hip); tools/bench_conv_vae.py times one against the other.
 FUSED_NORM_ACT = True
 
+# The same choice for precision "tf32" (set_precision): True rounds to fp16 while the convolution gathers from the f32 tensor; False has the
+# normalise pass write the activated tensor as fp16 and a plain fp16-input convolution read it.  Identical results.  Two-pass is shipped on
+# the argument of DESIGN section 15 (the fused gather re-evaluates the activation per tap and per output tile, against an MFMA loop 16x
+# shorter than the f32 one); tools/bench_conv_vae.py times one against the other on the 256 x 256 x 128 and the 32 x 32 x 512 layer.
+TF32_FUSED_NORM_ACT = False
+
+PRECISIONS = ("f32", "tf32")
+
 
 def Normalize(in_channels, num_groups=32):
     return nn.GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=1e-6, affine=True)
 
 
+def _pack_key(w):
+    return (w._version, w.data_ptr(), w.device)
+
+
 def _packed(conv):
     """[Cout, kh, kw, Cin] f32 copy of an nn.Conv2d's weight, cached on the module until the parameter is rewritten or moved."""
     w = conv.weight
-    key = (w._version, w.data_ptr(), w.device)
+    key = _pack_key(w)
     hit = conv.__dict__.get("_ldmae_pack")
     if hit is None or hit[0] != key:
         hit = (key, w.detach().float().permute(0, 2, 3, 1).contiguous())
@@ -42,11 +54,41 @@ def _packed(conv):
     return hit[1]
 
 
+def _packed_f16(conv):
+    """The fp16 rounding (saturating, ldmae_cast) of _packed(conv), cached next to it under the same (version, pointer, device) key."""
+    key = _pack_key(conv.weight)
+    hit = conv.__dict__.get("_ldmae_pack_f16")
+    if hit is None or hit[0] != key:
+        hit = (key, ops.cast(_packed(conv), torch.float16))
+        conv.__dict__["_ldmae_pack_f16"] = hit
+    return hit[1]
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision {precision!r}: one of {PRECISIONS} (\"tf32\": fp16-rounded operands, f32 accumulation)")
+    return precision
+
+
+def uses_tf32(precision, cin):
+    """Whether a 3x3 (or residual 1x1) convolution with `cin` input channels runs the fp16-MFMA kernel under `precision`.  The kernel takes
+    Cin % 8 == 0; every other layer (the 3-channel image convolution, a 4-channel latent conv_in) falls back to MORE precision: exact f32."""
+    return check_precision(precision) == "tf32" and cin % 8 == 0
+
+
+def conv3x3_layers(module):
+    """[(name, Cin, Cout)] of the 3x3 convolutions (and AttnBlock.proj_out, the residual 1x1) below `module`: the layers set_precision acts on."""
+    return [(n, m.in_channels, m.out_channels) for n, m in module.named_modules()
+            if isinstance(m, nn.Conv2d) and (m.kernel_size == (3, 3) or n.endswith("proj_out"))]
+
+
 def _f32(p):
     return None if p is None else p.detach().float().contiguous()
 
 
-def _conv3x3(conv, x, mode=ops.VAE_PLAIN, res=None):
+def _conv3x3(conv, x, mode=ops.VAE_PLAIN, res=None, precision="f32"):
+    if uses_tf32(precision, x.shape[3]):
+        return ops.conv3x3_vae_nhwc(x, _packed_f16(conv), _f32(conv.bias), mode=mode, res=res, precision="tf32")
     if x.shape[3] % 4:                     # the 3-channel image: the general gather of the existing convolution
         if mode != ops.VAE_PLAIN or res is not None:
             raise RuntimeError(f"conv3x3: {x.shape[3]} input channels (not a multiple of 4) are supported by the plain convolution only")
@@ -58,10 +100,17 @@ def _conv1x1(conv, x):
     return ops.conv2d_nhwc(x, _packed(conv), _f32(conv.bias), relu=False)
 
 
-def _norm_act_conv(norm, conv, x, res=None):
+def _norm_act_conv(norm, conv, x, res=None, precision="f32"):
     """conv(silu(norm(x))) + res."""
     stats = ops.groupnorm_stats_nhwc(x, norm.num_groups, norm.eps)
     gamma, beta = _f32(norm.weight), _f32(norm.bias)
+    if uses_tf32(precision, x.shape[3]):
+        w = _packed_f16(conv)
+        if TF32_FUSED_NORM_ACT:
+            return ops.conv3x3_vae_nhwc(x, w, _f32(conv.bias), mode=ops.VAE_NORM_ACT, res=res, stats=stats, gamma=gamma, beta=beta, silu=True,
+                                        precision="tf32")
+        a = ops.groupnorm_apply_nhwc(x, stats, gamma, beta, silu=True, out_dtype=torch.float16)
+        return ops.conv3x3_vae_nhwc(a, w, _f32(conv.bias), mode=ops.VAE_PLAIN, res=res, precision="tf32")
     if FUSED_NORM_ACT:
         return ops.conv3x3_vae_nhwc(x, _packed(conv), _f32(conv.bias), mode=ops.VAE_NORM_ACT, res=res, stats=stats, gamma=gamma, beta=beta, silu=True)
     a = ops.groupnorm_apply_nhwc(x, stats, gamma, beta, silu=True)
@@ -70,6 +119,17 @@ def _norm_act_conv(norm, conv, x, res=None):
 
 class _Kernels(nn.Module):
     """Forward-only module whose arithmetic runs on the HIP kernels: NCHW at the boundary, NHWC inside (forward_nhwc)."""
+
+    precision = "f32"          # never inferred from torch.backends.*: only set_precision changes it
+
+    def set_precision(self, precision):
+        """"f32" (default): every layer on the exact-f32 kernels.  "tf32": the 3x3 convolutions and AttnBlock.proj_out with Cin % 8 == 0 round
+        both operands once to fp16 and accumulate in f32 (what the reference's drivers compute under allow_tf32); everything else stays f32."""
+        check_precision(precision)
+        for m in self.modules():
+            if isinstance(m, _Kernels):
+                m.precision = precision
+        return self
 
     def forward(self, x, *args):
         with torch.no_grad():
@@ -86,7 +146,7 @@ class Upsample(_Kernels):
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
 
     def forward_nhwc(self, x):
-        return _conv3x3(self.conv, x, ops.VAE_UP)
+        return _conv3x3(self.conv, x, ops.VAE_UP, precision=self.precision)
 
 
 class Downsample(_Kernels):
@@ -98,7 +158,7 @@ class Downsample(_Kernels):
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
 
     def forward_nhwc(self, x):
-        return _conv3x3(self.conv, x, ops.VAE_DOWN)
+        return _conv3x3(self.conv, x, ops.VAE_DOWN, precision=self.precision)
 
 
 class ResnetBlock(_Kernels):
@@ -125,10 +185,10 @@ class ResnetBlock(_Kernels):
     def forward_nhwc(self, x, temb=None):
         if temb is not None:
             raise NotImplementedError("ResnetBlock: temb is not supported")
-        h = _norm_act_conv(self.norm1, self.conv1, x)
+        h = _norm_act_conv(self.norm1, self.conv1, x, precision=self.precision)
         if self.in_channels != self.out_channels:
-            x = _conv3x3(self.conv_shortcut, x) if self.use_conv_shortcut else _conv1x1(self.nin_shortcut, x)
-        return _norm_act_conv(self.norm2, self.conv2, h, res=x)
+            x = _conv3x3(self.conv_shortcut, x, precision=self.precision) if self.use_conv_shortcut else _conv1x1(self.nin_shortcut, x)
+        return _norm_act_conv(self.norm2, self.conv2, h, res=x, precision=self.precision)
 
 
 class AttnBlock(_Kernels):
@@ -168,6 +228,8 @@ class AttnBlock(_Kernels):
         for b in range(B):
             ops.gemm_nt(wv, hn[b], out=vt[b][:, :N])
         o = ops.attention_wide(qk[:, :, :C], qk[:, :, C:], vt, float(int(C) ** (-0.5)), bias=_f32(self.v.bias))
+        if uses_tf32(self.precision, C):
+            return ops.conv1x1_res_nhwc(o.view(B, H, W, C), _packed_f16(self.proj_out).view(C, C), _f32(self.proj_out.bias), res=x, precision="tf32")
         return ops.conv1x1_res_nhwc(o.view(B, H, W, C), _packed(self.proj_out).view(C, C), _f32(self.proj_out.bias), res=x)
 
 
@@ -210,7 +272,7 @@ class Encoder(_Kernels):
         self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, kernel_size=3, stride=1, padding=1)
 
     def forward_nhwc(self, x):
-        h = _conv3x3(self.conv_in, x)
+        h = _conv3x3(self.conv_in, x, precision=self.precision)
         for i_level in range(self.num_resolutions):
             for i_block in range(self.num_res_blocks):
                 h = self.down[i_level].block[i_block].forward_nhwc(h)
@@ -221,7 +283,7 @@ class Encoder(_Kernels):
         h = self.mid.block_1.forward_nhwc(h)
         h = self.mid.attn_1.forward_nhwc(h)
         h = self.mid.block_2.forward_nhwc(h)
-        return _norm_act_conv(self.norm_out, self.conv_out, h)
+        return _norm_act_conv(self.norm_out, self.conv_out, h, precision=self.precision)
 
 
 class Decoder(_Kernels):
@@ -265,7 +327,7 @@ class Decoder(_Kernels):
 
     def forward_nhwc(self, z):
         self.last_z_shape = (z.shape[0], z.shape[3], z.shape[1], z.shape[2])
-        h = _conv3x3(self.conv_in, z)
+        h = _conv3x3(self.conv_in, z, precision=self.precision)
         h = self.mid.block_1.forward_nhwc(h)
         h = self.mid.attn_1.forward_nhwc(h)
         h = self.mid.block_2.forward_nhwc(h)
@@ -278,7 +340,7 @@ class Decoder(_Kernels):
                 h = self.up[i_level].upsample.forward_nhwc(h)
         if self.give_pre_end:
             return h
-        return _norm_act_conv(self.norm_out, self.conv_out, h)
+        return _norm_act_conv(self.norm_out, self.conv_out, h, precision=self.precision)
 
 
 def _nhwc_in(x, ref):
@@ -316,6 +378,16 @@ class AutoencoderKL(nn.Module):
         msg = self.load_state_dict(sd, strict=False)
         print(msg)
         return msg
+
+    @property
+    def precision(self):
+        return self.encoder.precision
+
+    def set_precision(self, precision):
+        """Encoder.set_precision on both halves; quant_conv / post_quant_conv stay f32."""
+        self.encoder.set_precision(precision)
+        self.decoder.set_precision(precision)
+        return self
 
     def encode_moments(self, x):
         """The quantised encoder output [B, mult * embed_dim, h, w] (NCHW) before the posterior is formed."""

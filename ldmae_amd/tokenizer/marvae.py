@@ -24,6 +24,11 @@ class MAR_VAE:
         self.model = AutoencoderKL(embed_dim=self.embed_dim, ch_mult=(1, 1, 2, 2, 4), ckpt_path=self.ckpt_path, model_type='marvae').cuda().eval()
         return self
 
+    def set_precision(self, precision):
+        """"f32" (default) or "tf32": AutoencoderKL.set_precision of the model (tokenizer/autoencoder.py)."""
+        self.model.set_precision(precision)
+        return self
+
     def img_transform(self, p_hflip=0, img_size=None):
         return ImgTransform(img_size if img_size is not None else self.img_size, p_hflip)
 

@@ -174,6 +174,16 @@ class Diffusers_AutoencoderKL(nn.Module):
         print(msg)
         return msg
 
+    @property
+    def precision(self):
+        return self.encoder.precision
+
+    def set_precision(self, precision):
+        """"f32" (default) or "tf32": Encoder.set_precision on both halves (tokenizer/autoencoder.py); the quant convolutions stay f32."""
+        self.encoder.set_precision(precision)
+        self.decoder.set_precision(precision)
+        return self
+
     # ------------------------------------------------------------------ diffusers' interface, as far as the reference uses it
     def encode(self, x, return_dict=True):
         with torch.no_grad():

@@ -5,9 +5,12 @@ block widths (128, 256, 512, 512), two layers per block, 16 latent channels, 256
   - encode and decode images/s and TF/s (operations counted from the shapes of every convolution and GEMM call, over event time);
   - a per-call table (op, shape, GFLOP, ms, TF/s), calls of one op and shape added up;
   - the same network in torch (F.group_norm / F.silu / F.conv2d, f32, NCHW, TF32 off) on the same weights and input as yardstick;
-  - the fused norm-act gather against "normalise kernel, then plain convolution" on the 256 x 256 x 128 layer, alternating.
+  - the fused norm-act gather against "normalise kernel, then plain convolution" on the 256 x 256 x 128 layer, alternating;
+  - all of it per --precision: "f32" (the exact-f32 MFMA) and "tf32" (operands rounded once to fp16, f32 accumulation; set_precision), and
+    for tf32 the fused / two-pass comparison on the 256 x 256 x 128 and the 32 x 32 x 512 layer plus each layer class against its f32 kernel,
+    alternating in one process.
 
-    python tools/bench_conv_vae.py [--batch 16] [--size 256] [--iters 5] [--no-torch] [--out profiles/conv_vae_bench.txt]
+    python tools/bench_conv_vae.py [--batch 16] [--size 256] [--iters 5] [--precision f32,tf32] [--no-torch] [--out profiles/conv_vae_bench.txt]
 """
 import argparse
 import os
@@ -161,8 +164,10 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "conv_vae_bench.txt"))
+    ap.add_argument("--precision", default="f32,tf32", help="comma-separated: f32, tf32 (default both, so that each is timed against the other)")
     ap.add_argument("--no-torch", action="store_true", help="leave the torch yardstick out (its first call per shape pays MIOpen's kernel search)")
     args = ap.parse_args()
+    precisions = [ae.check_precision(p) for p in args.precision.split(",")]
     if not torch.cuda.is_available():
         raise SystemExit("bench_conv_vae needs a GPU: nothing is measured without one")
     global OUT
@@ -175,60 +180,104 @@ def main():
     vae = Diffusers_AutoencoderKL(img_size=S, layers_per_block=2, latent_channels=16, block_out_channels=(128, 256, 512, 512),
                                   use_quant_conv=False, use_post_quant_conv=False).cuda().eval()
     x = torch.rand(B, 3, S, S, device="cuda") * 2 - 1
-    say(f"conv KL-VAE (128, 256, 512, 512), latent 16, batch {B}, {S} x {S}, f32; {torch.cuda.get_device_name(0)}; median of {args.iters}")
+    say(f"conv KL-VAE (128, 256, 512, 512), latent 16, batch {B}, {S} x {S}, precision {' and '.join(precisions)}; {torch.cuda.get_device_name(0)}; median of {args.iters}")
 
-    # ---- fused gather against two passes on the widest-image layer, alternating
-    h = torch.randn(B, S, S, 128, device="cuda")
+    # ---- fused gather against two passes, alternating: the widest-image layer and (tf32) the deepest one; each precision against the other
     blk = vae.decoder.up[0].block[1]
-    w, bias, ga, be = ae._packed(blk.conv1), ae._f32(blk.conv1.bias), ae._f32(blk.norm1.weight), ae._f32(blk.norm1.bias)
-    st = ops.groupnorm_stats_nhwc(h)
-    fl = 2.0 * B * S * S * 128 * 9 * 128
-    fused = lambda: ops.conv3x3_vae_nhwc(h, w, bias, mode=ops.VAE_NORM_ACT, stats=st, gamma=ga, beta=be)
-    two = lambda: ops.conv3x3_vae_nhwc(ops.groupnorm_apply_nhwc(h, st, ga, be, silu=True), w, bias)
-    plain = lambda: ops.conv3x3_vae_nhwc(h, w, bias)
-    say(f"norm-act on [{B}, {S}, {S}, 128] -> 128 ({fl / 1e9:.1f} GFLOP), alternating fused / two-pass, ms:")
-    res = {"fused": [], "two-pass": []}
-    for _ in range(3):
-        res["fused"].append(timed(fused, args.iters))
-        res["two-pass"].append(timed(two, args.iters))
-    for k, v in res.items():
-        say(f"  {k:9s} {' '.join(f'{t:8.3f}' for t in v)}   best {min(v):8.3f} ms  {fl / min(v) / 1e9:6.1f} TF/s")
-    say(f"  plain conv alone {timed(plain, args.iters):8.3f} ms; statistics {timed(lambda: ops.groupnorm_stats_nhwc(h), args.iters):8.3f} ms; "
-        f"normalise+SiLU pass {timed(lambda: ops.groupnorm_apply_nhwc(h, st, ga, be, silu=True), args.iters):8.3f} ms")
-    del h
-    shipped = ae.FUSED_NORM_ACT
-    say(f"shipped default: FUSED_NORM_ACT = {shipped} ({'fused gather' if shipped else 'two-pass'}); faster here: "
-        f"{'fused gather' if min(res['fused']) < min(res['two-pass']) else 'two-pass'}")
+    deep = vae.decoder.mid.block_1
+    f16 = torch.float16
+    for (hh, C, rb) in ((S, 128, blk), (S // 8, 512, deep)):
+        h = torch.randn(B, hh, hh, C, device="cuda")
+        w, bias, ga, be = ae._packed(rb.conv1), ae._f32(rb.conv1.bias), ae._f32(rb.norm1.weight), ae._f32(rb.norm1.bias)
+        w16 = ae._packed_f16(rb.conv1)
+        st = ops.groupnorm_stats_nhwc(h)
+        fl = 2.0 * B * hh * hh * C * 9 * C
+        forms = OrderedDict()
+        if "f32" in precisions:
+            forms["f32 fused"] = lambda: ops.conv3x3_vae_nhwc(h, w, bias, mode=ops.VAE_NORM_ACT, stats=st, gamma=ga, beta=be)
+            forms["f32 two-pass"] = lambda: ops.conv3x3_vae_nhwc(ops.groupnorm_apply_nhwc(h, st, ga, be, silu=True), w, bias)
+            forms["f32 plain conv"] = lambda: ops.conv3x3_vae_nhwc(h, w, bias)
+        if "tf32" in precisions:
+            forms["tf32 fused"] = lambda: ops.conv3x3_vae_nhwc(h, w16, bias, mode=ops.VAE_NORM_ACT, stats=st, gamma=ga, beta=be, precision="tf32")
+            forms["tf32 two-pass"] = lambda: ops.conv3x3_vae_nhwc(ops.groupnorm_apply_nhwc(h, st, ga, be, silu=True, out_dtype=f16), w16, bias,
+                                                                  precision="tf32")
+            forms["tf32 plain conv"] = lambda: ops.conv3x3_vae_nhwc(h, w16, bias, precision="tf32")
+        say(f"norm-act on [{B}, {hh}, {hh}, {C}] -> {C} ({fl / 1e9:.1f} GFLOP), alternating, ms:")
+        res = {k: [] for k in forms}
+        for _ in range(3):
+            for k, fn in forms.items():
+                res[k].append(timed(fn, args.iters))
+        for k, v in res.items():
+            say(f"  {k:15s} {' '.join(f'{t:8.3f}' for t in v)}   best {min(v):8.3f} ms  {fl / min(v) / 1e9:6.1f} TF/s")
+        say(f"  statistics {timed(lambda: ops.groupnorm_stats_nhwc(h), args.iters):8.3f} ms; normalise+SiLU pass to f32 "
+            f"{timed(lambda: ops.groupnorm_apply_nhwc(h, st, ga, be, silu=True), args.iters):8.3f} ms, to fp16 "
+            f"{timed(lambda: ops.groupnorm_apply_nhwc(h, st, ga, be, silu=True, out_dtype=f16), args.iters):8.3f} ms")
+        for prec, knob in (("f32", ae.FUSED_NORM_ACT), ("tf32", ae.TF32_FUSED_NORM_ACT)):
+            if prec in precisions:
+                say(f"  {prec}: shipped {'fused gather' if knob else 'two-pass'}; faster here: "
+                    f"{'fused gather' if min(res[prec + ' fused']) < min(res[prec + ' two-pass']) else 'two-pass'}")
+        del h, forms
+    if len(precisions) == 2:
+        # the other layer classes, tf32 against f32, alternating: down, up, the 3-channel head, the residual 1x1
+        say("layer classes, f32 / tf32 alternating, best of 3 medians, ms:")
+        cases = []
+        for name, shape, mod, mode in (("down 256x256x128", (B, S, S, 128), vae.encoder.down[0].downsample.conv, ops.VAE_DOWN),
+                                       ("up 128x128x256", (B, S // 2, S // 2, 256), vae.decoder.up[1].upsample.conv, ops.VAE_UP),
+                                       ("conv_out 256x256x128 -> 3", (B, S, S, 128), vae.decoder.conv_out, ops.VAE_PLAIN)):
+            h = torch.randn(*shape, device="cuda")
+            w, w16, bias = ae._packed(mod), ae._packed_f16(mod), ae._f32(mod.bias)
+            cases.append((name, (lambda h=h, w=w, bias=bias, mode=mode: ops.conv3x3_vae_nhwc(h, w, bias, mode=mode)),
+                          (lambda h=h, w16=w16, bias=bias, mode=mode: ops.conv3x3_vae_nhwc(h, w16, bias, mode=mode, precision="tf32"))))
+        h1 = torch.randn(B, S // 8, S // 8, 512, device="cuda")
+        w1 = torch.randn(512, 512, device="cuda") / 23
+        w1h = ops.cast(w1, f16)
+        cases.append(("1x1 + residual 32x32x512", lambda: ops.conv1x1_res_nhwc(h1, w1, res=h1), lambda: ops.conv1x1_res_nhwc(h1, w1h, res=h1, precision="tf32")))
+        for name, f32fn, tf32fn in cases:
+            a, b = [], []
+            for _ in range(3):
+                a.append(timed(f32fn, args.iters))
+                b.append(timed(tf32fn, args.iters))
+            say(f"  {name:28s} f32 {min(a):8.3f}   tf32 {min(b):8.3f}   x{min(a) / min(b):.2f}")
+        del cases, h1
 
-    # ---- the whole encoder and decoder, in both forms of norm-act; the per-call table is taken in the shipped form
+    # ---- the whole encoder and decoder, per precision, in both forms of norm-act; the per-call table is taken in the shipped form
+    knob = {"f32": "FUSED_NORM_ACT", "tf32": "TF32_FUSED_NORM_ACT"}
     with torch.no_grad():
         z = vae.encode_images(x)
         for name, fn, tfn in (("encode", lambda: vae.encode_images(x), lambda: t_encoder(vae.encoder, x)),
                               ("decode", lambda: vae.decode(z).sample, lambda: t_decoder(vae.decoder, z))):
-            outs = []
-            for form in (False, True):
-                ae.FUSED_NORM_ACT = form
+            outs, f32_out = [], None
+            for prec in precisions:
+                vae.set_precision(prec)
+                shipped = getattr(ae, knob[prec])
+                for form in (False, True):
+                    setattr(ae, knob[prec], form)
+                    with Ledger() as led:
+                        out = fn()
+                        flops = led.total()
+                    ms = timed(fn, args.iters)
+                    outs.append((prec, form, ms, out))
+                    say(f"{name} [{prec}, {'fused gather' if form else 'two-pass'}{', shipped' if form == shipped else ''}]: {ms:9.2f} ms  "
+                        f"{B / ms * 1e3:8.1f} img/s  {flops / ms / 1e9:6.1f} TF/s ({flops / B / 1e9:.1f} GFLOP per image)")
+                    if prec == "f32" and form == shipped:
+                        f32_out = out
+                    elif prec == "tf32" and f32_out is not None:
+                        say(f"  max|tf32 - f32| / max|f32| {float((out - f32_out).abs().max() / f32_out.abs().max()):.2e}")
+                setattr(ae, knob[prec], shipped)
                 with Ledger() as led:
-                    out = fn()
-                    flops = led.total()
-                ms = timed(fn, args.iters)
-                outs.append((form, ms, out))
-                say(f"{name} [{'fused gather' if form else 'two-pass'}{', shipped' if form == shipped else ''}]: {ms:9.2f} ms  {B / ms * 1e3:8.1f} img/s  "
-                    f"{flops / ms / 1e9:6.1f} TF/s ({flops / B / 1e9:.1f} GFLOP per image)")
-            ae.FUSED_NORM_ACT = shipped
-            with Ledger() as led:
-                led.events = True
-                fn()
-                led.table(f"{name} [{'fused gather' if shipped else 'two-pass'}]")
+                    led.events = True
+                    fn()
+                    led.table(f"{name} [{prec}, {'fused gather' if shipped else 'two-pass'}]")
+            vae.set_precision("f32")
             if not args.no_torch:          # last: the first torch call of every shape pays MIOpen's kernel search
                 ref = tfn()
                 tms = timed(tfn, args.iters)
                 say(f"{name} [torch f32, F.conv2d / group_norm / silu]: {tms:9.2f} ms  {B / tms * 1e3:8.1f} img/s  {flops / tms / 1e9:6.1f} TF/s (our operation count)")
-                for form, ms, out in outs:
+                for prec, form, ms, out in outs:
                     err = float((out - ref).abs().max() / ref.abs().max())
-                    say(f"  {'fused gather' if form else 'two-pass'}: x{tms / ms:.2f} of torch, max|diff|/max against torch {err:.1e}")
+                    say(f"  {prec} {'fused gather' if form else 'two-pass'}: x{tms / ms:.2f} of torch, max|diff|/max against torch {err:.1e}")
                 del ref
-            del out, outs
+            del out, outs, f32_out
     OUT.close()
 
 
