@@ -462,6 +462,32 @@ int ldmae_conv1x1_res_nhwc_f16(const float* x, const void* w, const float* bias,
 int ldmae_groupnorm_apply_nhwc_f16out(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* out, int B,
                                       int HW, int C, int G, int silu, void* stream);
 
+/* ---- adaptive Dormand-Prince 5(4) ODE sampler (transport/integrators.py, sampling_method dopri5; csrc/ode.hip), f32 -----------------
+ * The seven stage derivatives live in one slab k_slab[7][ld], ld % 4 == 0 and ld >= n (every row 16-byte aligned for any n); y, y1, y_mid,
+ * out are dense [n], 16-byte aligned.  h, t, the error ratio and the norms are single floats in DEVICE memory: nothing here synchronises.
+ * Every sum is two-stage and fixed-order (no atomics; the order depends on n only): bitwise reproducible.  partial: ode_partials(n) floats.
+ * rk_stage: out = y + h * sum_{j < m} coef[j] * k_j, evaluated as acc = coef[0] * k_0; acc = fma(coef[j], k_j, acc) for j = 1 .. m - 1;
+ * out = fma(h, acc, y).  coef is a HOST array of m floats (passed to the kernel by value), 1 <= m <= 7, h = *h_dev.  t_out != NULL: also
+ * t_out[0 .. nt) = fma(ct, h, *t_dev), the time vector of the next model evaluation.
+ * dopri5_finish: y1 = y + h * sum b_j k_j (the same operations as rk_stage with the tableau's last row, the zero weights skipped) and
+ * *ratio_dev = sqrt(mean((h * sum e_j k_j / (atol + rtol * max(|y|, |y1|)))^2)) over all n elements; the error vector is never stored.
+ * rms_norm_scaled: *out_dev = sqrt(mean((x / (atol + rtol * |y|))^2)), y = x when y_or_null is NULL.
+ * dopri5_interp: out = the quartic through y0, y1, y_mid with slopes f0 = k_0, f1 = k_6, at x = (t_eval - *t0_dev) / *h_dev; exactly y0 at x = 0.
+ * dopri5_advance (one thread): r = *ratio_dev; accepted when r <= 1; h' = h * (r == 0 ? 10 : min(10, max(0.9 / r^(1/5), r < 1 ? 1 : 0.2)));
+ * t' = accepted ? t + h : t; writes status_dev[0..5] = {accepted, r, t, h, t', h'} (the record the host reads) and *t_dev = t', *h_dev = h'.
+ * dopri5_initial_step (one thread): the Hairer-Norsett-Wanner starting step from d_dev = {d0, d1, d2 h0, h0}: phase 0 writes
+ * h0 = (d0 < 1e-5 or d1 < 1e-5) ? 1e-6 : 0.01 d0 / d1 to *h_dev and d_dev[3]; phase 1 writes min(100 h0, (0.01 / max(d1, d2))^(1/5)). */
+int ldmae_ode_partials(long n);
+int ldmae_rk_stage_f32(const float* y, const float* k_slab, long ld, const float* coef, int m, const float* h_dev, float* out, long n,
+                       const float* t_dev, float ct, float* t_out, int nt, void* stream);
+int ldmae_dopri5_finish_f32(const float* y, const float* k_slab, long ld, const float* h_dev, float atol, float rtol, float* y1, float* partial,
+                            float* ratio_dev, long n, void* stream);
+int ldmae_rms_norm_scaled_f32(const float* x, const float* y_or_null, float atol, float rtol, float* partial, float* out_dev, long n, void* stream);
+int ldmae_dopri5_interp_f32(const float* y0, const float* y1, const float* y_mid, const float* k_slab, long ld, const float* h_dev,
+                            const float* t0_dev, float t_eval, float* out, long n, void* stream);
+int ldmae_dopri5_advance(const float* ratio_dev, float* h_dev, float* t_dev, float* status_dev, void* stream);
+int ldmae_dopri5_initial_step(float* d_dev, int phase, float* h_dev, void* stream);
+
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */
 int ldmae_prof_enable(int on);

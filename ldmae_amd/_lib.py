@@ -137,6 +137,13 @@ SIGNATURES = {
     "ldmae_conv3x3_vae_nhwc_f16": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "ldmae_conv1x1_res_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ldmae_groupnorm_apply_nhwc_f16out": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_ode_partials": (_i, [_l]),
+    "ldmae_rk_stage_f32": (_i, [_vp, _vp, _l, C.POINTER(_f), _i, _vp, _vp, _l, _vp, _f, _vp, _i, _vp]),
+    "ldmae_dopri5_finish_f32": (_i, [_vp, _vp, _l, _vp, _f, _f, _vp, _vp, _vp, _l, _vp]),
+    "ldmae_rms_norm_scaled_f32": (_i, [_vp, _vp, _f, _f, _vp, _vp, _l, _vp]),
+    "ldmae_dopri5_interp_f32": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _f, _vp, _l, _vp]),
+    "ldmae_dopri5_advance": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "ldmae_dopri5_initial_step": (_i, [_vp, _i, _vp, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

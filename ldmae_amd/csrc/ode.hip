@@ -1,0 +1,323 @@
+// Adaptive Dormand-Prince 5(4) ODE sampler (transport/integrators.py, sampler_type "dopri5"): the solver's own arithmetic between two model
+// evaluations.  All f32, plain vector code, every kernel bound by HBM traffic (one pass over its operands, 16-byte accesses).
+//
+// Layout.  The seven stage derivatives live in one slab k[7][ld] (ld % 4 == 0, ld >= n: every row 16-byte aligned for any n).  A kernel
+// walks "items": item v < n / 4 is the float4 at element 4 v, item n / 4 (present when n % 4 != 0) is the scalar tail.  A block of 256 threads
+// owns 1024 consecutive items, thread t the items t, t + 256, t + 512, t + 768 of them, so the grid is cdiv(items, 1024): a function of n
+// alone, never of the device.
+//
+// Reductions (the error ratio and the norms of the initial-step rule) are two-stage and fixed-order, no atomics: a thread adds its (up to 16)
+// squares in element order, a wave joins its 64 lanes in the xor butterfly 32, 16, 8, 4, 2, 1, the four waves are added as (w0 + w1) + (w2 + w3)
+// and the block stores partial[block].  ode_fold_kernel (one block) lets thread t add partial[t], partial[t + 256], ... in that order, joins
+// the 256 threads the same way and writes sqrt(sum / n).  The order depends on n only: two runs give the same bits.
+//
+// Step size, time and the accept decision stay on the device (ldmae_dopri5_advance): the kernels that read h and the decision taken from the
+// error ratio see the same bits, and the host reads one small status record per attempted step.
+#include "common.h"
+
+namespace {
+
+constexpr int ODE_THREADS = 256;
+constexpr int ODE_UNROLL = 4;                                   // items per thread
+constexpr long ODE_BLOCK_ITEMS = (long)ODE_THREADS * ODE_UNROLL;
+
+struct RkCoef { float c[7]; };
+
+// c_sol (= row 7 of the tableau: FSAL), c_error = c_sol - the embedded 4th-order weights; b[1] = e[1] = 0 and b[6] = 0
+constexpr float DP_B0 = (float)(35.0 / 384.0), DP_B2 = (float)(500.0 / 1113.0), DP_B3 = (float)(125.0 / 192.0), DP_B4 = (float)(-2187.0 / 6784.0),
+                DP_B5 = (float)(11.0 / 84.0);
+constexpr float DP_E0 = (float)(35.0 / 384.0 - 1951.0 / 21600.0), DP_E2 = (float)(500.0 / 1113.0 - 22642.0 / 50085.0),
+                DP_E3 = (float)(125.0 / 192.0 - 451.0 / 720.0), DP_E4 = (float)(-2187.0 / 6784.0 + 12231.0 / 42400.0),
+                DP_E5 = (float)(11.0 / 84.0 - 649.0 / 6300.0), DP_E6 = (float)(-1.0 / 60.0);
+
+inline long ode_items(long n) { return (n >> 2) + ((n & 3) ? 1 : 0); }
+inline unsigned ode_grid(long n) { return cdiv(ode_items(n), ODE_BLOCK_ITEMS); }
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// ---------------------------------------------------------------- out = y + h * sum_{j < M} coef_j k_j
+template <int M> __device__ __forceinline__ float stage1(float y, const float (&k)[7], const RkCoef& cf, float h) {
+  float acc = cf.c[0] * k[0];
+#pragma unroll
+  for (int j = 1; j < M; ++j) acc = __builtin_fmaf(cf.c[j], k[j], acc);
+  return __builtin_fmaf(h, acc, y);
+}
+
+template <int M>
+__global__ __launch_bounds__(ODE_THREADS) void rk_stage_kernel(const float* __restrict__ y, const float* __restrict__ k, long ld, RkCoef cf,
+                                                               const float* __restrict__ h_dev, float* out, long n,
+                                                               const float* __restrict__ t_dev, float ct, float* __restrict__ t_out, int nt) {
+  const float h = *h_dev;
+  if (t_out && blockIdx.x == 0) {                               // the time the NEXT model evaluation is fed: t + ct h, one value per sample
+    const float ts = __builtin_fmaf(ct, h, *t_dev);
+    for (int i = threadIdx.x; i < nt; i += ODE_THREADS) t_out[i] = ts;
+  }
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v < nvec) {
+      const float4 yy = ((const float4*)y)[v];
+      float4 kk[M];
+#pragma unroll
+      for (int j = 0; j < M; ++j) kk[j] = ((const float4*)(k + (long)j * ld))[v];
+      float a[7], b[7], c[7], d[7];
+#pragma unroll
+      for (int j = 0; j < M; ++j) { a[j] = kk[j].x; b[j] = kk[j].y; c[j] = kk[j].z; d[j] = kk[j].w; }
+      ((float4*)out)[v] = make_float4(stage1<M>(yy.x, a, cf, h), stage1<M>(yy.y, b, cf, h), stage1<M>(yy.z, c, cf, h), stage1<M>(yy.w, d, cf, h));
+    } else if (v == nvec) {
+      for (long i = nvec << 2; i < n; ++i) {
+        float kj[7];
+#pragma unroll
+        for (int j = 0; j < M; ++j) kj[j] = k[(long)j * ld + i];
+        out[i] = stage1<M>(y[i], kj, cf, h);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- block sum (fixed order), see the header comment
+__device__ __forceinline__ float ode_block_sum(float s, float* red) {
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(ODE_THREADS) void ode_fold_kernel(const float* __restrict__ partial, int nparts, float n, float* __restrict__ out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += ODE_THREADS) s += partial[i];
+  s = ode_block_sum(s, red);
+  if (threadIdx.x == 0) *out = sqrtf(s / n);
+}
+
+// ---------------------------------------------------------------- y1 = y + h sum b_j k_j; partial[block] = sum (h sum e_j k_j / tol)^2
+__device__ __forceinline__ float finish1(float y, float k0, float k2, float k3, float k4, float k5, float k6, float h, float atol, float rtol, float& y1) {
+  float acc = DP_B0 * k0;
+  acc = __builtin_fmaf(DP_B2, k2, acc);
+  acc = __builtin_fmaf(DP_B3, k3, acc);
+  acc = __builtin_fmaf(DP_B4, k4, acc);
+  acc = __builtin_fmaf(DP_B5, k5, acc);
+  y1 = __builtin_fmaf(h, acc, y);
+  float e = DP_E0 * k0;
+  e = __builtin_fmaf(DP_E2, k2, e);
+  e = __builtin_fmaf(DP_E3, k3, e);
+  e = __builtin_fmaf(DP_E4, k4, e);
+  e = __builtin_fmaf(DP_E5, k5, e);
+  e = __builtin_fmaf(DP_E6, k6, e);
+  const float tol = __builtin_fmaf(rtol, fmaxf(fabsf(y), fabsf(y1)), atol);
+  return (h * e) / tol;
+}
+
+__global__ __launch_bounds__(ODE_THREADS) void dopri5_finish_kernel(const float* __restrict__ y, const float* __restrict__ k, long ld,
+                                                                    const float* __restrict__ h_dev, float atol, float rtol, float* __restrict__ y1,
+                                                                    float* __restrict__ partial, long n) {
+  __shared__ float red[4];
+  const float h = *h_dev;
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+  const float *k2 = k + 2 * ld, *k3 = k + 3 * ld, *k4 = k + 4 * ld, *k5 = k + 5 * ld, *k6 = k + 6 * ld;
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v < nvec) {
+      const float4 yy = ((const float4*)y)[v], a0 = ((const float4*)k)[v], a2 = ((const float4*)k2)[v], a3 = ((const float4*)k3)[v],
+                   a4 = ((const float4*)k4)[v], a5 = ((const float4*)k5)[v], a6 = ((const float4*)k6)[v];
+      float4 o;
+      float q;
+      q = finish1(yy.x, a0.x, a2.x, a3.x, a4.x, a5.x, a6.x, h, atol, rtol, o.x); s = __builtin_fmaf(q, q, s);
+      q = finish1(yy.y, a0.y, a2.y, a3.y, a4.y, a5.y, a6.y, h, atol, rtol, o.y); s = __builtin_fmaf(q, q, s);
+      q = finish1(yy.z, a0.z, a2.z, a3.z, a4.z, a5.z, a6.z, h, atol, rtol, o.z); s = __builtin_fmaf(q, q, s);
+      q = finish1(yy.w, a0.w, a2.w, a3.w, a4.w, a5.w, a6.w, h, atol, rtol, o.w); s = __builtin_fmaf(q, q, s);
+      ((float4*)y1)[v] = o;
+    } else if (v == nvec) {
+      for (long i = nvec << 2; i < n; ++i) {
+        float o;
+        const float q = finish1(y[i], k[i], k2[i], k3[i], k4[i], k5[i], k6[i], h, atol, rtol, o);
+        s = __builtin_fmaf(q, q, s);
+        y1[i] = o;
+      }
+    }
+  }
+  s = ode_block_sum(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// ---------------------------------------------------------------- partial[block] = sum (x / (atol + rtol |y|))^2
+__global__ __launch_bounds__(ODE_THREADS) void rms_norm_scaled_kernel(const float* __restrict__ x, const float* __restrict__ y, float atol, float rtol,
+                                                                      float* __restrict__ partial, long n) {
+  __shared__ float red[4];
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+  float s = 0.f;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v < nvec) {
+      const float4 xx = ((const float4*)x)[v], yy = ((const float4*)y)[v];
+      float q;
+      q = xx.x / __builtin_fmaf(rtol, fabsf(yy.x), atol); s = __builtin_fmaf(q, q, s);
+      q = xx.y / __builtin_fmaf(rtol, fabsf(yy.y), atol); s = __builtin_fmaf(q, q, s);
+      q = xx.z / __builtin_fmaf(rtol, fabsf(yy.z), atol); s = __builtin_fmaf(q, q, s);
+      q = xx.w / __builtin_fmaf(rtol, fabsf(yy.w), atol); s = __builtin_fmaf(q, q, s);
+    } else if (v == nvec) {
+      for (long i = nvec << 2; i < n; ++i) {
+        const float q = x[i] / __builtin_fmaf(rtol, fabsf(y[i]), atol);
+        s = __builtin_fmaf(q, q, s);
+      }
+    }
+  }
+  s = ode_block_sum(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// ---------------------------------------------------------------- the quartic through y0, y1, f0, f1 and y_mid, evaluated at t_eval
+__device__ __forceinline__ float interp1(float y0, float y1, float ym, float f0, float f1, float h, float x) {
+  const float a = 2.f * h * (f1 - f0) - 8.f * (y1 + y0) + 16.f * ym;
+  const float b = h * (5.f * f0 - 3.f * f1) + 18.f * y0 + 14.f * y1 - 32.f * ym;
+  const float c = h * (f1 - 4.f * f0) - 11.f * y0 - 5.f * y1 + 16.f * ym;
+  const float d = h * f0;
+  float total = y0 + x * d;
+  float xp = x * x;
+  total = total + xp * c;
+  xp = xp * x;
+  total = total + xp * b;
+  xp = xp * x;
+  return total + xp * a;
+}
+
+__global__ __launch_bounds__(ODE_THREADS) void dopri5_interp_kernel(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ ym,
+                                                                    const float* __restrict__ k, long ld, const float* __restrict__ h_dev,
+                                                                    const float* __restrict__ t0_dev, float t_eval, float* __restrict__ out, long n) {
+  const float h = *h_dev;
+  const float x = (t_eval - *t0_dev) / h;
+  const float* k6 = k + 6 * ld;
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v < nvec) {
+      const float4 a = ((const float4*)y0)[v], b = ((const float4*)y1)[v], m = ((const float4*)ym)[v], f0 = ((const float4*)k)[v],
+                   f1 = ((const float4*)k6)[v];
+      ((float4*)out)[v] = make_float4(interp1(a.x, b.x, m.x, f0.x, f1.x, h, x), interp1(a.y, b.y, m.y, f0.y, f1.y, h, x),
+                                      interp1(a.z, b.z, m.z, f0.z, f1.z, h, x), interp1(a.w, b.w, m.w, f0.w, f1.w, h, x));
+    } else if (v == nvec) {
+      for (long i = nvec << 2; i < n; ++i) out[i] = interp1(y0[i], y1[i], ym[i], k[i], k6[i], h, x);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- controller (one thread)
+__global__ void dopri5_advance_kernel(const float* __restrict__ ratio_dev, float* __restrict__ h_dev, float* __restrict__ t_dev, float* __restrict__ status) {
+  const float r = *ratio_dev, h = *h_dev, t = *t_dev;
+  const bool accept = r <= 1.f;
+  const float dfactor = r < 1.f ? 1.f : 0.2f;                  // an accepted step never shrinks
+  const float factor = r == 0.f ? 10.f : fminf(10.f, fmaxf(0.9f / powf(r, 0.2f), dfactor));
+  const float t_new = accept ? t + h : t, h_new = h * factor;
+  status[0] = accept ? 1.f : 0.f;
+  status[1] = r;
+  status[2] = t;
+  status[3] = h;
+  status[4] = t_new;
+  status[5] = h_new;
+  *t_dev = t_new;
+  *h_dev = h_new;
+}
+
+// Hairer-Norsett-Wanner starting step.  d = [d0, d1, d2, h0]; phase 0: h0 from d0, d1; phase 1: the step from h0, d1 and d2 = d[2] / h0.
+__global__ void dopri5_initial_step_kernel(float* __restrict__ d, int phase, float* __restrict__ h_dev) {
+  const float d0 = d[0], d1 = d[1];
+  if (phase == 0) {
+    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    d[3] = h0;
+    *h_dev = h0;
+  } else {
+    const float h0 = d[3], d2 = d[2] / h0;
+    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
+    *h_dev = fminf(100.f * h0, h1);
+  }
+}
+
+template <int M>
+void launch_stage(const float* y, const float* k, long ld, const RkCoef& cf, const float* h_dev, float* out, long n, const float* t_dev, float ct,
+                  float* t_out, int nt, hipStream_t st) {
+  hipLaunchKernelGGL(rk_stage_kernel<M>, dim3(ode_grid(n)), dim3(ODE_THREADS), 0, st, y, k, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt);
+}
+
+}  // namespace
+
+extern "C" int ldmae_ode_partials(long n) { return n > 0 ? (int)ode_grid(n) : 0; }
+
+extern "C" int ldmae_rk_stage_f32(const float* y, const float* k_slab, long ld, const float* coef, int m, const float* h_dev, float* out, long n,
+                                  const float* t_dev, float ct, float* t_out, int nt, void* stream) {
+  LDMAE_REQUIRE(y && k_slab && coef && h_dev && out && n > 0 && m >= 1 && m <= 7, "rk_stage: bad arguments (m = %d, n = %ld)", m, n);
+  LDMAE_REQUIRE(ld >= n && (ld & 3) == 0 && al16(y) && al16(k_slab) && al16(out), "rk_stage: ld %ld must be a multiple of 4, >= n, and y, k_slab, out 16-byte aligned", ld);
+  LDMAE_REQUIRE(!t_out || (t_dev && nt > 0), "rk_stage: t_out needs t_dev and nt > 0");
+  LDMAE_REQUIRE(ode_items(n) <= 0x7fffffffL * ODE_BLOCK_ITEMS, "rk_stage: n too large");
+  RkCoef cf;
+  for (int j = 0; j < 7; ++j) cf.c[j] = j < m ? coef[j] : 0.f;
+  hipStream_t st = as_stream(stream);
+  switch (m) {
+    case 1: launch_stage<1>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+    case 2: launch_stage<2>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+    case 3: launch_stage<3>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+    case 4: launch_stage<4>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+    case 5: launch_stage<5>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+    case 6: launch_stage<6>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+    default: launch_stage<7>(y, k_slab, ld, cf, h_dev, out, n, t_dev, ct, t_out, nt, st); break;
+  }
+  LDMAE_CHECK_LAUNCH("rk_stage");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_dopri5_finish_f32(const float* y, const float* k_slab, long ld, const float* h_dev, float atol, float rtol, float* y1,
+                                       float* partial, float* ratio_dev, long n, void* stream) {
+  LDMAE_REQUIRE(y && k_slab && h_dev && y1 && partial && ratio_dev && n > 0, "dopri5_finish: bad arguments");
+  LDMAE_REQUIRE(ld >= n && (ld & 3) == 0 && al16(y) && al16(k_slab) && al16(y1), "dopri5_finish: ld %ld must be a multiple of 4, >= n, and y, k_slab, y1 16-byte aligned", ld);
+  LDMAE_REQUIRE(y1 != y, "dopri5_finish: y1 must not alias y");
+  const unsigned grid = ode_grid(n);
+  hipLaunchKernelGGL(dopri5_finish_kernel, dim3(grid), dim3(ODE_THREADS), 0, as_stream(stream), y, k_slab, ld, h_dev, atol, rtol, y1, partial, n);
+  hipLaunchKernelGGL(ode_fold_kernel, dim3(1), dim3(ODE_THREADS), 0, as_stream(stream), partial, (int)grid, (float)n, ratio_dev);
+  LDMAE_CHECK_LAUNCH("dopri5_finish");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_rms_norm_scaled_f32(const float* x, const float* y_or_null, float atol, float rtol, float* partial, float* out_dev, long n,
+                                         void* stream) {
+  LDMAE_REQUIRE(x && partial && out_dev && n > 0, "rms_norm_scaled: bad arguments");
+  const float* y = y_or_null ? y_or_null : x;
+  LDMAE_REQUIRE(al16(x) && al16(y), "rms_norm_scaled: x and y must be 16-byte aligned");
+  const unsigned grid = ode_grid(n);
+  hipLaunchKernelGGL(rms_norm_scaled_kernel, dim3(grid), dim3(ODE_THREADS), 0, as_stream(stream), x, y, atol, rtol, partial, n);
+  hipLaunchKernelGGL(ode_fold_kernel, dim3(1), dim3(ODE_THREADS), 0, as_stream(stream), partial, (int)grid, (float)n, out_dev);
+  LDMAE_CHECK_LAUNCH("rms_norm_scaled");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_dopri5_interp_f32(const float* y0, const float* y1, const float* y_mid, const float* k_slab, long ld, const float* h_dev,
+                                       const float* t0_dev, float t_eval, float* out, long n, void* stream) {
+  LDMAE_REQUIRE(y0 && y1 && y_mid && k_slab && h_dev && t0_dev && out && n > 0, "dopri5_interp: bad arguments");
+  LDMAE_REQUIRE(ld >= n && (ld & 3) == 0 && al16(y0) && al16(y1) && al16(y_mid) && al16(k_slab) && al16(out),
+                "dopri5_interp: ld %ld must be a multiple of 4, >= n, and every tensor 16-byte aligned", ld);
+  hipLaunchKernelGGL(dopri5_interp_kernel, dim3(ode_grid(n)), dim3(ODE_THREADS), 0, as_stream(stream), y0, y1, y_mid, k_slab, ld, h_dev, t0_dev, t_eval,
+                     out, n);
+  LDMAE_CHECK_LAUNCH("dopri5_interp");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_dopri5_advance(const float* ratio_dev, float* h_dev, float* t_dev, float* status_dev, void* stream) {
+  LDMAE_REQUIRE(ratio_dev && h_dev && t_dev && status_dev, "dopri5_advance: bad arguments");
+  hipLaunchKernelGGL(dopri5_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), ratio_dev, h_dev, t_dev, status_dev);
+  LDMAE_CHECK_LAUNCH("dopri5_advance");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_dopri5_initial_step(float* d_dev, int phase, float* h_dev, void* stream) {
+  LDMAE_REQUIRE(d_dev && h_dev && (phase == 0 || phase == 1), "dopri5_initial_step: bad arguments");
+  hipLaunchKernelGGL(dopri5_initial_step_kernel, dim3(1), dim3(1), 0, as_stream(stream), d_dev, phase, h_dev);
+  LDMAE_CHECK_LAUNCH("dopri5_initial_step");
+  return LDMAE_OK;
+}

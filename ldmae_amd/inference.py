@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sampling driver -- counterpart of the reference's LDMAE/inference.py (`run_inference.sh`): EMA checkpoint -> shifted-grid
-Euler ODE with classifier-free guidance (CFG on the first three channels, interval gate) -> latent de-normalisation -> VMAE
-``decode_to_images`` -> PNGs.  Ranks are independent replicas (seed = global_seed * world + rank, inference.py:87)."""
+ODE (sample.sampling_method: euler / heun / midpoint / dopri5) with classifier-free guidance (CFG on the first three channels, interval
+gate) -> latent de-normalisation -> VMAE ``decode_to_images`` -> PNGs.  Ranks are independent replicas (seed = global_seed * world + rank, inference.py:87)."""
 import argparse
 import math
 import os
@@ -52,6 +52,9 @@ def sample_latents(model, sample_fn, n, cfg_scale, cfg_interval_start, device, n
     if cfg_scale > 1.0:
         z = torch.cat([z, z], 0)
         y = torch.cat([y, torch.full((n,), num_classes, device=device)], 0)
+        # dopri5's error norm runs over the whole doubled batch, as the reference's does: it gets forward_with_cfg at every evaluation
+        fixed_step = getattr(getattr(sample_fn, "__self__", None), "sampler_type", "euler") != "dopri5"
+
         def cfg_forward(x, t, y, cfg_scale, cfg_interval=None, cfg_interval_start=None):
             # Below the interval start forward_with_cfg applies NO guidance (lightningdit.py:436-439): the conditional half gets its own
             # output, and the unconditional half's output is never used for the samples that are kept -- every step rebuilds the doubled
@@ -63,7 +66,7 @@ def sample_latents(model, sample_fn, n, cfg_scale, cfg_interval_start, device, n
             # adaLN path as the doubled one (the batched bf16 adaLN GEMM needs a batch that is a multiple of 8; an n of 4, 12, 20 ... would put
             # the half on the per-block f32 path and the guided steps on the batched bf16 one: not bit-for-bit the doubled batch any more).
             same_path = _act_dtype(getattr(model, "precision", None)) != torch.bfloat16 or (len(x) // 2) % 8 == 0 or len(x) % 8 != 0
-            if cfg_interval is True and cfg_interval_start and float(t[0]) < cfg_interval_start and same_path:
+            if fixed_step and cfg_interval is True and cfg_interval_start and float(t[0]) < cfg_interval_start and same_path:
                 half = len(x) // 2
                 out = model.forward(x[:half], t[:half], y[:half])
                 return torch.cat([out, out], dim=0)
@@ -221,6 +224,9 @@ def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", 
         for it in range(total // (n * world)):
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=precision == "bf16"):
                 lat, _ = sample_latents(model, sample_fn, n, cfg_scale, s.get('cfg_interval_start', 0), device, cfg['data']['num_classes'], truncation=trunc)
+            solver = getattr(sample_fn, "__self__", None)
+            if it == 0 and rank == 0 and getattr(solver, "sampler_type", None) == "dopri5":
+                print(f"dopri5 (atol {solver.atol:g}, rtol {solver.rtol:g}): nfe {solver.nfe}, accepted {solver.accepted}, rejected {solver.rejected}")
             imgs = decode(lat)
             writer.put(imgs, [f"{out_dir}/{i * world + rank + done:06d}.png" for i in range(len(imgs))])   # index rule: inference.py:294
             done += n * world

@@ -1477,3 +1477,90 @@ def attention_wide(q, k, vt, scale, bias=None):
         softmax_rows_(s, N, scale)
         gemm_nt(s, vt[b], bias=bias, out=out[b])
     return out
+
+
+# ----------------------------------------------------------------------------- adaptive dopri5 ODE sampler (csrc/ode.hip), f32
+def _ode_vec(t, what, n):
+    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+        raise RuntimeError(f"{what}: need a contiguous f32 tensor of {n} elements, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _ode_slab(k, n):
+    if k.dtype != torch.float32 or k.dim() != 2 or k.shape[0] != 7 or not k.is_contiguous() or k.shape[1] < n or k.shape[1] % 4:
+        raise RuntimeError(f"ode: the stage slab must be a contiguous f32 [7, ld] tensor with ld % 4 == 0 and ld >= {n}, got {tuple(k.shape)} {k.dtype}")
+    return k
+
+
+def _ode_scalar(t, what, n=1):
+    if t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous():
+        raise RuntimeError(f"{what}: need f32 device memory of {n} element(s), got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def ode_slab_ld(n):
+    """Row length of the [7, ld] stage slab for a state of n elements: n rounded up to a multiple of 4 (every row 16-byte aligned)."""
+    return (n + 3) // 4 * 4
+
+
+def ode_partials(n):
+    """Number of per-block partial sums ldmae_dopri5_finish_f32 / ldmae_rms_norm_scaled_f32 write for n elements (a function of n alone)."""
+    return int(L.load().ldmae_ode_partials(n))
+
+
+def rk_stage(y, k_slab, coef, h_dev, out, t_dev=None, ct=0.0, t_out=None):
+    """out = y + h * sum_j coef[j] * k_slab[j] (one pass, fixed left-to-right order); h read from the device scalar h_dev.  With t_out (f32 [B]):
+    every element of t_out = t + ct * h as well, the time vector of the next model evaluation.  Returns out."""
+    n = y.numel()
+    m = len(coef)
+    _ode_vec(y, "rk_stage y", n), _ode_vec(out, "rk_stage out", n), _ode_slab(k_slab, n), _ode_scalar(h_dev, "rk_stage h_dev")
+    if t_out is not None:
+        _ode_scalar(t_dev, "rk_stage t_dev"), _ode_vec(t_out, "rk_stage t_out", t_out.numel())
+    cf = (ctypes.c_float * 7)(*[float(c) for c in coef])
+    call("ldmae_rk_stage_f32", ptr(y), ptr(k_slab), k_slab.shape[1], cf, m, ptr(h_dev), ptr(out), n, ptr(t_dev), float(ct), ptr(t_out),
+         0 if t_out is None else t_out.numel(), stream())
+    return out
+
+
+def dopri5_finish(y, k_slab, h_dev, atol, rtol, y1, partial, ratio_dev):
+    """y1 = y + h * sum b_j k_j and ratio_dev = rms over ALL elements of (h * sum e_j k_j) / (atol + rtol * max(|y|, |y1|)), in one pass plus a
+    one-block fold; fixed summation order (bitwise reproducible), no atomics.  partial: >= ode_partials(n) f32."""
+    n = y.numel()
+    _ode_vec(y, "dopri5_finish y", n), _ode_vec(y1, "dopri5_finish y1", n), _ode_slab(k_slab, n), _ode_scalar(h_dev, "dopri5_finish h_dev")
+    _ode_scalar(partial, "dopri5_finish partial", ode_partials(n)), _ode_scalar(ratio_dev, "dopri5_finish ratio_dev")
+    call("ldmae_dopri5_finish_f32", ptr(y), ptr(k_slab), k_slab.shape[1], ptr(h_dev), float(atol), float(rtol), ptr(y1), ptr(partial), ptr(ratio_dev),
+         n, stream())
+    return y1
+
+
+def rms_norm_scaled(x, y, atol, rtol, partial, out_dev):
+    """out_dev = sqrt(mean((x / (atol + rtol * |y|))^2)) (y None: y = x), the norm of the starting-step rule; same two-stage fold as dopri5_finish."""
+    n = x.numel()
+    _ode_vec(x, "rms_norm_scaled x", n), _ode_scalar(partial, "rms_norm_scaled partial", ode_partials(n)), _ode_scalar(out_dev, "rms_norm_scaled out_dev")
+    if y is not None:
+        _ode_vec(y, "rms_norm_scaled y", n)
+    call("ldmae_rms_norm_scaled_f32", ptr(x), ptr(y), float(atol), float(rtol), ptr(partial), ptr(out_dev), n, stream())
+    return out_dev
+
+
+def dopri5_interp(y0, y1, y_mid, k_slab, h_dev, t0_dev, t_eval, out):
+    """out = the quartic through y0, y1, y_mid with end slopes k_slab[0], k_slab[6], at x = (t_eval - t0) / h; coefficients never stored."""
+    n = y0.numel()
+    for t, w in ((y0, "y0"), (y1, "y1"), (y_mid, "y_mid"), (out, "out")):
+        _ode_vec(t, "dopri5_interp " + w, n)
+    _ode_slab(k_slab, n), _ode_scalar(h_dev, "dopri5_interp h_dev"), _ode_scalar(t0_dev, "dopri5_interp t0_dev")
+    call("ldmae_dopri5_interp_f32", ptr(y0), ptr(y1), ptr(y_mid), ptr(k_slab), k_slab.shape[1], ptr(h_dev), ptr(t0_dev), float(t_eval), ptr(out), n, stream())
+    return out
+
+
+def dopri5_advance(ratio_dev, h_dev, t_dev, status_dev):
+    """The step-size controller on the device (one thread): status_dev[0..5] = (accepted, ratio, t, h, t', h'); t_dev, h_dev updated in place."""
+    _ode_scalar(ratio_dev, "dopri5_advance ratio_dev"), _ode_scalar(h_dev, "dopri5_advance h_dev"), _ode_scalar(t_dev, "dopri5_advance t_dev")
+    _ode_scalar(status_dev, "dopri5_advance status_dev", 6)
+    call("ldmae_dopri5_advance", ptr(ratio_dev), ptr(h_dev), ptr(t_dev), ptr(status_dev), stream())
+
+
+def dopri5_initial_step(d_dev, phase, h_dev):
+    """The Hairer-Norsett-Wanner starting step from the norms d_dev = (d0, d1, d2 * h0, h0): phase 0 writes h0, phase 1 the step, to h_dev."""
+    _ode_scalar(d_dev, "dopri5_initial_step d_dev", 4), _ode_scalar(h_dev, "dopri5_initial_step h_dev")
+    call("ldmae_dopri5_initial_step", ptr(d_dev), int(phase), ptr(h_dev), stream())
