@@ -487,6 +487,19 @@ int ldmae_dopri5_interp_f32(const float* y0, const float* y1, const float* y_mid
                             const float* t0_dev, float t_eval, float* out, long n, void* stream);
 int ldmae_dopri5_advance(const float* ratio_dev, float* h_dev, float* t_dev, float* status_dev, void* stream);
 int ldmae_dopri5_initial_step(float* d_dev, int phase, float* h_dev, void* stream);
+/* Likelihood evaluation (transport.Sampler.sample_ode_likelihood: the probability-flow ODE on the augmented state (x, logp) with Hutchinson's
+ * trace estimator), f32, no atomics, fixed summation order.
+ * rademacher: out[i] = +1 or -1 from Philox4x32-10 (Salmon, Moraes, Dror & Shaw, SC'11) with key (seed low, seed high) and counter words
+ * (counter low, counter high, v low, v high), v = i / 4: element i takes word i % 4 of block v, +1 when the word's top bit is set.
+ * rowdot: out[r] = sum_j a[r, j] b[r, j] for B rows of m floats (a, b dense [B, m]; b == a gives the row sums of squares).  One fma chain per
+ * thread over its elements of a 4096-element chunk of the row, the block sum of csrc/ode.hip, partial[r * ceil(m / 4096) + c], then one block
+ * per row folds its chunks.  16-byte loads when every row start is aligned, element loads otherwise (another, equally fixed, order).
+ * partial: ldmae_rowdot_partials(B, m) floats.
+ * likelihood_finish: logp[b] = (c - sumsq[b] / 2) - delta[b], c = -m / 2 log(2 pi) from the host; every operation rounded once. */
+int ldmae_rademacher_f32(float* out, long n, unsigned long long seed, unsigned long long counter, void* stream);
+long ldmae_rowdot_partials(int B, long m);
+int ldmae_rowdot_f32(const float* a, const float* b, float* out, int B, long m, float* partial, void* stream);
+int ldmae_likelihood_finish_f32(const float* sumsq, const float* delta, float c, float* logp, int B, void* stream);
 
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */

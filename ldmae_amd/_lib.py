@@ -144,6 +144,10 @@ SIGNATURES = {
     "ldmae_dopri5_interp_f32": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _f, _vp, _l, _vp]),
     "ldmae_dopri5_advance": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ldmae_dopri5_initial_step": (_i, [_vp, _i, _vp, _vp]),
+    "ldmae_rademacher_f32": (_i, [_vp, _l, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "ldmae_rowdot_partials": (_l, [_i, _l]),
+    "ldmae_rowdot_f32": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "ldmae_likelihood_finish_f32": (_i, [_vp, _vp, _f, _vp, _i, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

@@ -13,6 +13,10 @@
 //
 // Step size, time and the accept decision stay on the device (ldmae_dopri5_advance): the kernels that read h and the decision taken from the
 // error ratio see the same bits, and the host reads one small status record per attempted step.
+//
+// Likelihood evaluation (transport.Sampler.sample_ode_likelihood) adds the Hutchinson probe and its reductions at the end of this file: the
+// Rademacher draw from Philox4x32-10 (Salmon et al., SC'11: a counter-based generator, so the draw is a function of (seed, counter, element)
+// alone), the per-sample dot product of two [B, m] tensors, and the last line of the log-likelihood.  Same rules: f32, no atomics, fixed order.
 #include "common.h"
 
 namespace {
@@ -241,6 +245,93 @@ __global__ void dopri5_initial_step_kernel(float* __restrict__ d, int phase, flo
   }
 }
 
+// ---------------------------------------------------------------- Rademacher probe: Philox4x32-10, one sign per 32-bit word
+constexpr unsigned PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(PHILOX_M0, c[0]), lo0 = PHILOX_M0 * c[0], hi1 = __umulhi(PHILOX_M1, c[2]), lo1 = PHILOX_M1 * c[2];
+    const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    k0 += PHILOX_W0; k1 += PHILOX_W1;
+  }
+}
+
+__device__ __forceinline__ float rad_sign(unsigned w) { return (w >> 31) ? 1.f : -1.f; }      // the top bit of the word
+
+// item v = the four signs of elements 4 v .. 4 v + 3 = the four words of the block with counter (counter, v); vec: out is 16-byte aligned
+__global__ __launch_bounds__(ODE_THREADS) void rademacher_kernel(float* __restrict__ out, long n, unsigned k0, unsigned k1, unsigned c0, unsigned c1,
+                                                                 int vec) {
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v > nvec || (v == nvec && (n & 3) == 0)) continue;
+    unsigned c[4] = {c0, c1, (unsigned)((unsigned long)v & 0xffffffffu), (unsigned)((unsigned long)v >> 32)};
+    philox4x32_10(c, k0, k1);
+    const float s[4] = {rad_sign(c[0]), rad_sign(c[1]), rad_sign(c[2]), rad_sign(c[3])};
+    if (v < nvec && vec) {
+      ((float4*)out)[v] = make_float4(s[0], s[1], s[2], s[3]);
+    } else {
+      const long e0 = v << 2;
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j < n) out[e0 + j] = s[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------- out[r] = sum_j a[r, j] b[r, j], rows of m floats
+// Stage 1: block (r, c) owns the 4096 elements [4096 c, 4096 c + 4096) of row r.  vec (both row starts 16-byte aligned for every r): thread t
+// takes the float4s t, t + 256, t + 512, t + 768 of the chunk, element order inside each; otherwise thread t takes the elements t, t + 256, ...
+// (16 of them).  One fma chain per thread, then ode_block_sum; partial[r * chunks + c].  Stage 2: one block per row folds its chunks.
+constexpr long ROW_CHUNK = 4096;
+
+__global__ __launch_bounds__(ODE_THREADS) void rowdot_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ partial,
+                                                             long m, long chunks, int vec) {
+  __shared__ float red[4];
+  const long r = blockIdx.x / chunks, c = blockIdx.x - r * chunks;
+  const float *ar = a + r * m, *br = b + r * m;
+  const long lo = c * ROW_CHUNK, hi = lo + ROW_CHUNK < m ? lo + ROW_CHUNK : m;
+  float s = 0.f;
+  if (vec) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long e = lo + 4 * ((long)threadIdx.x + (long)u * ODE_THREADS);
+      if (e + 4 <= hi) {
+        const float4 x = *(const float4*)(ar + e), y = *(const float4*)(br + e);
+        s = __builtin_fmaf(x.x, y.x, s); s = __builtin_fmaf(x.y, y.y, s); s = __builtin_fmaf(x.z, y.z, s); s = __builtin_fmaf(x.w, y.w, s);
+      } else {
+        for (long i = e; i < hi; ++i) s = __builtin_fmaf(ar[i], br[i], s);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const long i = lo + threadIdx.x + (long)u * ODE_THREADS;
+      if (i < hi) s = __builtin_fmaf(ar[i], br[i], s);
+    }
+  }
+  s = ode_block_sum(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(ODE_THREADS) void rowdot_fold_kernel(const float* __restrict__ partial, long chunks, float* __restrict__ out) {
+  __shared__ float red[4];
+  const float* p = partial + (long)blockIdx.x * chunks;
+  float s = 0.f;
+  for (long i = threadIdx.x; i < chunks; i += ODE_THREADS) s += p[i];
+  s = ode_block_sum(s, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+// logp[b] = (c - sumsq[b] / 2) - delta[b], each operation rounded once (no contraction: the host formula, operation by operation)
+__global__ void likelihood_finish_kernel(const float* __restrict__ sumsq, const float* __restrict__ delta, float c, float* __restrict__ logp, int B) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B) logp[i] = __fsub_rn(__fsub_rn(c, __fmul_rn(sumsq[i], 0.5f)), delta[i]);
+}
+
 template <int M>
 void launch_stage(const float* y, const float* k, long ld, const RkCoef& cf, const float* h_dev, float* out, long n, const float* t_dev, float ct,
                   float* t_out, int nt, hipStream_t st) {
@@ -319,5 +410,35 @@ extern "C" int ldmae_dopri5_initial_step(float* d_dev, int phase, float* h_dev, 
   LDMAE_REQUIRE(d_dev && h_dev && (phase == 0 || phase == 1), "dopri5_initial_step: bad arguments");
   hipLaunchKernelGGL(dopri5_initial_step_kernel, dim3(1), dim3(1), 0, as_stream(stream), d_dev, phase, h_dev);
   LDMAE_CHECK_LAUNCH("dopri5_initial_step");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_rademacher_f32(float* out, long n, unsigned long long seed, unsigned long long counter, void* stream) {
+  LDMAE_REQUIRE(out && n > 0 && ((uintptr_t)out & 3) == 0, "rademacher: bad arguments (n = %ld)", n);
+  LDMAE_REQUIRE(ode_items(n) <= 0x7fffffffL * ODE_BLOCK_ITEMS, "rademacher: n too large");
+  hipLaunchKernelGGL(rademacher_kernel, dim3(ode_grid(n)), dim3(ODE_THREADS), 0, as_stream(stream), out, n, (unsigned)(seed & 0xffffffffu),
+                     (unsigned)(seed >> 32), (unsigned)(counter & 0xffffffffu), (unsigned)(counter >> 32), al16(out) ? 1 : 0);
+  LDMAE_CHECK_LAUNCH("rademacher");
+  return LDMAE_OK;
+}
+
+extern "C" long ldmae_rowdot_partials(int B, long m) { return (B > 0 && m > 0) ? (long)B * cdiv(m, ROW_CHUNK) : 0; }
+
+extern "C" int ldmae_rowdot_f32(const float* a, const float* b, float* out, int B, long m, float* partial, void* stream) {
+  LDMAE_REQUIRE(a && b && out && partial && B > 0 && m > 0, "rowdot: bad arguments (B = %d, m = %ld)", B, m);
+  LDMAE_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0, "rowdot: a and b must be 4-byte aligned");
+  const long chunks = cdiv(m, ROW_CHUNK);
+  LDMAE_REQUIRE((long)B * chunks <= 0x7fffffffL, "rowdot: B * ceil(m / 4096) = %ld blocks is too many", (long)B * chunks);
+  const int vec = (al16(a) && al16(b) && (B == 1 || (m & 3) == 0)) ? 1 : 0;      // every row start 16-byte aligned
+  hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)(B * chunks)), dim3(ODE_THREADS), 0, as_stream(stream), a, b, partial, m, chunks, vec);
+  hipLaunchKernelGGL(rowdot_fold_kernel, dim3(B), dim3(ODE_THREADS), 0, as_stream(stream), partial, chunks, out);
+  LDMAE_CHECK_LAUNCH("rowdot");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_likelihood_finish_f32(const float* sumsq, const float* delta, float c, float* logp, int B, void* stream) {
+  LDMAE_REQUIRE(sumsq && delta && logp && B > 0, "likelihood_finish: bad arguments");
+  hipLaunchKernelGGL(likelihood_finish_kernel, dim3(cdiv(B, 256)), dim3(256), 0, as_stream(stream), sumsq, delta, c, logp, B);
+  LDMAE_CHECK_LAUNCH("likelihood_finish");
   return LDMAE_OK;
 }

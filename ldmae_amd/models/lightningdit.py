@@ -16,6 +16,7 @@ autocast behaviour (SURVEY.md §7 "mixed-precision semantics").
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import numpy as np
@@ -117,8 +118,9 @@ class _PatchEmbedFn(torch.autograd.Function):
     """tokens @ W^T + b + pos_embed (timm PatchEmbed as used at :309,402 then + pos_embed)."""
 
     @staticmethod
-    def forward(ctx, tok, w2d, b, pos, T, dtype=torch.float32):
+    def forward(ctx, tok, w2d, b, pos, T, dtype=torch.float32, input_only=False):
         tok = tok.contiguous()
+        ctx.input_only = bool(input_only)
         # under bf16 autocast the conv runs in bf16 (f32 accumulate, f32 output) like the reference's autocast conv2d; the bf16
         # MFMA GEMM needs K = C*p*p to be a multiple of 64 (VMAE 8x8x3 = 192; the DiT's K = 16 stays on the f32 kernel)
         lowp = dtype == torch.bfloat16 and tok.shape[1] % 64 == 0 and tok.shape[0] % 64 == 0
@@ -136,12 +138,14 @@ class _PatchEmbedFn(torch.autograd.Function):
     def backward(ctx, g):
         tok, w2d = ctx.saved_tensors
         g = g.contiguous()
+        if ctx.input_only:               # LightningDiT.input_grad_only: the token gradient alone
+            return ops.gemm_nt(g, ops.cast_weight(w2d, torch.float32, True, False)[1]), None, None, None, None, None, None
         dtok = ops.gemm_nt(g, ops.cast_weight(w2d, torch.float32, True, False)[1]) if ctx.needs_input_grad[0] else None
         if not ctx.lowp and g.dtype == torch.float32 and tok.dtype == torch.float32 and ops.thin_ok(g.shape[1], tok.shape[1]):
             dw, db = ops.thin_tn(g, tok)            # weight and bias gradient in ONE pass over the 805-MB gradient
-            return dtok, dw, db, None, None, None
+            return dtok, dw, db, None, None, None, None
         dw = ops.gemm_tn(ops.cast(g, torch.bfloat16), tok) if ctx.lowp else ops.gemm_tn(g, tok)
-        return dtok, dw, ops.colsum(g), None, None, None
+        return dtok, dw, ops.colsum(g), None, None, None, None
 
 
 def _dmod_times_w(dmod, adaw):
@@ -206,14 +210,14 @@ def _qk_layernorm_fwd(qkv, qnw, qnb, knw, knb, cos, sin, B, N, H, hd, dtype):
     return q, k, v, (q32, k32, muq, rsq, muk, rsk)
 
 
-def _qk_layernorm_bwd(dq, dk, dv, saved, qnw, knw, cos, sin, B, N, H, hd, dtype):
-    """-> (dqkv [B*N, 3*H*hd], dqnw, dqnb, dknw, dknb, dbqkv)."""
+def _qk_layernorm_bwd(dq, dk, dv, saved, qnw, knw, cos, sin, B, N, H, hd, dtype, with_bias=True):
+    """-> (dqkv [B*N, 3*H*hd], dqnw, dqnb, dknw, dknb, dbqkv); with_bias=False: no column sums, dbqkv None."""
     q32, k32, muq, rsq, muk, rsk = saved
     dxq, dxk = torch.zeros_like(q32), torch.zeros_like(k32)
     dqw, dqb = ops.layernorm_bwd(ops.rope(dq, cos, sin, transposed=True).view(-1, hd), q32, qnw, muq, rsq, dxq)
     dkw, dkb = ops.layernorm_bwd(ops.rope(dk, cos, sin, transposed=True).view(-1, hd), k32, knw, muk, rsk, dxk)
     dqkv = ops.heads_merge(ops.cast(dxq, dtype).view(B, H, N, hd), ops.cast(dxk, dtype).view(B, H, N, hd), dv, B, N, H, hd)
-    return dqkv, dqw, dqb, dkw, dkb, ops.colsum(dqkv)
+    return dqkv, dqw, dqb, dkw, dkb, (ops.colsum(dqkv) if with_bias else None)
 
 
 class _GradChain:
@@ -294,7 +298,7 @@ class _DiTBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, sc, cos, sin, H, eps, dtype, inplace, chain, idx, direct, fwd_only, mod_all, swiglu,
-                n1w, qkvw, qkvb, qnw, knw, qnb, knb, pw, pb, n2w, w12, b12, w3, b3, adaw, adab):
+                n1w, qkvw, qkvb, qnw, knw, qnb, knb, pw, pb, n2w, w12, b12, w3, b3, adaw, adab, input_only=False):
         """n1w / n2w None: LayerNorm without affine parameters (use_rmsnorm=False).  qnw / knw None: no QK-norm; with qnb / knb: nn.LayerNorm
         QK-norm (use_qknorm without use_rmsnorm).  swiglu False: w12 / b12 / w3 / b3 are fc1 / fc2 of the timm Mlp with tanh-GELU (use_swiglu=False)."""
         B, N, D = x.shape
@@ -357,6 +361,18 @@ class _DiTBlockFn(torch.autograd.Function):
         xout, y2 = ops.gemm_nt_gate_res(hid, W3, b3, xmid, g2, N, save_y=bwd)
         if not bwd:
             return xout.view(B, N, D)
+        ctx.input_only = bool(input_only)
+        if input_only:
+            # LightningDiT.input_grad_only: dx is wanted and nothing else.  Saved: what the dx chain reads (the weight-gradient GEMMs' left
+            # operands xm1 / xm2 / hid, SiLU(c) and the adaLN weight are not); y1 / y2 stay because the fused norm + gate backward reads them
+            ctx.save_for_backward(x2, cos, sin, mod, rstd1, qkv, q, k, v, o, lse, y1, xmid, rstd2, h12, y2, n1w, qnw, knw, n2w,
+                                  WqkvT, WpT, W12T, W3T, *(qk_saved or ()))
+            ctx.dims = (B, N, D, H, hd, eps, dtype)
+            ctx.swiglu, ctx.qk_ln, ctx.nmod, ctx.inplace = bool(swiglu), qk_saved is not None, nmod, bool(inplace)
+            ctx.chain, ctx.idx = chain, idx
+            if chain is not None:
+                chain.up[idx] = (y2, mod)
+            return xout.view(B, N, D)
         ctx.save_for_backward(x2, sc, cos, sin, mod, rstd1, xm1, qkv, q, k, v, o, lse, y1, xmid, rstd2, xm2, h12, hid, y2,
                               n1w, qnw, knw, n2w, adaw, WqkvT, WpT, W12T, W3T, *(qk_saved or ()))
         ctx.dims = (B, N, D, H, hd, eps, dtype)
@@ -371,7 +387,59 @@ class _DiTBlockFn(torch.autograd.Function):
         return xout.view(B, N, D)
 
     @staticmethod
+    def _backward_input_only(ctx, gout):
+        """The dx chain of backward() below, launch for launch, and nothing else: no weight-gradient GEMM, no side stream, no bias / norm-weight /
+        QK-norm-weight reduction that a kernel lets us turn off, no adaLN gradients, no .grad writes.  Kernels that form a parameter gradient
+        as a by-product of the pass that produces dx (the fused norm + gate backward, the attention backward with the QK-norm epilogue, the
+        norm backward's weight and modulation sums) run unchanged and the by-product is dropped: dx has the bits of the full backward."""
+        (x2, cos, sin, mod, rstd1, qkv, q, k, v, o, lse, y1, xmid, rstd2, h12, y2, n1w, qnw, knw, n2w, WqkvT, WpT, W12T, W3T) = ctx.saved_tensors[:24]
+        qk_saved = ctx.saved_tensors[24:] if ctx.qk_ln else None
+        B, N, D, H, hd, eps, dtype = ctx.dims
+        M = B * N
+        dx = gout.contiguous().view(M, D)
+        if not ctx.inplace and dx.data_ptr() == gout.data_ptr():
+            dx = dx.clone()
+        chain, idx = ctx.chain, ctx.idx
+        c_sh1, c_s1, c_g1, c_sh2, c_s2, c_g2 = (0, 1, 2, 3, 4, 5) if ctx.nmod == 6 else (None, 0, 1, None, 2, 3)
+        col = lambda t_, c_: None if c_ is None else t_[:, c_ * D:(c_ + 1) * D]      # noqa: E731
+        s1, g1, s2, g2 = col(mod, c_s1), col(mod, c_g1), col(mod, c_s2), col(mod, c_g2)
+        # ---- MLP branch
+        pre = chain.pre.pop(idx, None) if chain is not None else None
+        if pre is not None and pre[0] == dx.data_ptr():
+            _, dy2, _, dmod = pre
+        else:
+            dmod = chain.dmod(idx, mod) if chain is not None else torch.empty(mod.shape, dtype=mod.dtype, device=mod.device)
+            dy2 = ops.gate_bwd(dx, y2, g2, None, N, dtype)
+        if ctx.swiglu:
+            dh12 = ops.gemm_nt_swiglu_bwd(dy2, W3T, h12)
+        else:
+            dh12 = ops.gelu_tanh_bwd(ops.gemm_nt(dy2, W3T), h12)
+        dxm2 = ops.gemm_nt(dh12, W12T)
+        _, dy1, _ = ops.rmsnorm_modulate_bwd_gate(dxm2, xmid, n2w, s2, rstd2, dx, col(dmod, c_sh2), col(dmod, c_s2), y1, g1, col(dmod, c_g1), N, dtype)
+        # ---- attention branch
+        do = ops.gemm_nt(dy1, WpT)
+        if qk_saved is not None:
+            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
+            dqkv = _qk_layernorm_bwd(dq, dk, dv, qk_saved, qnw, knw, cos, sin, B, N, H, hd, dtype, with_bias=False)[0]
+        elif v is None and hd in (64, 128) and N % 64 == 0 and _FUSED_QKN_BWD:
+            dqkv = ops.attention_bwd_pv_qknorm(q, k, qkv, o, do, lse, hd ** -0.5, qnw, knw, cos, sin, eps)[0]
+        elif v is None:
+            dq, dk, dqkv = ops.attention_bwd_pv(q, k, qkv, o, do, lse, hd ** -0.5)
+            dqkv = ops.qknorm_rope_bwd(dq, dk, None, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, dqkv=dqkv)[0]
+        else:
+            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
+            dqkv = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, B, N, H, hd, eps)[0]
+        dxm1 = ops.gemm_nt(dqkv.view(M, 3 * D), WqkvT)
+        if chain is not None:
+            chain.norm_bwd(idx, dxm1, x2, n1w, s1, rstd1, dx, col(dmod, c_sh1), col(dmod, c_s1), N, dtype)
+        else:
+            ops.rmsnorm_modulate_bwd(dxm1, x2, n1w, s1, rstd1, dx, col(dmod, c_sh1), col(dmod, c_s1), N)
+        return (dx.view(B, N, D),) + (None,) * 30
+
+    @staticmethod
     def backward(ctx, gout):
+        if ctx.input_only:
+            return _DiTBlockFn._backward_input_only(ctx, gout)
         (x2, sc, cos, sin, mod, rstd1, xm1, qkv, q, k, v, o, lse, y1, xmid, rstd2, xm2, h12, hid, y2,
          n1w, qnw, knw, n2w, adaw, WqkvT, WpT, W12T, W3T) = ctx.saved_tensors[:29]
         qk_saved = ctx.saved_tensors[29:] if ctx.qk_ln else None
@@ -458,7 +526,7 @@ class _DiTBlockFn(torch.autograd.Function):
             if r is not None:
                 r(p_)
         return (dx.view(B, N, D), dsc, None, None, None, None, None, None, None, None, None, None, dmod_all, None,
-                dn1, dWqkv, dbqkv, dqn, dkn, dqnb, dknb, dWp, dbp, dn2, dW12, db12, dW3, db3, dadaw, dadab)
+                dn1, dWqkv, dbqkv, dqn, dkn, dqnb, dknb, dWp, dbp, dn2, dW12, db12, dW3, db3, dadaw, dadab, None)
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -517,8 +585,9 @@ class _FinalLayerFn(torch.autograd.Function):
     """FinalLayer.forward (:267-272): adaLN(2) -> RMSNorm -> modulate -> Linear."""
 
     @staticmethod
-    def forward(ctx, x, sc, eps, dtype, chain, idx, nw, lw, lb, adaw, adab):
+    def forward(ctx, x, sc, eps, dtype, chain, idx, nw, lw, lb, adaw, adab, input_only=False):
         B, N, D = x.shape
+        ctx.input_only = bool(input_only)
         M = B * N
         x2 = x.contiguous().view(M, D)
         sc = sc.contiguous()
@@ -536,8 +605,10 @@ class _FinalLayerFn(torch.autograd.Function):
         B, N, D, dtype = ctx.dims
         M = B * N
         g = gout.contiguous().view(M, -1)
-        ga = ops.cast(g, dtype)
-        dlw, dlb = ops.gemm_tn(ga, xf), ops.colsum(g)
+        io = ctx.input_only              # LightningDiT.input_grad_only: the dx chain alone (the norm backward's weight / modulation sums are dropped)
+        if not io:
+            ga = ops.cast(g, dtype)
+            dlw, dlb = ops.gemm_tn(ga, xf), ops.colsum(g)
         if g.dtype == torch.float32 and ops.thin_ok(lw.shape[1], lw.shape[0]):                        # K = p*p*C = 16 / 32: ldmae_thin_nt
             dxf = ops.thin_nt(g, lw.float().t().contiguous(), out_dtype=dtype)
         else:
@@ -548,9 +619,11 @@ class _FinalLayerFn(torch.autograd.Function):
             dnw = ctx.chain.norm_bwd(ctx.idx, dxf, x2, nw, mod[:, D:], rstd, dx, dmod[:, :D], dmod[:, D:], N, dtype, accumulate=False)
         else:
             dnw = ops.rmsnorm_modulate_bwd(dxf, x2, nw, mod[:, D:], rstd, dx, dmod[:, :D], dmod[:, D:], N, accumulate=False)
+        if io:
+            return (dx.view(B, N, D),) + (None,) * 11
         dadaw, dadab = ops.gemm_tn(dmod, sc), ops.colsum(dmod)
         dsc = _dmod_times_w(dmod, adaw)
-        return dx.view(B, N, D), dsc, None, None, None, None, dnw, dlw, dlb, dadaw, dadab
+        return dx.view(B, N, D), dsc, None, None, None, None, dnw, dlw, dlb, dadaw, dadab, None
 
 
 # ----------------------------------------------------------------------------- modules (reference names / keys)
@@ -576,7 +649,7 @@ class PatchEmbed(nn.Module):
         x = x.float().reshape(B, C, Hh // p, p, Ww // p, p).permute(0, 2, 4, 1, 3, 5)
         return x.reshape(B * (Hh // p) * (Ww // p), C * p * p)
 
-    def forward(self, x, pos=None, dtype=None):
+    def forward(self, x, pos=None, dtype=None, input_only=False):
         B = x.shape[0]
         w2d = self.proj.weight.view(self.proj.weight.shape[0], -1)
         if pos is None:
@@ -586,7 +659,7 @@ class PatchEmbed(nn.Module):
             pad = (-w2d.shape[1]) % 16    # and the weight gradient comes back through the pad sliced to the real columns
             tok, w2d = torch.nn.functional.pad(tok, (0, pad)), torch.nn.functional.pad(w2d, (0, pad))
         return _PatchEmbedFn.apply(tok, w2d, self.proj.bias, pos, self.num_patches,
-                                   dtype or torch.float32).view(B, self.num_patches, -1)
+                                   dtype or torch.float32, input_only).view(B, self.num_patches, -1)
 
 
 class TimestepEmbedder(nn.Module):
@@ -718,7 +791,8 @@ class LightningDiTBlock(nn.Module):
         self.wo_shift = wo_shift
         self.precision = None
 
-    def forward(self, x, c, feat_rope=None, _silu_c=None, _dtype=None, _inplace_grad=False, _chain=None, _idx=0, _direct=False, _mod_all=None):
+    def forward(self, x, c, feat_rope=None, _silu_c=None, _dtype=None, _inplace_grad=False, _chain=None, _idx=0, _direct=False, _mod_all=None,
+                _input_only=False):
         sc = _silu_c if _silu_c is not None else _SiluFn.apply(c.float())
         a, m = self.attn, self.mlp
         cos, sin = (feat_rope.freqs_cos, feat_rope.freqs_sin) if feat_rope is not None else _identity_rope(x.shape[1], a.head_dim, x.device)
@@ -730,7 +804,7 @@ class LightningDiTBlock(nn.Module):
             _inplace_grad, _chain, _idx, _direct, not torch.is_grad_enabled(), _mod_all, swiglu,
             self.norm1.weight, a.qkv.weight, a.qkv.bias, qnw, knw, qnb, knb, a.proj.weight, a.proj.bias,
             self.norm2.weight, l1.weight, l1.bias, l2.weight, l2.bias,
-            self.adaLN_modulation[1].weight, self.adaLN_modulation[1].bias)
+            self.adaLN_modulation[1].weight, self.adaLN_modulation[1].bias, _input_only)
 
 
 class FinalLayer(nn.Module):
@@ -743,7 +817,7 @@ class FinalLayer(nn.Module):
         self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 2 * hidden_size, bias=True))
         self.precision = None
 
-    def forward(self, x, c, _silu_c=None, _dtype=None, _chain=None, _idx=0):
+    def forward(self, x, c, _silu_c=None, _dtype=None, _chain=None, _idx=0, _input_only=False):
         sc = _silu_c if _silu_c is not None else _SiluFn.apply(c.float())
         lw, lb = self.linear.weight, self.linear.bias
         nout = lw.shape[0]
@@ -751,7 +825,7 @@ class FinalLayer(nn.Module):
             pad = (-nout) % 16
             lw, lb = torch.nn.functional.pad(lw, (0, 0, 0, pad)), torch.nn.functional.pad(lb, (0, pad))
         out = _FinalLayerFn.apply(x.float(), sc, self.norm_final.eps, _dtype or _act_dtype(self.precision), _chain, _idx,
-                                  self.norm_final.weight, lw, lb, self.adaLN_modulation[1].weight, self.adaLN_modulation[1].bias)
+                                  self.norm_final.weight, lw, lb, self.adaLN_modulation[1].weight, self.adaLN_modulation[1].bias, _input_only)
         return out if out.shape[-1] == nout else out[..., :nout]
 
 
@@ -793,6 +867,7 @@ class LightningDiT(nn.Module):
                               use_rmsnorm=use_rmsnorm, wo_shift=wo_shift) for _ in range(depth)])
         self.final_layer = FinalLayer(hidden_size, patch_size, self.out_channels, use_rmsnorm=use_rmsnorm)
         self.precision = None          # None: follow torch.autocast; or torch.float32 / torch.bfloat16
+        self._input_grad_only = False  # see input_grad_only()
         self.initialize_weights()
 
     def set_precision(self, dtype):
@@ -802,6 +877,19 @@ class LightningDiT(nn.Module):
             b.attn.precision = dtype
         self.final_layer.precision = dtype
         return self
+
+    @contextlib.contextmanager
+    def input_grad_only(self, on=True):
+        """Inside this context a grad-enabled forward builds a graph whose backward returns the gradient with respect to the input x ALONE:
+        every parameter gets None (its .grad is left as it is), the conditioning path (t, y) is evaluated without a graph -- it does not depend
+        on x -- and the backward launches no weight-gradient GEMM, no side stream and no bias / norm-weight reduction it can avoid.  dx has the
+        bits of the full backward.  For vector-Jacobian products with frozen weights (likelihood evaluation: transport.Sampler.
+        sample_ode_likelihood); off by default, training never enters it."""
+        was, self._input_grad_only = self._input_grad_only, bool(on)
+        try:
+            yield self
+        finally:
+            self._input_grad_only = was
 
     def initialize_weights(self):
         """:340-374."""
@@ -844,12 +932,21 @@ class LightningDiT(nn.Module):
         dtype = _act_dtype(self.precision)
         if dtype != torch.float32 and self.hidden_size % 64 != 0:
             dtype = torch.float32         # the 16-bit MFMA GEMMs contract in steps of 64: other widths (no registry entry has one) keep f32 activations
+        io = self._input_grad_only and torch.is_grad_enabled()
+        if io and self.use_checkpoint:
+            raise NotImplementedError("ldmae_amd LightningDiT: input_grad_only with use_checkpoint is not implemented (nothing to recompute for: no parameter gradients)")
         with torch.autocast(device_type="cuda", enabled=False):
-            x = self.x_embedder(x, self.pos_embed[0])
-            t = self.t_embedder(t)
-            y = self.y_embedder(y, self.training)
-            c = t + y
-            sc = _SiluFn.apply(c)
+            if io:                        # input_grad_only(): the conditioning does not depend on x -- no graph through it
+                x = self.x_embedder(x, self.pos_embed[0], input_only=True)
+                with torch.no_grad():
+                    c = self.t_embedder(t) + self.y_embedder(y, self.training)
+                    sc = _SiluFn.apply(c)
+            else:
+                x = self.x_embedder(x, self.pos_embed[0])
+                t = self.t_embedder(t)
+                y = self.y_embedder(y, self.training)
+                c = t + y
+                sc = _SiluFn.apply(c)
             # a block output of this chain has exactly one consumer (the next block / the final layer) unless someone taps it with a
             # module hook: only then may a block's backward re-use the incoming gradient buffer, and only when that holds for the
             # whole chain do consecutive backward passes hand work to each other (_GradChain)
@@ -866,15 +963,19 @@ class LightningDiT(nn.Module):
             if self._use_batched_adaln() and dtype == torch.bfloat16 and not self.use_checkpoint and len(self.blocks) <= 64 and sc.shape[0] % 8 == 0 and \
                     (chain is not None or not torch.is_grad_enabled()):
                 lins = [b.adaLN_modulation[1] for b in self.blocks]
-                mod_all = _AdaLNAllFn.apply(sc, not torch.is_grad_enabled(), *[l.weight for l in lins], *[l.bias for l in lins])
+                if io:
+                    with torch.no_grad():
+                        mod_all = _AdaLNAllFn.apply(sc, True, *[l.weight for l in lins], *[l.bias for l in lins])
+                else:
+                    mod_all = _AdaLNAllFn.apply(sc, not torch.is_grad_enabled(), *[l.weight for l in lins], *[l.bias for l in lins])
                 if chain is not None:
                     chain.mod_cols = mod_all.shape[1]
             for i, block in enumerate(self.blocks):
                 if self.use_checkpoint:
                     x = checkpoint(block, x, c, self.feat_rope, sc, dtype, not hooked[i], use_reentrant=True)
                 else:
-                    x = block(x, c, self.feat_rope, sc, dtype, not hooked[i], chain, i, self.direct_param_grads and chain is not None, mod_all)
-            x = self.final_layer(x, c, sc, dtype, chain, len(self.blocks))
+                    x = block(x, c, self.feat_rope, sc, dtype, not hooked[i], chain, i, self.direct_param_grads and chain is not None and not io, mod_all, io)
+            x = self.final_layer(x, c, sc, dtype, chain, len(self.blocks), io)
             x = self.unpatchify(x)
             if self.learn_sigma:
                 x, _ = x.chunk(2, dim=1)

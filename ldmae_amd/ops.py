@@ -16,6 +16,8 @@ from . import _lib as L
 from ._lib import (BF16, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_POS, EPI_F16_INF, EPI_GATE_RES, EPI_GELU_BWD, EPI_HALF_LINES, EPI_SWIGLU, EPI_SWIGLU_BWD, EPI_TILE_LAUNCH, F32, call, dt,
                    ptr, stream)
 
+launch_counts = L.launch_counts      # launch counts by kernel family (which arithmetic type, which GEMM form the calls were dispatched to)
+
 _ws = {}
 
 
@@ -1564,3 +1566,41 @@ def dopri5_initial_step(d_dev, phase, h_dev):
     """The Hairer-Norsett-Wanner starting step from the norms d_dev = (d0, d1, d2 * h0, h0): phase 0 writes h0, phase 1 the step, to h_dev."""
     _ode_scalar(d_dev, "dopri5_initial_step d_dev", 4), _ode_scalar(h_dev, "dopri5_initial_step h_dev")
     call("ldmae_dopri5_initial_step", ptr(d_dev), int(phase), ptr(h_dev), stream())
+
+
+# ----------------------------------------------------------------------------- likelihood evaluation (csrc/ode.hip), f32
+def rademacher(shape, seed, counter, device):
+    """+-1.0 of the given shape from Philox4x32-10 keyed by `seed`, counter words (counter, element index / 4); one sign per 32-bit word (its top
+    bit).  A function of (seed, counter, element index) alone; transport/probe.py restates it in numpy bit for bit."""
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    if out.numel() == 0:
+        raise RuntimeError("rademacher: empty shape")
+    call("ldmae_rademacher_f32", ptr(out), out.numel(), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), stream())
+    return out
+
+
+def rowdot(a, b=None, out=None):
+    """out[r] = sum over everything but dim 0 of a[r] * b[r] (b None: b = a, the row sums of squares); f32, contiguous, two-stage fixed-order sum."""
+    b = a if b is None else b
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous() or a.dim() < 1 \
+            or a.numel() == 0:
+        raise RuntimeError(f"rowdot: two contiguous non-empty f32 tensors of one shape expected, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    B, m = a.shape[0], a.numel() // a.shape[0]
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=a.device)
+    else:
+        _ode_vec(out, "rowdot out", B)
+    partial = torch.empty(int(L.load().ldmae_rowdot_partials(B, m)), dtype=torch.float32, device=a.device)
+    call("ldmae_rowdot_f32", ptr(a), ptr(b), ptr(out), B, m, ptr(partial), stream())
+    return out
+
+
+def likelihood_finish(sumsq, delta, m):
+    """logp[b] = (-m / 2 log(2 pi) - sumsq[b] / 2) - delta[b]: transport.prior_logp of a state with row sums of squares `sumsq` minus the
+    integrated divergence."""
+    import math
+    B = sumsq.numel()
+    _ode_vec(sumsq, "likelihood_finish sumsq", B), _ode_vec(delta, "likelihood_finish delta", B)
+    out = torch.empty(B, dtype=torch.float32, device=sumsq.device)
+    call("ldmae_likelihood_finish_f32", ptr(sumsq), ptr(delta), -m / 2.0 * math.log(2 * math.pi), ptr(out), B, stream())
+    return out

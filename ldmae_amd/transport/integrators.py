@@ -44,7 +44,11 @@ class ode:
         self.nfe = self.accepted = self.rejected = 0            # set by sample() (dopri5)
 
     def sample(self, x, model, **model_kwargs):
-        """Returns the stacked trajectory [len(t), ...] like odeint; callers take [-1] (inference.py:287)."""
+        """Returns the stacked trajectory [len(t), ...] like odeint; callers take [-1] (inference.py:287).  x may be the tuple (x, logp) of
+        likelihood evaluation (logp [B] f32): the drift then maps ((x, logp), t, model) to the pair of derivatives, and the result is the
+        tuple of the two stacked trajectories, as odeint returns it."""
+        if isinstance(x, (tuple, list)):
+            return self._sample_augmented(tuple(x), model, **model_kwargs)
         if self.sampler_type == "dopri5":
             return self._sample_dopri5(x, model, **model_kwargs)
         t = self.t.to(x.device)
@@ -66,7 +70,41 @@ class ode:
                 xs.append(x)
         return th.stack(xs)
 
-    def _sample_dopri5(self, x, model, **model_kwargs):
+    def _sample_augmented(self, state, model, **model_kwargs):
+        """The tuple state (x, logp).  torchdiffeq flattens the tuple into ONE vector of n + B elements, with one tolerance per element and the
+        RMS norm over that whole vector; so does this: dopri5 runs on slab rows of n + B floats (x first, logp behind it), with the kernels and
+        the controller of the plain state.  The fixed-step methods apply their update to both members."""
+        if len(state) != 2:
+            raise ValueError("ode.sample: a tuple state is the pair (x, logp)")
+        x, logp = state
+        if logp.shape != (x.shape[0],) or logp.dtype != th.float32 or x.dtype != th.float32:
+            raise ValueError(f"ode.sample: (x, logp) needs f32 x and f32 logp of shape [{x.shape[0]}], got {x.dtype} and {tuple(logp.shape)} {logp.dtype}")
+        if self.sampler_type == "dopri5":
+            return self._sample_dopri5(x, model, logp=logp, **model_kwargs)
+        t = self.t.to(x.device)
+
+        def f(tk, s):
+            return self.drift(s, th.ones(x.size(0), device=x.device) * tk, model, **model_kwargs)
+
+        def step(s, c, d):
+            return tuple(a + c * b for a, b in zip(s, d))
+
+        s, out = (x, logp), [(x, logp)]
+        with th.no_grad():
+            for k in range(len(t) - 1):
+                dt = t[k + 1] - t[k]
+                if self.sampler_type == "euler":
+                    s = step(s, dt, f(t[k], s))
+                elif self.sampler_type == "midpoint":
+                    s = step(s, dt, f(t[k] + dt / 2, step(s, dt / 2, f(t[k], s))))
+                else:
+                    k1 = f(t[k], s)
+                    k2 = f(t[k + 1], step(s, dt, k1))
+                    s = step(s, dt / 2, tuple(a + b for a, b in zip(k1, k2)))
+                out.append(s)
+        return th.stack([o[0] for o in out]), th.stack([o[1] for o in out])
+
+    def _sample_dopri5(self, x, model, logp=None, **model_kwargs):
         """Adaptive Dormand-Prince 5(4) with FSAL from t[0] to t[-1], controlled as torchdiffeq controls it: the error ratio is the RMS over the
         WHOLE state tensor (all samples, both CFG halves) of err / (atol + rtol max(|y0|, |y1|)); a step is accepted when it is <= 1; the next
         step is h min(10, max(0.9 / ratio^(1/5), 1 if accepted else 0.2)); the first step comes from the Hairer-Norsett-Wanner rule under the
@@ -75,20 +113,30 @@ class ode:
         under the reference.  Sets self.nfe / accepted / rejected.
 
         Everything between two model evaluations is one HIP launch (ops.rk_stage / dopri5_finish / dopri5_advance / dopri5_interp); t, h and
-        the ratio stay on the device and the host reads one 6-float record per attempted step (the only synchronisation of the solver)."""
+        the ratio stay on the device and the host reads one 6-float record per attempted step (the only synchronisation of the solver).
+
+        logp (the augmented state of _sample_augmented): the state vector is x flattened followed by logp, n = x.numel() + B; the drift is handed
+        (x, logp) and its two results go to k[s, :x.numel()] and k[s, x.numel():n].  Returns the pair of trajectories."""
         import numpy as np
         from .. import ops
         if not x.is_cuda:
             raise RuntimeError("ldmae_amd dopri5: the solver's kernels need the state on a HIP device (no CPU fallback); got " + str(x.device))
         grid = [float(v) for v in self.t.to(th.float32)]
-        shape, n, dev = x.shape, x.numel(), x.device
+        shape, nx, dev = x.shape, x.numel(), x.device
+        n = nx if logp is None else nx + logp.numel()
         ld = ops.ode_slab_ld(n)
-        traj = th.empty((len(grid),) + tuple(shape), dtype=th.float32, device=dev)
-        traj[0].copy_(x)
+        traj = th.empty((len(grid),) + (tuple(shape) if logp is None else (n,)), dtype=th.float32, device=dev)
+        if logp is None:
+            traj[0].copy_(x)
         k = th.empty(7, ld, dtype=th.float32, device=dev)
         ybuf = th.empty(4, ld, dtype=th.float32, device=dev)
         y, y1, ytmp, ymid = (ybuf[i, :n] for i in range(4))
-        y.copy_(x.reshape(-1))
+        if logp is None:
+            y.copy_(x.reshape(-1))
+        else:
+            y[:nx].copy_(x.reshape(-1))
+            y[nx:].copy_(logp)
+            traj[0].copy_(y)
         partial = th.empty(ops.ode_partials(n), dtype=th.float32, device=dev)
         # device scalars: t, h, ratio, the constant 1, the status record of dopri5_advance (6), the norms of the starting-step rule (4)
         st = th.tensor([grid[0], 0.0, 0.0, 1.0] + [0.0] * 10, dtype=th.float32, device=dev)
@@ -97,8 +145,13 @@ class ode:
         self.nfe = self.accepted = self.rejected = 0
 
         def f(yin, slot):
-            out = self.drift(yin.view(shape), tvec, model, **model_kwargs)
-            k[slot, :n].view(shape).copy_(out)
+            if logp is None:
+                out = self.drift(yin.view(shape), tvec, model, **model_kwargs)
+                k[slot, :n].view(shape).copy_(out)
+            else:
+                dx, dlogp = self.drift((yin[:nx].view(shape), yin[nx:]), tvec, model, **model_kwargs)
+                k[slot, :nx].view(shape).copy_(dx)
+                k[slot, nx:n].copy_(dlogp)
             self.nfe += 1
 
         with th.no_grad():
@@ -144,4 +197,6 @@ class ode:
                 ops.dopri5_interp(y1, y, ymid, k, status[3:4], status[2:3], grid[i], dst)
                 if n % 4:
                     traj[i].view(-1).copy_(dst)
+        if logp is not None:
+            return traj[:, :nx].reshape((len(grid),) + tuple(shape)), traj[:, nx:].contiguous()
         return traj

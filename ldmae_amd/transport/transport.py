@@ -1,4 +1,5 @@
 """Transport objective + samplers (reference: LDMAE/transport/transport.py)."""
+import contextlib
 import enum
 
 import numpy as np
@@ -113,7 +114,7 @@ class Transport:
 
 
 class Sampler:
-    """transport.py:270-443, ODE sampler (the SDE sampler and likelihood evaluation are out of scope, SURVEY.md 2.1 #7)."""
+    """transport.py:270-502, ODE sampler and likelihood evaluation (the SDE sampler is out of scope, SURVEY.md 2.1 #7)."""
 
     def __init__(self, transport):
         self.transport = transport
@@ -128,3 +129,48 @@ class Sampler:
 
     def sample_sde(self, **_):
         raise NotImplementedError("ldmae_amd Sampler: SDE sampling is out of scope (SURVEY.md 2.1 #7); run_inference.sh uses sample_ode")
+
+    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, seed=0, noise=None):
+        """transport.py:445-502: a function (x, model, **model_kwargs) -> (logp, z).  The probability-flow ODE is integrated from data to noise
+        (time reversed: t -> 1 - t, state derivative -v) on the augmented state (x, logp); d logp / dt is Hutchinson's estimate eps^T (dv/dx) eps
+        of the divergence with a fresh Rademacher eps per drift evaluation, and logp = prior_logp(z) - delta_logp.
+
+        Where this departs from the reference: the network runs ONCE per drift evaluation -- v and the vector-Jacobian product eps^T dv/dx come
+        from the same forward (the reference runs it a second time for v) -- and eps is a named draw: ops.rademacher (Philox4x32-10) keyed by
+        `seed` with the evaluation index as the counter, so a likelihood is a function of (x, seed).  noise(nfe_index, shape) -> a +-1 tensor
+        replaces the draw (tests).  A model with an input-gradient-only backward (LightningDiT.input_grad_only) is evaluated in that mode: no
+        parameter gradient is computed."""
+        from .. import ops
+        calls = [0]
+
+        def _likelihood_drift(state, t, model, **model_kwargs):
+            x, _ = state
+            idx, calls[0] = calls[0], calls[0] + 1
+            eps = noise(idx, x.shape).to(x) if noise is not None else ops.rademacher(x.shape, seed, idx, x.device)
+            t = th.ones_like(t) * (1 - t)
+            with th.enable_grad():
+                xg = x.detach().requires_grad_(True)
+                v = self.drift(xg, t, model, **model_kwargs)
+                (vjp,) = th.autograd.grad(v, xg, grad_outputs=eps.contiguous())
+            return -v.detach(), ops.rowdot(vjp.contiguous(), eps.contiguous())
+
+        t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, sde=False, eval=True, reverse=False,
+                                               last_step_size=0.0)
+        _ode = ode(drift=_likelihood_drift, t0=t0, t1=t1, sampler_type=sampling_method, num_steps=num_steps, atol=atol, rtol=rtol)
+
+        def _sample_fn(x, model, **model_kwargs):
+            if not x.is_cuda:
+                raise RuntimeError("ldmae_amd likelihood: the probe, its reductions and the solver are HIP kernels: the state must be on a HIP "
+                                   "device (no CPU fallback); got " + str(x.device))
+            calls[0] = 0
+            x = x.float().contiguous()
+            owner = getattr(model, "__self__", model)                       # model may be a bound method (forward / forward_with_cfg)
+            mode = owner.input_grad_only() if hasattr(owner, "input_grad_only") else contextlib.nullcontext()
+            with mode:
+                zs, deltas = _ode.sample((x, th.zeros(x.size(0), dtype=th.float32, device=x.device)), model, **model_kwargs)
+            z, delta = zs[-1].contiguous(), deltas[-1].contiguous()
+            logp = ops.likelihood_finish(ops.rowdot(z), delta, z[0].numel())     # prior_logp(z) - delta_logp in one launch
+            return logp, z
+
+        _sample_fn.ode = _ode                                               # nfe / accepted / rejected of the last call
+        return _sample_fn
