@@ -419,6 +419,34 @@ int ldmae_lpips_layer_bwd(const float* f, const float* lin_w, const float* g, fl
                           int accumulate, void* stream);
 int ldmae_lpips_prep_bwd(const float* g, float* out, int B, int H, int W, void* stream);
 
+/* ---- LPIPS in 16 bits (models/lpips.py, precision="fp16"; csrc/lpips_f16.hip): the reference's autocast arithmetic without its loss scaler ----
+ * The arithmetic contract.  FORWARD: every conv operand is fp16 (round to nearest even, saturating at +-65504 as ldmae_cast does); products are
+ * exact in f32 and accumulated in f32 on v_mfma_f32_16x16x32_f16; bias is added in f32, ReLU applied, and the result rounded ONCE to fp16
+ * (saturating) and stored as fp16 NHWC: activations between layers live in memory as fp16.  The max pool runs on fp16 (exact); the heads read the
+ * fp16 taps and do all their arithmetic in f32.  BACKWARD: gradients stay f32 in memory; the data-gradient conv rounds both operands to bf16
+ * (dy * [y > 0] at the fetch, w_rot once by the caller), accumulates in f32 on v_mfma_f32_16x16x32_bf16 and writes f32; the ReLU mask is y > 0 on
+ * the stored fp16 activation.  bf16, not fp16: the gradient scales as 1 / (h w) and falls below fp16's smallest normal already at 33 x 47.
+ * No split K, no atomics: summation order is fixed by the shape, the same bits run to run.
+ * lpips_prep_f16: ldmae_lpips_prep's f32 arithmetic, then one rounding; out fp16 NHWC [2B, H, W, 8], channels 3 .. 7 zero.  out 16-B aligned.
+ * conv3x3_relu_nhwc_f16: x fp16 [B, H, W, Cin] (Cin % 8 == 0), w fp16 [Cout, 3, 3, Cin], bias f32 [Cout] or NULL, out fp16 [B, H, W, Cout] =
+ * fp16(max(conv + bias, 0)); stride 1, pad 1; any Cout, any B H W.  x, w 16-B aligned.
+ * maxpool2x2_nhwc_f16: x fp16 [B, H, W, C] (C % 8 == 0, H, W >= 2) -> out fp16 [B, H/2, W/2, C]; the odd last row / column is dropped.
+ * lpips_layer_f16 / lpips_layer_bwd_f16: ldmae_lpips_layer / ldmae_lpips_layer_bwd with f fp16; out, g, d_input, d_target f32, the same arithmetic.
+ * conv3x3_relu_dgrad_nhwc_bf16: dy f32 [B, H, W, Cy] (Cy % 8 == 0), y fp16 of the same shape, w_rot bf16 [Cx, 3, 3, Cy], dx f32 [B, H, W, Cx],
+ * overwritten.  dy, y, w_rot 16-B aligned.
+ * maxpool2x2_bwd_nhwc_xf16: ldmae_maxpool2x2_bwd_nhwc_f32 with the pooled input x fp16; dy, dx f32.
+ * lpips_prep_bwd_c8: g f32 NHWC [B, H, W, 8] (conv1_1's data gradient; channels 3 .. 7 are ignored) -> out NCHW [B, 3, H, W] = g[..., c] / scale[c]. */
+int ldmae_lpips_prep_f16(const float* input, const float* target, void* out, int B, int H, int W, void* stream);
+int ldmae_conv3x3_relu_nhwc_f16(const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout, void* stream);
+int ldmae_maxpool2x2_nhwc_f16(const void* x, void* out, int B, int H, int W, int C, void* stream);
+int ldmae_lpips_layer_f16(const void* f, const float* lin_w, float* out, int B, int h, int w, int C, void* workspace, void* stream);
+int ldmae_conv3x3_relu_dgrad_nhwc_bf16(const float* dy, const void* y, const void* w_rot, float* dx, int B, int H, int W, int Cy, int Cx,
+                                       void* stream);
+int ldmae_maxpool2x2_bwd_nhwc_xf16(const float* dy, const void* x, float* dx, int B, int H, int W, int C, void* stream);
+int ldmae_lpips_layer_bwd_f16(const void* f, const float* lin_w, const float* g, float* d_input, float* d_target, int B, int h, int w, int C,
+                              int accumulate, void* stream);
+int ldmae_lpips_prep_bwd_c8(const float* g, float* out, int B, int H, int W, void* stream);
+
 /* ---- convolutional KL-VAE tokenizers (tokenizer/autoencoder.py: the LDM Encoder / Decoder), f32 NHWC, forward only -----------------------
  * groupnorm_stats: mean / rstd [B, G] of x [B, HW, C]: per (image, group) mean and rstd = 1 / sqrt(var + eps), biased variance over the
  * HW * (C / G) elements of the group; two passes (mean, then the mean of (x - mean)^2), blocked summation (csrc/conv_vae.hip).

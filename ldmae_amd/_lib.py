@@ -129,6 +129,14 @@ SIGNATURES = {
     "ldmae_maxpool2x2_bwd_nhwc_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ldmae_lpips_layer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ldmae_lpips_prep_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ldmae_lpips_prep_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ldmae_conv3x3_relu_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_maxpool2x2_nhwc_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "ldmae_lpips_layer_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ldmae_conv3x3_relu_dgrad_nhwc_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_maxpool2x2_bwd_nhwc_xf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ldmae_lpips_layer_bwd_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ldmae_lpips_prep_bwd_c8": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "ldmae_groupnorm_stats_nhwc_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "ldmae_groupnorm_apply_nhwc_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ldmae_conv3x3_vae_nhwc_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -126,6 +126,13 @@ template <> struct Vec8<f16> {
   }
 };
 
+// four adjacent channels as floats from an f32 (16 B) or fp16 (8 B) tensor: the LPIPS heads and pool backward read either
+__device__ __forceinline__ float4 load4f(const float* p) { return *(const float4*)p; }
+__device__ __forceinline__ float4 load4f(const f16* p) {
+  const f16x4 v = *(const f16x4*)p;
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+
 // ---------------------------------------------------------------- wave / block reductions (wave = 64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

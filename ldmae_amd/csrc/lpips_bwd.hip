@@ -104,7 +104,8 @@ __device__ __forceinline__ float pool_pick(float v00, float v01, float v10, floa
   return idx == mine ? d : 0.f;
 }
 
-__global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx, int B,
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __restrict__ dy, const T* __restrict__ x, float* __restrict__ dx, int B,
                                                              int H, int W, int C4, int Ho, int Wo) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)B * H * W * C4) return;
@@ -114,8 +115,8 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __rest
   float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
   if (py < 2 * Ho && px < 2 * Wo) {
     const int oy = py >> 1, ox = px >> 1, mine = (py & 1) * 2 + (px & 1);
-    const float4* xw = (const float4*)x + (((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c;
-    const float4 v00 = xw[0], v01 = xw[C4], v10 = xw[(size_t)W * C4], v11 = xw[(size_t)W * C4 + C4];
+    const T* xw = x + ((((size_t)b * H + 2 * oy) * W + 2 * ox) * C4 + c) * 4;
+    const float4 v00 = load4f(xw), v01 = load4f(xw + 4 * C4), v10 = load4f(xw + (size_t)W * C4 * 4), v11 = load4f(xw + ((size_t)W * C4 + C4) * 4);
     const float4 d = ((const float4*)dy)[(((size_t)b * Ho + oy) * Wo + ox) * C4 + c];
     o.x = pool_pick(v00.x, v01.x, v10.x, v11.x, mine, d.x);
     o.y = pool_pick(v00.y, v01.y, v10.y, v11.y, mine, d.y);
@@ -125,16 +126,26 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __rest
   ((float4*)dx)[i] = o;
 }
 
-extern "C" int ldmae_maxpool2x2_bwd_nhwc_f32(const float* dy, const float* x, float* dx, int B, int H, int W, int C, void* stream) {
-  LDMAE_REQUIRE(x && dx && B > 0 && H > 0 && W > 0 && C > 0 && (long)B * H * W * C < (1L << 40), "maxpool2x2_bwd: bad arguments");
-  LDMAE_REQUIRE(C % 4 == 0, "maxpool2x2_bwd: %d channels (a multiple of 4)", C);
+template <typename T>
+static int launch_maxpool2x2_bwd(const char* name, const float* dy, const T* x, float* dx, int B, int H, int W, int C, void* stream) {
+  LDMAE_REQUIRE(x && dx && B > 0 && H > 0 && W > 0 && C > 0 && (long)B * H * W * C < (1L << 40), "%s: bad arguments", name);
+  LDMAE_REQUIRE(C % 4 == 0, "%s: %d channels (a multiple of 4)", name, C);
   const int Ho = H / 2, Wo = W / 2;
-  LDMAE_REQUIRE(dy || Ho == 0 || Wo == 0, "maxpool2x2_bwd: dy is null");     // an image thinner than one window has no dy: dx is all zeros
-  LDMAE_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0, "maxpool2x2_bwd: dy, x and dx must be 16-byte aligned");
+  LDMAE_REQUIRE(dy || Ho == 0 || Wo == 0, "%s: dy is null", name);     // an image thinner than one window has no dy: dx is all zeros
+  LDMAE_REQUIRE(((uintptr_t)dy & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0, "%s: dy, x and dx must be 16-byte aligned", name);
   const long n = (long)B * H * W * (C / 4);
-  hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), dy, x, dx, B, H, W, C / 4, Ho, Wo);
-  LDMAE_CHECK_LAUNCH("maxpool2x2_bwd");
+  hipLaunchKernelGGL(maxpool2x2_bwd_kernel<T>, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), dy, x, dx, B, H, W, C / 4, Ho, Wo);
+  LDMAE_CHECK_LAUNCH(name);
   return 0;
+}
+
+extern "C" int ldmae_maxpool2x2_bwd_nhwc_f32(const float* dy, const float* x, float* dx, int B, int H, int W, int C, void* stream) {
+  return launch_maxpool2x2_bwd("maxpool2x2_bwd", dy, x, dx, B, H, W, C, stream);
+}
+
+// x is the fp16 activation the fp16 VGG path pooled; dy and dx stay f32.  The comparisons are the same (fp16 -> f32 is exact).
+extern "C" int ldmae_maxpool2x2_bwd_nhwc_xf16(const float* dy, const void* x, float* dx, int B, int H, int W, int C, void* stream) {
+  return launch_maxpool2x2_bwd("maxpool2x2_bwd_xf16", dy, (const f16*)x, dx, B, H, W, C, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ LPIPS head backward of one tap
@@ -152,15 +163,15 @@ __device__ __forceinline__ float lane_group_sum_bwd(float v) {
   return v;
 }
 
-template <int C, bool ACC>
-__global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const float* __restrict__ f, const float* __restrict__ lw, const float* __restrict__ gout,
+template <int C, bool ACC, typename T>
+__global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const T* __restrict__ f, const float* __restrict__ lw, const float* __restrict__ gout,
                                                                 float* __restrict__ d0, float* __restrict__ d1, int B, int HW, int chunks) {
 #pragma clang fp contract(off)      // n0 - n1 from two rounded products, as the forward kernel forms it
   constexpr int L = C / 4 < 64 ? C / 4 : 64, V = C / (4 * L), PPB = LB_NT / L;
   const int tid = threadIdx.x, g = tid / L, gl = tid % L;
   const int b = blockIdx.y;
-  const float* f0 = f + (size_t)b * HW * C;
-  const float* f1 = f + (size_t)(B + b) * HW * C;
+  const T* f0 = f + (size_t)b * HW * C;
+  const T* f1 = f + (size_t)(B + b) * HW * C;
   float* o0 = d0 ? d0 + (size_t)b * HW * C : nullptr;
   float* o1 = d1 ? d1 + (size_t)b * HW * C : nullptr;
   const float coef = 2.f * gout[b] / (float)HW;
@@ -172,8 +183,8 @@ __global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const float* __r
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      a[v] = *(const float4*)(f0 + p * C + (v * L + gl) * 4);
-      c[v] = *(const float4*)(f1 + p * C + (v * L + gl) * 4);
+      a[v] = load4f(f0 + p * C + (v * L + gl) * 4);
+      c[v] = load4f(f1 + p * C + (v * L + gl) * 4);
       s0 += a[v].x * a[v].x + a[v].y * a[v].y + a[v].z * a[v].z + a[v].w * a[v].w;
       s1 += c[v].x * c[v].x + c[v].y * c[v].y + c[v].z * c[v].z + c[v].w * c[v].w;
     }
@@ -216,19 +227,20 @@ __global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const float* __r
   }
 }
 
-template <int C>
-static void launch_lpips_layer_bwd(dim3 grid, hipStream_t st, const float* f, const float* lw, const float* g, float* d0, float* d1, int B, int HW,
+template <int C, typename T>
+static void launch_lpips_layer_bwd(dim3 grid, hipStream_t st, const T* f, const float* lw, const float* g, float* d0, float* d1, int B, int HW,
                                    int chunks, int accumulate) {
-  if (accumulate) hipLaunchKernelGGL((lpips_layer_bwd_kernel<C, true>), grid, dim3(LB_NT), 0, st, f, lw, g, d0, d1, B, HW, chunks);
-  else hipLaunchKernelGGL((lpips_layer_bwd_kernel<C, false>), grid, dim3(LB_NT), 0, st, f, lw, g, d0, d1, B, HW, chunks);
+  if (accumulate) hipLaunchKernelGGL((lpips_layer_bwd_kernel<C, true, T>), grid, dim3(LB_NT), 0, st, f, lw, g, d0, d1, B, HW, chunks);
+  else hipLaunchKernelGGL((lpips_layer_bwd_kernel<C, false, T>), grid, dim3(LB_NT), 0, st, f, lw, g, d0, d1, B, HW, chunks);
 }
 
-extern "C" int ldmae_lpips_layer_bwd(const float* f, const float* lin_w, const float* g, float* d_input, float* d_target, int B, int h, int w, int C,
-                                     int accumulate, void* stream) {
-  LDMAE_REQUIRE(f && lin_w && g && (d_input || d_target) && B > 0 && h > 0 && w > 0 && B <= 65535 && (long)h * w < (1L << 31), "lpips_layer_bwd: bad arguments");
-  LDMAE_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, "lpips_layer_bwd: C = %d (64, 128, 256 or 512)", C);
+template <typename T>
+static int lpips_layer_bwd_any(const char* name, const T* f, const float* lin_w, const float* g, float* d_input, float* d_target, int B, int h, int w,
+                               int C, int accumulate, void* stream) {
+  LDMAE_REQUIRE(f && lin_w && g && (d_input || d_target) && B > 0 && h > 0 && w > 0 && B <= 65535 && (long)h * w < (1L << 31), "%s: bad arguments", name);
+  LDMAE_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, "%s: C = %d (64, 128, 256 or 512)", name, C);
   LDMAE_REQUIRE(((uintptr_t)f & 15) == 0 && ((uintptr_t)lin_w & 15) == 0 && ((uintptr_t)d_input & 15) == 0 && ((uintptr_t)d_target & 15) == 0,
-                "lpips_layer_bwd: features, lin weight and gradients must be 16-byte aligned");
+                "%s: features, lin weight and gradients must be 16-byte aligned", name);
   const int HW = h * w, L = C / 4 < 64 ? C / 4 : 64, ppb = LB_NT / L;
   const int chunks = (int)std::min<long>(4096, cdiv(HW, ppb));      // every pixel has one owner: the split only shapes the grid
   const dim3 grid(chunks, B);
@@ -239,17 +251,30 @@ extern "C" int ldmae_lpips_layer_bwd(const float* f, const float* lin_w, const f
     case 256: launch_lpips_layer_bwd<256>(grid, st, f, lin_w, g, d_input, d_target, B, HW, chunks, accumulate); break;
     default: launch_lpips_layer_bwd<512>(grid, st, f, lin_w, g, d_input, d_target, B, HW, chunks, accumulate); break;
   }
-  LDMAE_CHECK_LAUNCH("lpips_layer_bwd");
+  LDMAE_CHECK_LAUNCH(name);
   return 0;
 }
 
+extern "C" int ldmae_lpips_layer_bwd(const float* f, const float* lin_w, const float* g, float* d_input, float* d_target, int B, int h, int w, int C,
+                                     int accumulate, void* stream) {
+  return lpips_layer_bwd_any("lpips_layer_bwd", f, lin_w, g, d_input, d_target, B, h, w, C, accumulate, stream);
+}
+
+// The taps as the fp16 VGG path stores them; gradients stay f32 and every operation after the load is the arithmetic above.
+extern "C" int ldmae_lpips_layer_bwd_f16(const void* f, const float* lin_w, const float* g, float* d_input, float* d_target, int B, int h, int w, int C,
+                                         int accumulate, void* stream) {
+  return lpips_layer_bwd_any("lpips_layer_bwd_f16", (const f16*)f, lin_w, g, d_input, d_target, B, h, w, C, accumulate, stream);
+}
+
 // ------------------------------------------------------------------------------------------------ ScalingLayer backward
-// g NHWC [B, H, W, 4] (the data gradient of conv1_1; channel 3 is the padding channel) -> out NCHW [B, 3, H, W] = g / scale.
+// g NHWC [B, H, W, LD] (the data gradient of conv1_1; channels 3 .. LD - 1 are padding channels, never read past the first float4) -> out NCHW
+// [B, 3, H, W] = g / scale.  LD = 4: the f32 path; LD = 8: the fp16 path, whose conv1_1 takes 8 input channels.
+template <int LD>
 __global__ __launch_bounds__(256) void lpips_prep_bwd_kernel(const float* __restrict__ g, float* __restrict__ out, int B, long HW) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)B * HW) return;
   const long n = i / HW, p = i % HW;
-  const float4 v = *(const float4*)(g + i * 4);
+  const float4 v = *(const float4*)(g + i * LD);
   float* dst = out + n * 3 * HW + p;
   dst[0] = v.x / 0.458f;
   dst[HW] = v.y / 0.448f;
@@ -260,7 +285,16 @@ extern "C" int ldmae_lpips_prep_bwd(const float* g, float* out, int B, int H, in
   LDMAE_REQUIRE(g && out && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 40), "lpips_prep_bwd: bad arguments");
   LDMAE_REQUIRE(((uintptr_t)g & 15) == 0, "lpips_prep_bwd: g must be 16-byte aligned");
   const long HW = (long)H * W;
-  hipLaunchKernelGGL(lpips_prep_bwd_kernel, dim3(cdiv((long)B * HW, 256)), dim3(256), 0, as_stream(stream), g, out, B, HW);
+  hipLaunchKernelGGL(lpips_prep_bwd_kernel<4>, dim3(cdiv((long)B * HW, 256)), dim3(256), 0, as_stream(stream), g, out, B, HW);
   LDMAE_CHECK_LAUNCH("lpips_prep_bwd");
+  return 0;
+}
+
+extern "C" int ldmae_lpips_prep_bwd_c8(const float* g, float* out, int B, int H, int W, void* stream) {
+  LDMAE_REQUIRE(g && out && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 40), "lpips_prep_bwd_c8: bad arguments");
+  LDMAE_REQUIRE(((uintptr_t)g & 15) == 0, "lpips_prep_bwd_c8: g must be 16-byte aligned");
+  const long HW = (long)H * W;
+  hipLaunchKernelGGL(lpips_prep_bwd_kernel<8>, dim3(cdiv((long)B * HW, 256)), dim3(256), 0, as_stream(stream), g, out, B, HW);
+  LDMAE_CHECK_LAUNCH("lpips_prep_bwd_c8");
   return 0;
 }

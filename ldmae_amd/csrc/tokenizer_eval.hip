@@ -23,6 +23,30 @@ __global__ __launch_bounds__(256) void lpips_prep_kernel(const float* __restrict
   *(float4*)(out + i * 4) = v;
 }
 
+// The same f32 arithmetic, then ONE rounding to fp16 (round to nearest even, saturating at +-65504), 8 channels per pixel (3 real, 5 zero): the
+// Cin % 8 == 0 operand of the fp16 VGG path (lpips_f16.hip).  One thread per pixel, one 16-B store.
+__global__ __launch_bounds__(256) void lpips_prep_f16_kernel(const float* __restrict__ in0, const float* __restrict__ in1, f16* __restrict__ out, int B,
+                                                             long HW) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2L * B * HW) return;
+  const long n = i / HW, p = i % HW;
+  const float* src = (n < B ? in0 + n * 3 * HW : in1 + (n - B) * 3 * HW) + p;
+  f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+  v[0] = (f16)sat_f16((src[0] - (-0.030f)) / 0.458f, 65504.f);
+  v[1] = (f16)sat_f16((src[HW] - (-0.088f)) / 0.448f, 65504.f);
+  v[2] = (f16)sat_f16((src[2 * HW] - (-0.188f)) / 0.450f, 65504.f);
+  *(f16x8*)(out + i * 8) = v;
+}
+
+extern "C" int ldmae_lpips_prep_f16(const float* input, const float* target, void* out, int B, int H, int W, void* stream) {
+  LDMAE_REQUIRE(input && target && out && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 40), "lpips_prep_f16: bad arguments");
+  LDMAE_REQUIRE(((uintptr_t)out & 15) == 0, "lpips_prep_f16: out must be 16-byte aligned");
+  const long HW = (long)H * W;
+  hipLaunchKernelGGL(lpips_prep_f16_kernel, dim3(cdiv(2L * B * HW, 256)), dim3(256), 0, as_stream(stream), input, target, (f16*)out, B, HW);
+  LDMAE_CHECK_LAUNCH("lpips_prep_f16");
+  return 0;
+}
+
 extern "C" int ldmae_lpips_prep(const float* input, const float* target, float* out, int B, int H, int W, void* stream) {
   LDMAE_REQUIRE(input && target && out && B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 40), "lpips_prep: bad arguments");
   LDMAE_REQUIRE(((uintptr_t)out & 15) == 0, "lpips_prep: out must be 16-byte aligned");
@@ -46,16 +70,16 @@ __device__ __forceinline__ float lane_group_sum(float v) {
   return v;
 }
 
-template <int C>
-__global__ __launch_bounds__(LP_NT) void lpips_layer_kernel(const float* __restrict__ f, const float* __restrict__ lw, float* __restrict__ part,
+template <int C, typename T>
+__global__ __launch_bounds__(LP_NT) void lpips_layer_kernel(const T* __restrict__ f, const float* __restrict__ lw, float* __restrict__ part,
                                                             int B, int HW, int chunks) {
 #pragma clang fp contract(off)      // a * r0 - c * r1 with both products rounded: equal halves give exactly 0, not the residual of an fma
   constexpr int L = C / 4 < 64 ? C / 4 : 64, V = C / (4 * L), PPB = LP_NT / L;      // lanes per pixel, float4 per lane, pixels per pass
   __shared__ float red[LP_NT / 64];
   const int tid = threadIdx.x, g = tid / L, gl = tid % L;
   const int b = blockIdx.y;
-  const float* f0 = f + (size_t)b * HW * C;
-  const float* f1 = f + (size_t)(B + b) * HW * C;
+  const T* f0 = f + (size_t)b * HW * C;
+  const T* f1 = f + (size_t)(B + b) * HW * C;
   float4 w[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) w[v] = *(const float4*)(lw + (v * L + gl) * 4);
@@ -65,8 +89,8 @@ __global__ __launch_bounds__(LP_NT) void lpips_layer_kernel(const float* __restr
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-      a[v] = *(const float4*)(f0 + p * C + (v * L + gl) * 4);
-      c[v] = *(const float4*)(f1 + p * C + (v * L + gl) * 4);
+      a[v] = load4f(f0 + p * C + (v * L + gl) * 4);
+      c[v] = load4f(f1 + p * C + (v * L + gl) * 4);
       s0 += a[v].x * a[v].x + a[v].y * a[v].y + a[v].z * a[v].z + a[v].w * a[v].w;
       s1 += c[v].x * c[v].x + c[v].y * c[v].y + c[v].z * c[v].z + c[v].w * c[v].w;
     }
@@ -108,22 +132,32 @@ static int lpips_chunks(long HW) { return (int)std::min<long>(LP_MAX_CHUNKS, std
 
 extern "C" long ldmae_lpips_workspace_bytes(int B, int h, int w) { return (long)B * lpips_chunks((long)h * w) * (long)sizeof(float); }
 
-extern "C" int ldmae_lpips_layer(const float* f, const float* lin_w, float* out, int B, int h, int w, int C, void* workspace, void* stream) {
-  LDMAE_REQUIRE(f && lin_w && out && workspace && B > 0 && h > 0 && w > 0 && B <= 65535 && (long)h * w < (1L << 31), "lpips_layer: bad arguments");
-  LDMAE_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, "lpips_layer: C = %d (64, 128, 256 or 512)", C);
-  LDMAE_REQUIRE(((uintptr_t)f & 15) == 0 && ((uintptr_t)lin_w & 15) == 0, "lpips_layer: features and lin weight must be 16-byte aligned");
+template <typename T>
+static int launch_lpips_layer(const char* name, const T* f, const float* lin_w, float* out, int B, int h, int w, int C, void* workspace, void* stream) {
+  LDMAE_REQUIRE(f && lin_w && out && workspace && B > 0 && h > 0 && w > 0 && B <= 65535 && (long)h * w < (1L << 31), "%s: bad arguments", name);
+  LDMAE_REQUIRE(C == 64 || C == 128 || C == 256 || C == 512, "%s: C = %d (64, 128, 256 or 512)", name, C);
+  LDMAE_REQUIRE(((uintptr_t)f & 15) == 0 && ((uintptr_t)lin_w & 15) == 0, "%s: features and lin weight must be 16-byte aligned", name);
   const int HW = h * w, chunks = lpips_chunks(HW);
   float* part = (float*)workspace;
   const dim3 grid(chunks, B);
   switch (C) {
-    case 64: hipLaunchKernelGGL(lpips_layer_kernel<64>, grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
-    case 128: hipLaunchKernelGGL(lpips_layer_kernel<128>, grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
-    case 256: hipLaunchKernelGGL(lpips_layer_kernel<256>, grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
-    default: hipLaunchKernelGGL(lpips_layer_kernel<512>, grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
+    case 64: hipLaunchKernelGGL((lpips_layer_kernel<64, T>), grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
+    case 128: hipLaunchKernelGGL((lpips_layer_kernel<128, T>), grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
+    case 256: hipLaunchKernelGGL((lpips_layer_kernel<256, T>), grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
+    default: hipLaunchKernelGGL((lpips_layer_kernel<512, T>), grid, dim3(LP_NT), 0, as_stream(stream), f, lin_w, part, B, HW, chunks); break;
   }
   hipLaunchKernelGGL(lpips_finish_kernel, dim3(cdiv(B, 64)), dim3(64), 0, as_stream(stream), part, out, B, HW, chunks);
-  LDMAE_CHECK_LAUNCH("lpips_layer");
+  LDMAE_CHECK_LAUNCH(name);
   return 0;
+}
+
+extern "C" int ldmae_lpips_layer(const float* f, const float* lin_w, float* out, int B, int h, int w, int C, void* workspace, void* stream) {
+  return launch_lpips_layer("lpips_layer", f, lin_w, out, B, h, w, C, workspace, stream);
+}
+
+// The taps as the fp16 VGG path stores them; every operation after the load is the f32 arithmetic above (fp16 -> f32 is exact).
+extern "C" int ldmae_lpips_layer_f16(const void* f, const float* lin_w, float* out, int B, int h, int w, int C, void* workspace, void* stream) {
+  return launch_lpips_layer("lpips_layer_f16", (const f16*)f, lin_w, out, B, h, w, C, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ SSIM (torchmetrics 1.x defaults)

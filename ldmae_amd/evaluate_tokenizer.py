@@ -155,6 +155,9 @@ def build_parser():
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--lpips_vgg", type=str, default=None, help="torchvision vgg16-397923af.pth (default: $LDMAE_LPIPS_VGG, torch.hub)")
     ap.add_argument("--lpips_lin", type=str, default=None, help="taming's LPIPS vgg.pth (default: $LDMAE_LPIPS_LIN, the reference's path)")
+    ap.add_argument("--lpips_precision", default=None, choices=["f32", "fp16"],
+                    help="arithmetic of the LPIPS network: f32 (default, exact) or fp16 (fp16 VGG, f32 accumulation; models/lpips.py).  When given, "
+                         "the JSON line names it")
     ap.add_argument("--fid_weights", type=str, default=None, help="pt_inception-2015-12-05-6726825d.pth (default: $LDMAE_FID_WEIGHTS, torch.hub)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--synthetic", type=int, default=0, help="N seeded random images instead of an image folder")
@@ -189,7 +192,8 @@ def evaluate_tokenizer(args, cfg, log=print_with_prefix):
     torch.cuda.set_device(device)
     log(f"Loading model... {model_type.upper()} {args.epsilon}", rank=rank)
     # weights first: a missing file fails before any image is written
-    lpips = LPIPS(args.lpips_vgg, args.lpips_lin, device=device)
+    lpips_precision = getattr(args, "lpips_precision", None)
+    lpips = LPIPS(args.lpips_vgg, args.lpips_lin, device=device, precision=lpips_precision or "f32")
     if args.fid_weights:
         os.environ[fid.WEIGHTS_ENV] = args.fid_weights
     fid.resolve_weights()
@@ -215,7 +219,8 @@ def evaluate_tokenizer(args, cfg, log=print_with_prefix):
 
     dataset = SyntheticImages(args.synthetic) if args.synthetic else _image_folder(args.data_path)
     res, save_dir, ref_path = reconstruct_and_score(args, model_type, lambda images: model.encode(images).latent_dist.mode(),
-                                                    lambda latents: model.decode(latents).sample, dataset, latent_std, lpips, device, rank, world, log)
+                                                    lambda latents: model.decode(latents).sample, dataset, latent_std, lpips, device, rank, world, log,
+                                                    extra={"lpips_precision": lpips_precision} if lpips_precision else None)
     if distributed:
         dist.destroy_process_group()
     return res, save_dir, ref_path

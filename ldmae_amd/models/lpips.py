@@ -17,6 +17,16 @@ Nothing is copied to keep them: when one half requires grad every layer runs as 
 One deliberate difference from torch: at a pixel whose channels are all zero in a half, that half's gradient is exactly 0 (torch: NaN, from sqrt's
 backward at 0).  The value is bitwise the forward-only value.
 
+precision="fp16" (opt-in; the default "f32" is the exact-f32 path above, unchanged) runs the VGG in 16 bits, the reference's autocast arithmetic
+without its GradScaler (csrc/lpips_f16.hip).  Forward: every conv operand fp16 (round to nearest even, saturating at +-65504), products exact in f32
+and accumulated in f32 on the fp16 MFMA, bias and ReLU in f32, ONE rounding to fp16 at the store; activations live in memory as fp16 (half the kept
+bytes: 35 MB per 256 x 256 image), the pool runs on fp16 (exact), the heads read fp16 taps and compute in f32.  The ScalingLayer'd image has 8
+channels (3 real, 5 zero) and conv1_1 a weight zero-padded to Cin 8, so all 13 convolutions are one kernel.  Backward: gradients stay f32 in memory;
+the data gradient rounds dy * [y > 0] (at the fetch) and w_rot (once per object) to bf16 and accumulates in f32 on the bf16 MFMA -- bf16 because the
+gradient scales as 1 / (h w) and is below fp16's smallest normal already at 33 x 47; the mask is y > 0 on the stored fp16 activation.  The launch
+structure, the "one half requires grad" rule, the bitwise value and the all-zero-pixel rule are those of the f32 path.  The precision is an argument,
+never inferred from torch.backends or autocast state.
+
 Weights are the user's files, never downloaded:
   - torchvision's vgg16-397923af.pth (keys features.{0,2,5,...,28}.weight|bias): the `vgg_weights` argument, then $LDMAE_LPIPS_VGG, then
     torch.hub's checkpoints/ directory;
@@ -155,6 +165,47 @@ def conv_weights(sd):
     return out
 
 
+PRECISIONS = ("f32", "fp16")
+
+
+def check_precision(precision):
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"LPIPS precision {precision!r}: one of {PRECISIONS}")
+    return precision
+
+
+def conv_weights_c8(sd):
+    """conv_weights with conv1_1's weight zero-padded from Cin 3 to 8 (f32): the shapes of the fp16 path, matching lpips_prep_f16's 8 channels."""
+    return [(torch.nn.functional.pad(w, (0, 4)).contiguous() if w.shape[3] == 4 else w, b, s) for w, b, s in conv_weights(sd)]
+
+
+def conv_weights_f16(sd):
+    """[(weight [Cout, 3, 3, Cin'] fp16, bias [Cout] f32, slice)]: conv_weights_c8 with each weight rounded once to fp16 (round to nearest even; VGG
+    weights are far inside fp16's range)."""
+    return [(w.half().contiguous(), b, s) for w, b, s in conv_weights_c8(sd)]
+
+
+def rotate_weight_bf16(w):
+    """rotate_weight of the f32 channels-last forward weight, rounded once to bf16: the data gradient's weight of the fp16 path."""
+    return rotate_weight(w.float()).to(torch.bfloat16).contiguous()
+
+
+class _Family:
+    """The kernels of one precision under one set of names: _run and _LPIPSFn are written once over them."""
+
+    def __init__(self, ops, precision):
+        f32 = precision == "f32"
+        self.act_dtype = torch.float32 if f32 else torch.float16
+        self.prep = ops.lpips_prep if f32 else ops.lpips_prep_f16
+        self.conv = (lambda x, w, b, out=None: ops.conv2d_nhwc(x, w, b, (1, 1), (1, 1), True, out=out)) if f32 else ops.conv3x3_relu_nhwc_f16
+        self.pool = (lambda x: ops.pool2d_nhwc(x, "max", k=2, stride=2, pad=0)) if f32 else ops.maxpool2x2_nhwc_f16
+        self.head = ops.lpips_layer if f32 else ops.lpips_layer_f16
+        self.dgrad = ops.conv3x3_relu_dgrad_nhwc if f32 else ops.conv3x3_relu_dgrad_nhwc_bf16
+        self.pool_bwd = ops.maxpool2x2_bwd_nhwc if f32 else ops.maxpool2x2_bwd_nhwc_xf16
+        self.head_bwd = ops.lpips_layer_bwd if f32 else ops.lpips_layer_bwd_f16
+        self.prep_bwd = ops.lpips_prep_bwd if f32 else ops.lpips_prep_bwd_c8
+
+
 def conv_flops_per_image(H, W):
     """2 x multiply-adds of the 13 VGG convolutions for ONE image at H x W (a pair runs two): 2 x 15.35 GMAC = 30.7 GFLOP at 224^2,
     40.1 GFLOP at 256^2 (the real Cin 3 of conv1_1, not the padded 4)."""
@@ -193,7 +244,7 @@ class _LPIPSFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        mod, ops = ctx.mod, ctx.mod._ops
+        mod, k_ = ctx.mod, ctx.mod._k
         saved = list(ctx.saved_tensors)
         taps, rest = saved[:len(CHANNELS)], saved[len(CHANNELS):]
         B = taps[0].shape[0] // 2
@@ -210,36 +261,43 @@ class _LPIPSFn(torch.autograd.Function):
                 if _last_of_slice(i):
                     y = taps[k][half * B:(half + 1) * B]
                     # gradient of tap k: the following pool's backward writes the buffer, the head backward adds to it (fixed order)
-                    buf = ops.maxpool2x2_bwd_nhwc(d, y) if d is not None else torch.empty_like(y)
-                    ops.lpips_layer_bwd(taps[k], mod.lins[k], g, d_input=buf if half == 0 else None, d_target=buf if half == 1 else None,
-                                        accumulate=d is not None)
+                    buf = k_.pool_bwd(d, y) if d is not None else torch.empty(y.shape, dtype=torch.float32, device=y.device)
+                    k_.head_bwd(taps[k], mod.lins[k], g, d_input=buf if half == 0 else None, d_target=buf if half == 1 else None,
+                                accumulate=d is not None)
                     d = buf
                 else:
                     y = inner.pop()
-                d = ops.conv3x3_relu_dgrad_nhwc(d, y, mod.wrot[i])
-            grads[half] = ops.lpips_prep_bwd(d).to(ctx.devices[half], ctx.dtypes[half])
+                d = k_.dgrad(d, y, mod.wrot[i])
+            grads[half] = k_.prep_bwd(d).to(ctx.devices[half], ctx.dtypes[half])
         return None, grads[0], grads[1]
 
 
 class LPIPS:
     """forward(input, target): NCHW f32 [B, 3, H, W] in [-1, 1] -> f32 [B, 1, 1, 1], as the reference's LPIPS().eval().  Forward only unless built with
-    differentiable=True (then a torch.autograd.Function with the same value, bit for bit; activation memory: module docstring)."""
+    differentiable=True (then a torch.autograd.Function with the same value, bit for bit; activation memory: module docstring).
+    precision "f32" (default: the exact-f32 path) or "fp16" (fp16 VGG forward, bf16 data gradient: module docstring); anything else is a ValueError."""
 
     differentiable = False
+    precision = "f32"
 
-    def __init__(self, vgg_weights=None, lin_weights=None, state_dict=None, device="cuda", differentiable=False):
+    def __init__(self, vgg_weights=None, lin_weights=None, state_dict=None, device="cuda", differentiable=False, precision="f32"):
+        self.precision = check_precision(precision)
         from .. import ops
         self._ops = ops
+        self._k = _Family(ops, self.precision)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError(f"LPIPS runs on a HIP device (no CPU fallback); got {device}")
         if state_dict is None:
             state_dict = load_state_dict_from_files(vgg_weights, lin_weights)
-        self.convs = [(w.to(self.device), b.to(self.device), s) for w, b, s in conv_weights(state_dict)]
+        packs = conv_weights(state_dict) if self.precision == "f32" else conv_weights_f16(state_dict)
+        self.convs = [(w.to(self.device), b.to(self.device), s) for w, b, s in packs]
         self.lins = [state_dict[f"lin{k}.model.1.weight"].float().reshape(-1).contiguous().to(self.device) for k in range(len(CHANNELS))]
         if differentiable:
             self.differentiable = True
-            self.wrot = [rotate_weight(w) for w, _, _ in self.convs]          # once per object; conv1_1's padded 4th row is zero
+            # once per object; conv1_1's padded rows are zero.  fp16 path: the f32 weight rounded once to bf16 (not through fp16)
+            self.wrot = ([rotate_weight(w) for w, _, _ in self.convs] if self.precision == "f32" else
+                         [rotate_weight_bf16(w).to(self.device) for w, _, _ in conv_weights_c8(state_dict)])
 
     def to(self, device):
         if torch.device(device) != self.device:
@@ -259,8 +317,8 @@ class LPIPS:
         x = input.detach().to(self.device, torch.float32).contiguous()
         y = target.detach().to(self.device, torch.float32).contiguous()
         B = x.shape[0]
-        ops = self._ops
-        h = ops.lpips_prep(x, y)
+        k_ = self._k
+        h = k_.prep(x, y)
         out = torch.zeros(B, dtype=torch.float32, device=self.device)
         taps, acts = [], [[] if k else None for k in keep]
         # ONE half kept: each layer runs as two launches of B images, so the kept half's outputs are tensors of their own (kept without a copy)
@@ -271,20 +329,20 @@ class LPIPS:
         prev = 1
         for i, (w, b, s) in enumerate(self.convs):
             if s != prev:                              # end of slice prev: its last ReLU output is tap prev - 1; then the 2x2 / 2 max pool
-                ops.lpips_layer(h, self.lins[prev - 1], out)
+                k_.head(h, self.lins[prev - 1], out)
                 taps.append(h)
-                hs = [ops.pool2d_nhwc(t, "max", k=2, stride=2, pad=0) for t in hs]
+                hs = [k_.pool(t) for t in hs]
                 prev = s
             if split and _last_of_slice(i):            # a tap: both halves into one tensor
-                h = torch.empty(2 * B, hs[0].shape[1], hs[0].shape[2], w.shape[0], dtype=torch.float32, device=self.device)
-                hs = [ops.conv2d_nhwc(t, w, b, (1, 1), (1, 1), True, out=h[j * B:(j + 1) * B]) for j, t in enumerate(hs)]
+                h = torch.empty(2 * B, hs[0].shape[1], hs[0].shape[2], w.shape[0], dtype=k_.act_dtype, device=self.device)
+                hs = [k_.conv(t, w, b, out=h[j * B:(j + 1) * B]) for j, t in enumerate(hs)]
             else:
-                hs = [ops.conv2d_nhwc(t, w, b, (1, 1), (1, 1), True) for t in hs]
+                hs = [k_.conv(t, w, b) for t in hs]
                 h = hs[0]                              # (read only where it is the whole batch: not split)
             for half, a in enumerate(acts):
                 if a is not None:
                     a.append(None if _last_of_slice(i) else (hs[half] if split else h[half * B:(half + 1) * B]))
-        ops.lpips_layer(h, self.lins[prev - 1], out)
+        k_.head(h, self.lins[prev - 1], out)
         taps.append(h)
         return out.view(-1, 1, 1, 1), taps, acts
 

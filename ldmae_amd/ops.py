@@ -1282,6 +1282,158 @@ def lpips_prep_bwd(g):
     return out
 
 
+# ----------------------------------------------------------------------------- LPIPS in 16 bits (csrc/lpips_f16.hip): fp16 forward, bf16 data gradient
+def _nhwc_t(t, what, dtype):
+    if t.dtype != dtype or t.dim() != 4 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: need a contiguous {str(dtype)[6:]} NHWC tensor, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _aligned16(t, what):
+    if t.data_ptr() % 16:
+        raise RuntimeError(f"{what}: the tensor's storage must be 16-byte aligned")
+
+
+def lpips_prep_f16(input, target):
+    """lpips_prep's f32 arithmetic, then one rounding: NCHW f32 [B, 3, H, W] x 2 -> NHWC fp16 [2B, H, W, 8], input first, channels 3 .. 7 zero
+    (the Cin % 8 == 0 operand of conv3x3_relu_nhwc_f16)."""
+    _nchw(input, "lpips_prep_f16 input", 3)
+    _nchw(target, "lpips_prep_f16 target", 3)
+    _same(input, target, "lpips_prep_f16")
+    B, _, H, W = input.shape
+    out = torch.empty(2 * B, H, W, 8, dtype=torch.float16, device=input.device)
+    call("ldmae_lpips_prep_f16", ptr(input), ptr(target), ptr(out), B, H, W, stream())
+    return out
+
+
+def conv3x3_relu_nhwc_f16(x, w, bias=None, out=None):
+    """relu(conv3x3(x, w) + bias), stride 1, pad 1, on the fp16 MFMA with f32 accumulation: x fp16 [B, H, W, Cin] (Cin % 8 == 0), w fp16
+    [Cout, 3, 3, Cin], bias f32 [Cout]; the f32 result is rounded once to fp16 (saturating at +-65504) into out [B, H, W, Cout] (a contiguous
+    view of a larger tensor is taken as it is; allocated when None)."""
+    _nhwc_t(x, "conv3x3_relu_nhwc_f16 x", torch.float16)
+    B, H, W, Cin = x.shape
+    if w.dtype != torch.float16 or w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, Cin) or not w.is_contiguous() or w.device != x.device:
+        raise RuntimeError(f"conv3x3_relu_nhwc_f16: weight {tuple(w.shape)} {w.dtype} on {w.device} is not a contiguous fp16 [Cout, 3, 3, {Cin}] "
+                           f"tensor on {x.device}")
+    if Cin % 8 or x.numel() == 0:
+        raise RuntimeError(f"conv3x3_relu_nhwc_f16: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 8 channels")
+    Cout = w.shape[0]
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous() or bias.device != x.device):
+        raise RuntimeError(f"conv3x3_relu_nhwc_f16: bias must be a contiguous f32 [{Cout}] tensor on {x.device}, got {tuple(bias.shape)} {bias.dtype}")
+    if out is None:
+        out = torch.empty(B, H, W, Cout, dtype=torch.float16, device=x.device)
+    _nhwc_t(out, "conv3x3_relu_nhwc_f16 out", torch.float16)
+    if tuple(out.shape) != (B, H, W, Cout) or out.device != x.device:
+        raise RuntimeError(f"conv3x3_relu_nhwc_f16: out {tuple(out.shape)} on {out.device} is not [{B}, {H}, {W}, {Cout}] on {x.device}")
+    _aligned16(x, "conv3x3_relu_nhwc_f16 x")
+    _aligned16(w, "conv3x3_relu_nhwc_f16 w")
+    call("ldmae_conv3x3_relu_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), B, H, W, Cin, Cout, stream())
+    return out
+
+
+def maxpool2x2_nhwc_f16(x):
+    """2x2 / 2 max pool of fp16 NHWC [B, H, W, C] (C % 8 == 0, H, W >= 2) -> [B, H // 2, W // 2, C]; the odd last row / column is dropped."""
+    _nhwc_t(x, "maxpool2x2_nhwc_f16", torch.float16)
+    B, H, W, C = x.shape
+    if C % 8 or B == 0 or H < 2 or W < 2:
+        raise RuntimeError(f"maxpool2x2_nhwc_f16: x {tuple(x.shape)}: need at least 2 x 2 pixels and a multiple of 8 channels")
+    _aligned16(x, "maxpool2x2_nhwc_f16 x")
+    out = torch.empty(B, H // 2, W // 2, C, dtype=torch.float16, device=x.device)
+    call("ldmae_maxpool2x2_nhwc_f16", ptr(x), ptr(out), B, H, W, C, stream())
+    return out
+
+
+def lpips_layer_f16(f, lin_w, out):
+    """lpips_layer on fp16 taps f [2B, h, w, C]: the same f32 arithmetic on the (exactly converted) values; out f32 [B] accumulated in place."""
+    _nhwc_t(f, "lpips_layer_f16", torch.float16)
+    n, h, w, C = f.shape
+    if n % 2 or C not in (64, 128, 256, 512):
+        raise RuntimeError(f"lpips_layer_f16: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
+    B = n // 2
+    lin_w = _arg(lin_w, "lpips_layer_f16 lin_w", torch.float32, numel=C)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous() or lin_w.device != f.device or out.device != f.device:
+        raise RuntimeError(f"lpips_layer_f16: out must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(out.shape)} {out.dtype}")
+    _aligned16(f, "lpips_layer_f16 f")
+    ws = workspace(L.load().ldmae_lpips_workspace_bytes(B, h, w), f.device, "lpips")
+    call("ldmae_lpips_layer_f16", ptr(f), ptr(lin_w), ptr(out), B, h, w, C, ptr(ws), stream())
+    return out
+
+
+def conv3x3_relu_dgrad_nhwc_bf16(dy, y, w_rot, out=None):
+    """conv3x3_relu_dgrad_nhwc with 16-bit operands: dy f32 [B, H, W, Cy] (Cy % 8 == 0), y the stored fp16 activation of the same shape, w_rot bf16
+    [Cx, 3, 3, Cy]; dx f32 [B, H, W, Cx] = conv3x3(bf16(dy * [y > 0]), w_rot), f32 accumulation on the bf16 MFMA."""
+    _nhwc(dy, "conv3x3_relu_dgrad_nhwc_bf16 dy")
+    _nhwc_t(y, "conv3x3_relu_dgrad_nhwc_bf16 y", torch.float16)
+    _same(dy, y, "conv3x3_relu_dgrad_nhwc_bf16")
+    B, H, W, Cy = dy.shape
+    if w_rot.dtype != torch.bfloat16 or w_rot.dim() != 4 or tuple(w_rot.shape[1:]) != (3, 3, Cy) or not w_rot.is_contiguous() or w_rot.device != dy.device:
+        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc_bf16: rotated weight {tuple(w_rot.shape)} {w_rot.dtype} on {w_rot.device} is not a contiguous "
+                           f"bf16 [Cx, 3, 3, {Cy}] tensor on {dy.device}")
+    if Cy % 8 or dy.numel() == 0:
+        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc_bf16: {Cy} gradient channels (a multiple of 8) of a non-empty tensor")
+    Cx = w_rot.shape[0]
+    if out is None:
+        out = torch.empty(B, H, W, Cx, dtype=torch.float32, device=dy.device)
+    _nhwc(out, "conv3x3_relu_dgrad_nhwc_bf16 out")
+    if tuple(out.shape) != (B, H, W, Cx) or out.device != dy.device:
+        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc_bf16: out {tuple(out.shape)} on {out.device} is not [{B}, {H}, {W}, {Cx}] on {dy.device}")
+    for t, what in ((dy, "dy"), (y, "y"), (w_rot, "w_rot")):
+        _aligned16(t, f"conv3x3_relu_dgrad_nhwc_bf16 {what}")
+    call("ldmae_conv3x3_relu_dgrad_nhwc_bf16", ptr(dy), ptr(y), ptr(w_rot), ptr(out), B, H, W, Cy, Cx, stream())
+    return out
+
+
+def maxpool2x2_bwd_nhwc_xf16(dy, x, out=None):
+    """maxpool2x2_bwd_nhwc with the pooled input x stored as fp16; dy and dx f32."""
+    _nhwc_t(x, "maxpool2x2_bwd_nhwc_xf16 x", torch.float16)
+    _nhwc(dy, "maxpool2x2_bwd_nhwc_xf16 dy")
+    B, H, W, C = x.shape
+    if tuple(dy.shape) != (B, H // 2, W // 2, C) or dy.device != x.device:
+        raise RuntimeError(f"maxpool2x2_bwd_nhwc_xf16: dy {tuple(dy.shape)} on {dy.device} is not [{B}, {H // 2}, {W // 2}, {C}] on {x.device}")
+    if C % 4 or x.numel() == 0:
+        raise RuntimeError(f"maxpool2x2_bwd_nhwc_xf16: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 4 channels")
+    if out is None:
+        out = torch.empty(B, H, W, C, dtype=torch.float32, device=x.device)
+    _nhwc(out, "maxpool2x2_bwd_nhwc_xf16 out")
+    if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
+        raise RuntimeError(f"maxpool2x2_bwd_nhwc_xf16: out {tuple(out.shape)} on {out.device} does not match x {tuple(x.shape)} on {x.device}")
+    _aligned16(x, "maxpool2x2_bwd_nhwc_xf16 x")
+    call("ldmae_maxpool2x2_bwd_nhwc_xf16", ptr(dy) if dy.numel() else None, ptr(x), ptr(out), B, H, W, C, stream())
+    return out
+
+
+def lpips_layer_bwd_f16(f, lin_w, g, d_input=None, d_target=None, accumulate=False):
+    """lpips_layer_bwd on fp16 taps f [2B, h, w, C]; g, d_input, d_target f32, the same arithmetic.  -> (d_input, d_target)."""
+    _nhwc_t(f, "lpips_layer_bwd_f16", torch.float16)
+    n, h, w, C = f.shape
+    if n % 2 or C not in (64, 128, 256, 512):
+        raise RuntimeError(f"lpips_layer_bwd_f16: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
+    B = n // 2
+    lin_w = _arg(lin_w, "lpips_layer_bwd_f16 lin_w", torch.float32, numel=C)
+    if g.dtype != torch.float32 or tuple(g.shape) != (B,) or not g.is_contiguous() or g.device != f.device or lin_w.device != f.device:
+        raise RuntimeError(f"lpips_layer_bwd_f16: g must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(g.shape)} {g.dtype} on {g.device}")
+    if d_input is None and d_target is None:
+        raise RuntimeError("lpips_layer_bwd_f16: neither d_input nor d_target given: nothing to compute")
+    for d, what in ((d_input, "d_input"), (d_target, "d_target")):
+        if d is not None and (d.dtype != torch.float32 or tuple(d.shape) != (B, h, w, C) or not d.is_contiguous() or d.device != f.device):
+            raise RuntimeError(f"lpips_layer_bwd_f16: {what} must be a contiguous f32 [{B}, {h}, {w}, {C}] tensor on {f.device}, got {tuple(d.shape)} {d.dtype}")
+    _aligned16(f, "lpips_layer_bwd_f16 f")
+    call("ldmae_lpips_layer_bwd_f16", ptr(f), ptr(lin_w), ptr(g), ptr(d_input), ptr(d_target), B, h, w, C, 1 if accumulate else 0, stream())
+    return d_input, d_target
+
+
+def lpips_prep_bwd_c8(g):
+    """lpips_prep_bwd from the 8-channel data gradient of the fp16 path's conv1_1: g NHWC f32 [B, H, W, 8] -> NCHW f32 [B, 3, H, W] = g[..., c] /
+    scale[c]; channels 3 .. 7 (exactly zero: their weight rows are) are ignored."""
+    _nhwc(g, "lpips_prep_bwd_c8")
+    B, H, W, C = g.shape
+    if C != 8:
+        raise RuntimeError(f"lpips_prep_bwd_c8: gradient {tuple(g.shape)}: need [B, H, W, 8]")
+    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=g.device)
+    call("ldmae_lpips_prep_bwd_c8", ptr(g), ptr(out), B, H, W, stream())
+    return out
+
+
 def ssim(preds, target, lo=-1.0, hi=1.0, data_range=2.0):
     """Per-image SSIM f32 [B] of NCHW f32 [B, C, H, W] (H, W >= 11): torchmetrics' default Gaussian SSIM of the inputs clamped to [lo, hi]
     (+-inf: no clamp) with c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2."""

@@ -29,5 +29,7 @@ stage3=(--no_cls --tune_decoder --perceptual_loss_ratio 10.0 --batch_size 16 --a
         --precision fp16 --data_path "$DATA_PATH" --output_dir "$OUT3" --log_dir "$OUT3" --resume "$OUT/checkpoint-90.pth")
 [ -n "$LPIPS_VGG" ] && stage3+=(--lpips_vgg "$LPIPS_VGG")
 [ -n "$LPIPS_LIN" ] && stage3+=(--lpips_lin "$LPIPS_LIN")
+# LPIPS_PRECISION=fp16: the VGG in 16 bits (fp16 forward, bf16 data gradient; models/lpips.py); default f32 = exact
+stage3+=(--lpips_precision "${LPIPS_PRECISION:-f32}")
 echo "Stage 3: decoder tuning (256 x 256, LPIPS ratio 10.0)"
 python -m torch.distributed.run --nproc-per-node "$GPUS_PER_NODE" --nnodes 1 --node-rank 0 --master-addr 127.0.0.1 vmae_pretrain.py "${stage3[@]}" "$@" || exit 1

@@ -369,7 +369,8 @@ def set_for_tuning_decoder(args, model, log=print):
     return frozen
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line, with every refusal that needs no GPU (exit code 2): -> args (args.stage3: the decoder tuning is selected)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="mae_for_ldmae_f8d16_prev")
     ap.add_argument("--input_size", type=int, default=256)
@@ -410,6 +411,9 @@ def main(argv=None):
     ap.add_argument("--tune_decoder", action="store_true", help="stage 3 of train_ae.sh (decoder tuning with LPIPS); only together with --perceptual_loss_ratio, refused alone")
     ap.add_argument("--lpips_vgg", type=str, default=None, help="stage 3: torchvision vgg16-397923af.pth (default: $LDMAE_LPIPS_VGG, torch.hub)")
     ap.add_argument("--lpips_lin", type=str, default=None, help="stage 3: taming's LPIPS vgg.pth (default: $LDMAE_LPIPS_LIN, the reference's path)")
+    ap.add_argument("--lpips_precision", default=None, choices=["f32", "fp16"],
+                    help="stage 3 only (refused otherwise): arithmetic of the LPIPS network; f32 (default) = exact f32, fp16 = fp16 VGG forward with f32 "
+                         "accumulation and a bf16 data gradient (models/lpips.py)")
     ap.add_argument("--pred_with_conv", action="store_true", help="refused: not a shipped form")
     ap.add_argument("--gradual_resol", action="store_true", help="refused: not a shipped form")
     ap.add_argument("--log_dir", default=None, help="accepted and ignored (TensorBoard is out of scope)")
@@ -426,15 +430,27 @@ def main(argv=None):
     refused = [n for n in ("pred_with_conv", "gradual_resol") if getattr(args, n)]
     if not stage3:
         refused += (["tune_decoder"] if args.tune_decoder else []) + (["perceptual_loss_ratio"] if args.perceptual_loss_ratio is not None else [])
+        refused += ["lpips_precision"] if args.lpips_precision is not None else []
     if refused or args.device != "cuda":
         ap.error(f"not available in ldmae_amd/vmae_pretrain.py: {refused or args.device} (--tune_decoder and --perceptual_loss_ratio only TOGETHER: stage 3 of "
-                 "train_ae.sh; pred_with_conv / gradual_resol are not shipped forms)")
+                 "train_ae.sh, --lpips_precision only with them; pred_with_conv / gradual_resol are not shipped forms)")
+    if args.lpips_precision is None:
+        args.lpips_precision = "f32"
     if stage3:
         from ldmae_amd.models import lpips as lpips_mod
         try:                                                                  # before anything touches the GPU; never downloads
             lpips_mod.resolve_weights(args.lpips_vgg, args.lpips_lin)
         except FileNotFoundError as ex:
             ap.error(str(ex))
+    args.stage3 = stage3
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    stage3 = args.stage3
+    if stage3:
+        from ldmae_amd.models import lpips as lpips_mod
     import torch.distributed as dist
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     # LDMAE_DIST_BACKEND=gloo + LDMAE_DEVICE=0: several ranks share ONE GPU (rehearsal of the multi-rank launch on a 1-GPU box), as train_accum.py
@@ -465,8 +481,9 @@ def main(argv=None):
     torch.manual_seed(args.seed)                                              # every rank builds the same initial weights
     extra = {}
     if stage3:
-        log(f"Using Perceptual loss with ratio = {args.perceptual_loss_ratio}")
-        extra = dict(perceptual_loss=lpips_mod.LPIPS(args.lpips_vgg, args.lpips_lin, device=torch.device("cuda", local), differentiable=True),
+        log(f"Using Perceptual loss with ratio = {args.perceptual_loss_ratio}; LPIPS precision {args.lpips_precision}")
+        extra = dict(perceptual_loss=lpips_mod.LPIPS(args.lpips_vgg, args.lpips_lin, device=torch.device("cuda", local), differentiable=True,
+                                                     precision=args.lpips_precision),
                      perceptual_loss_ratio=args.perceptual_loss_ratio)
     model = getattr(models_mae, args.model)(ldmae_mode=stage3, no_cls=True, kl_loss_weight=args.kl_loss_weight, smooth_output=True, norm_pix_loss=args.norm_pix_loss,
                                             img_size=args.input_size, fixed_std=args.fixed_std, **extra).cuda()  # main_pretrain.py:193-205

@@ -1,12 +1,16 @@
-"""Cost of the LPIPS perceptual loss in the stage-3 decoder tuning on one MI355X, random weights:
-  - every conv data-gradient geometry of the VGG16 backward (ops.conv3x3_relu_dgrad_nhwc) next to the forward conv of the same layer: ms and TF/s;
+"""Cost of the LPIPS perceptual loss in the stage-3 decoder tuning on one MI355X, random weights, per LPIPS precision (models/lpips.py: "f32" =
+exact f32, "fp16" = fp16 VGG forward + bf16 data gradient).  The precisions ALTERNATE inside one process, round by round, so that a difference
+between them is measured against the spread of the same process; every figure is the median over the rounds with (min .. max):
+  - every conv geometry of the VGG16: forward conv and data gradient (ReLU mask in the gather), ms and TF/s;
   - LPIPS forward + backward with the gradient to the target only (what stage 3 asks for) at B = 16, 256 x 256, against the forward-only call;
-  - one stage-3 step (vmae_pretrain's model at --batch_size 16, bf16 and fp16 autocast) and the share LPIPS forward + backward takes of it.
+  - one stage-3 step (vmae_pretrain's model at --batch_size 16, bf16 and fp16 autocast), the share LPIPS forward + backward takes of it, and
+    torch.cuda.max_memory_allocated of the step.
 
-    python tools/bench_lpips_train.py [--batch 16] [--iters 5] [--out profiles/lpips_train_bench.txt]
+    python tools/bench_lpips_train.py [--batch 16] [--iters 5] [--rounds 5] [--precisions f32,fp16] [--out profiles/lpips_train_bench.txt]
 """
 import argparse
 import os
+import statistics
 import sys
 import time
 
@@ -15,11 +19,10 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from ldmae_amd import ops  # noqa: E402
-from ldmae_amd.models.lpips import CONVS, LPIPS, random_state_dict  # noqa: E402
+from ldmae_amd.models.lpips import CONVS, LPIPS, PRECISIONS, random_state_dict  # noqa: E402
 
 
-def timed(fn, iters, warmup=2):
+def timed(fn, iters, warmup=0):
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -30,12 +33,36 @@ def timed(fn, iters, warmup=2):
     return (time.perf_counter() - t0) / iters
 
 
+def alternate(fns, iters, rounds):
+    """fns {key: callable} -> {key: [seconds per call, one per round]}; every callable is warmed up first, then the keys take turns round by round."""
+    for fn in fns.values():
+        timed(fn, 2)
+    out = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            out[k].append(timed(fn, iters))
+    return out
+
+
+def med(ts):
+    return statistics.median(ts)
+
+
+def ms(ts):
+    return f"{med(ts) * 1e3:.3f} ({min(ts) * 1e3:.3f} .. {max(ts) * 1e3:.3f})"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--precisions", default="f32,fp16")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lpips_train_bench.txt"))
     a = ap.parse_args()
+    precs = a.precisions.split(",")
+    if not precs or any(p not in PRECISIONS for p in precs):
+        ap.error(f"--precisions: a comma-separated subset of {PRECISIONS}")
     B, S = a.batch, 256
     lines = []
 
@@ -43,56 +70,80 @@ def main():
         print(s, flush=True)
         lines.append(s)
     torch.manual_seed(0)
-    lp = LPIPS(state_dict=random_state_dict(0), device="cuda", differentiable=True)
+    sd = random_state_dict(0)
+    lps = {p: LPIPS(state_dict=sd, device="cuda", differentiable=True, precision=p) for p in precs}
     x = torch.rand(B, 3, S, S, device="cuda") * 2 - 1
     y = (x + 0.1 * torch.randn_like(x)).clamp(-1, 1)
 
-    say(f"conv data gradient (ReLU mask in the gather) vs the forward conv, one half = {B} images of {S} x {S}, f32")
-    say(f"{'layer':>8} {'H x W':>9} {'Cin':>4} {'Cout':>4} {'fwd ms':>8} {'fwd TF/s':>8} {'dgrad ms':>8} {'dgrad TF/s':>10} {'ratio':>6}")
-    h, prev, tot_f, tot_d = S, 1, 0.0, 0.0
+    say(f"precisions {precs} alternating in one process; {a.rounds} rounds of {a.iters} calls; ms = median (min .. max) over the rounds")
+    say(f"forward conv and conv data gradient (ReLU mask in the gather), one half = {B} images of {S} x {S}; TF/s by the layer's real Cin (3 for conv1_1)")
+    say(f"{'layer':>8} {'H x W':>9} {'Cin':>4} {'Cout':>4} {'prec':>5} {'fwd ms':>24} {'fwd TF/s':>8} {'dgrad ms':>24} {'dgrad TF/s':>10}")
+    h, prev = S, 1
+    tot = {p: [0.0, 0.0] for p in precs}
     for j, (i, s, cin, cout) in enumerate(CONVS):
         if s != prev:
             h, prev = h // 2, s
-        w, b, _ = lp.convs[j]
-        cx = w.shape[3]                                              # 4 for conv1_1 (padded)
-        xin = torch.randn(B, h, h, cx, device="cuda")
-        yout = ops.conv2d_nhwc(xin, w, b, (1, 1), (1, 1), True)
-        dy = torch.randn_like(yout)
-        flops = 2.0 * B * h * h * cout * 9 * cx
-        tf = timed(lambda: ops.conv2d_nhwc(xin, w, b, (1, 1), (1, 1), True, out=yout), a.iters)
-        dx = torch.empty_like(xin)
-        td = timed(lambda: ops.conv3x3_relu_dgrad_nhwc(dy, yout, lp.wrot[j], out=dx), a.iters)
-        tot_f, tot_d = tot_f + tf, tot_d + td
-        say(f"{'conv' + str(s) + '_' + str(j):>8} {h:>4}x{h:<4} {cx:>4} {cout:>4} {tf * 1e3:>8.3f} {flops / tf / 1e12:>8.1f} {td * 1e3:>8.3f} {flops / td / 1e12:>10.1f} "
-            f"{tf / td:>6.2f}")
-    say(f"sum over the 13 layers: forward {tot_f * 1e3:.2f} ms, data gradient {tot_d * 1e3:.2f} ms (ratio = dgrad TF/s over forward TF/s)")
+        flops = 2.0 * B * h * h * cout * 9 * cin
+        fwd, bwd = {}, {}
+        keep = []
+        for p in precs:
+            lp = lps[p]
+            w, b, _ = lp.convs[j]
+            xin = torch.randn(B, h, h, w.shape[3], device="cuda").to(lp._k.act_dtype)      # 4 (f32) or 8 (fp16) channels for conv1_1 (padded)
+            yout = lp._k.conv(xin, w, b)
+            dy = torch.randn(yout.shape, device="cuda")
+            dx = torch.empty(xin.shape, dtype=torch.float32, device="cuda")
+            keep.append((xin, yout, dy, dx))
+            fwd[p] = lambda lp=lp, xin=xin, w=w, b=b, yout=yout: lp._k.conv(xin, w, b, out=yout)
+            bwd[p] = lambda lp=lp, dy=dy, yout=yout, j=j, dx=dx: lp._k.dgrad(dy, yout, lp.wrot[j], out=dx)
+        tf, td = alternate(fwd, a.iters, a.rounds), alternate(bwd, a.iters, a.rounds)
+        for p in precs:
+            tot[p][0] += med(tf[p])
+            tot[p][1] += med(td[p])
+            say(f"{'conv' + str(s) + '_' + str(j):>8} {h:>4}x{h:<4} {cin:>4} {cout:>4} {p:>5} {ms(tf[p]):>24} {flops / med(tf[p]) / 1e12:>8.1f} {ms(td[p]):>24} "
+                f"{flops / med(td[p]) / 1e12:>10.1f}")
+        del keep
+    for p in precs:
+        say(f"sum of the 13 layers' medians, {p}: forward {tot[p][0] * 1e3:.2f} ms, data gradient {tot[p][1] * 1e3:.2f} ms")
 
-    with torch.no_grad():
-        t_fwd = timed(lambda: lp(x, y), a.iters)
+    def fwd_only(lp):
+        with torch.no_grad():
+            lp(x, y)
 
-    def fwd_bwd():
+    def fwd_bwd(lp):
         yg = y.clone().requires_grad_()
         lp(x, yg).mean().backward()
-    t_fb = timed(fwd_bwd, a.iters)
-    say(f"LPIPS B = {B}, {S}^2: forward only {t_fwd * 1e3:.2f} ms; forward + backward to the target {t_fb * 1e3:.2f} ms = {t_fb / t_fwd:.2f} x "
-        f"(by FLOP count 1.5 x: the backward of one half costs one half's forward convs)")
+    t_fwd = alternate({p: (lambda lp=lps[p]: fwd_only(lp)) for p in precs}, a.iters, a.rounds)
+    t_fb = alternate({p: (lambda lp=lps[p]: fwd_bwd(lp)) for p in precs}, a.iters, a.rounds)
+    for p in precs:
+        say(f"LPIPS {p} B = {B}, {S}^2: forward only {ms(t_fwd[p])} ms; forward + backward to the target {ms(t_fb[p])} ms = {med(t_fb[p]) / med(t_fwd[p]):.2f} x")
 
     from ldmae_amd.tokenizer import models_mae
     torch.manual_seed(0)
-    model = models_mae.mae_for_ldmae_f8d16_prev(ldmae_mode=True, no_cls=True, smooth_output=True, kl_loss_weight=0.0, img_size=S, perceptual_loss=lp,
+    model = models_mae.mae_for_ldmae_f8d16_prev(ldmae_mode=True, no_cls=True, smooth_output=True, kl_loss_weight=0.0, img_size=S, perceptual_loss=lps[precs[0]],
                                                 perceptual_loss_ratio=10.0).cuda()
     for prec, dt in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
-        def step(with_lpips=True):
-            model.perceptual_loss = lp if with_lpips else None
+        def step(lp):
+            model.perceptual_loss = lp
             with torch.autocast("cuda", dtype=dt):
                 loss = model(x, mask_ratio=0.0)[0]
             loss.backward()
             model.zero_grad(set_to_none=True)
-        t_step = timed(step, a.iters)
-        t_bare = timed(lambda: step(False), a.iters)
-        model.perceptual_loss = lp
-        say(f"stage-3 step (forward + backward, batch {B}, {prec}, mask_ratio 0.0): {t_step * 1e3:.2f} ms; without LPIPS {t_bare * 1e3:.2f} ms; "
-            f"LPIPS share {100 * (t_step - t_bare) / t_step:.1f} %")
+        fns = {p: (lambda lp=lps[p]: step(lp)) for p in precs}
+        fns["none"] = lambda: step(None)
+        t = alternate(fns, a.iters, a.rounds)
+        peak = {}
+        for k, fn in fns.items():                                                   # the step's own peak, one call each after the timing
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            fn()
+            torch.cuda.synchronize()
+            peak[k] = torch.cuda.max_memory_allocated() / 2 ** 30
+        model.perceptual_loss = lps[precs[0]]
+        say(f"stage-3 step (forward + backward, batch {B}, {prec} autocast, mask_ratio 0.0) without LPIPS: {ms(t['none'])} ms; peak memory {peak['none']:.2f} GiB")
+        for p in precs:
+            say(f"stage-3 step, {prec} autocast, LPIPS {p}: {ms(t[p])} ms; LPIPS share {100 * (med(t[p]) - med(t['none'])) / med(t[p]):.1f} %; "
+                f"peak memory {peak[p]:.2f} GiB")
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")

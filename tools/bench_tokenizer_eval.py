@@ -4,12 +4,16 @@
     the VGG time;
   - end-to-end images/s of encode, decode, the metrics, the device-to-host copy and the PNG encode (the driver's loop, no disk reads).
 
-    python tools/bench_tokenizer_eval.py [--batch 64] [--iters 5] [--no-e2e]
+Per LPIPS precision (models/lpips.py: "f32" exact, "fp16" the 16-bit VGG): the LPIPS call of the precisions ALTERNATES round by round inside one
+process (the figure is the median over the rounds), then the pieces and the end-to-end loop are timed per precision; one JSON line each.
+
+    python tools/bench_tokenizer_eval.py [--batch 64] [--iters 5] [--rounds 3] [--precisions f32,fp16] [--no-e2e]
 """
 import argparse
 import io
 import json
 import os
+import statistics
 import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
@@ -21,7 +25,7 @@ import torch  # noqa: E402
 
 from ldmae_amd import ops  # noqa: E402
 from ldmae_amd.metrics import psnr_from_sse, ssim  # noqa: E402
-from ldmae_amd.models.lpips import LPIPS, conv_flops_per_image, random_state_dict  # noqa: E402
+from ldmae_amd.models.lpips import LPIPS, PRECISIONS, conv_flops_per_image, random_state_dict  # noqa: E402
 
 
 def timed(fn, iters, warmup=1):
@@ -46,41 +50,59 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--precisions", default="f32,fp16")
     ap.add_argument("--no-e2e", action="store_true")
     a = ap.parse_args()
+    precs = a.precisions.split(",")
+    if not precs or any(p not in PRECISIONS for p in precs):
+        ap.error(f"--precisions: a comma-separated subset of {PRECISIONS}")
     B, S = a.batch, 256
     torch.manual_seed(0)
-    lp = LPIPS(state_dict=random_state_dict(0), device="cuda")
+    sd = random_state_dict(0)
+    lps = {p: LPIPS(state_dict=sd, device="cuda", precision=p) for p in precs}
     x = torch.rand(B, 3, S, S, device="cuda") * 2 - 1
     y = (x + 0.1 * torch.randn_like(x)).clamp(-1, 1)
-    res = {"batch": B, "size": S}
+    t_rounds = {p: [] for p in precs}
+    for p in precs:
+        timed(lambda: lps[p](x, y), 1)
+    for _ in range(a.rounds):                                   # the precisions take turns: a difference is seen against this process's own spread
+        for p in precs:
+            t_rounds[p].append(timed(lambda: lps[p](x, y), a.iters, warmup=0))
+    for p in precs:
+        bench_one(a, p, lps[p], x, y, t_rounds[p])
 
-    t_lpips = timed(lambda: lp(x, y), a.iters)
+
+def bench_one(a, prec, lp, x, y, t_rounds):
+    B, S = a.batch, 256
+    k_ = lp._k
+    res = {"batch": B, "size": S, "lpips_precision": prec}
+    t_lpips = statistics.median(t_rounds)
     vgg_flops = 2 * B * conv_flops_per_image(S, S)
     # the pieces apart from the convolutions, on the tensors the forward really sees
-    taps, h, prev = [], ops.lpips_prep(x, y), 1
+    taps, h, prev = [], k_.prep(x, y), 1
     for w, b, s in lp.convs:
         if s != prev:
             taps.append(h)
-            h = ops.pool2d_nhwc(h, "max", k=2, stride=2, pad=0)
+            h = k_.pool(h)
             prev = s
-        h = ops.conv2d_nhwc(h, w, b, (1, 1), (1, 1), True)
+        h = k_.conv(h, w, b)
     taps.append(h)
     out = torch.zeros(B, device="cuda")
-    t_prep = timed(lambda: ops.lpips_prep(x, y), a.iters)
-    t_heads = timed(lambda: [ops.lpips_layer(t, lp.lins[k], out) for k, t in enumerate(taps)], a.iters)
-    t_pool = timed(lambda: [ops.pool2d_nhwc(t, "max", k=2, stride=2, pad=0) for t in taps[:4]], a.iters)
+    t_prep = timed(lambda: k_.prep(x, y), a.iters)
+    t_heads = timed(lambda: [k_.head(t, lp.lins[k], out) for k, t in enumerate(taps)], a.iters)
+    t_pool = timed(lambda: [k_.pool(t) for t in taps[:4]], a.iters)
     t_ssim = timed(lambda: ssim(x, y, reduction="none"), a.iters)
     t_quant = timed(lambda: ops.recon_quantize_sse(x, y), a.iters)
     t_vgg = t_lpips - t_prep - t_heads
     res.update({
-        "lpips_ms": t_lpips * 1e3, "lpips_pairs_per_s": B / t_lpips,
+        "lpips_ms": t_lpips * 1e3, "lpips_ms_min": min(t_rounds) * 1e3, "lpips_ms_max": max(t_rounds) * 1e3, "lpips_pairs_per_s": B / t_lpips,
         "vgg_ms": t_vgg * 1e3, "vgg_tflops": vgg_flops / t_vgg / 1e12, "pool_ms": t_pool * 1e3,
         "prep_ms": t_prep * 1e3, "heads_ms": t_heads * 1e3, "ssim_ms": t_ssim * 1e3, "quantize_psnr_ms": t_quant * 1e3,
         "non_conv_share_of_vgg": (t_prep + t_heads + t_ssim + t_quant) / t_vgg,
     })
-    print(f"LPIPS  batch {B} pairs of {S}^2: {t_lpips * 1e3:.1f} ms = {B / t_lpips:.0f} pairs/s; VGG part (LPIPS minus prep and heads) "
-          f"{t_vgg * 1e3:.1f} ms = {vgg_flops / t_vgg / 1e12:.1f} TF/s (pools included: {t_pool * 1e3:.2f} ms)")
+    print(f"LPIPS {prec}  batch {B} pairs of {S}^2: {t_lpips * 1e3:.1f} ms ({min(t_rounds) * 1e3:.1f} .. {max(t_rounds) * 1e3:.1f}) = {B / t_lpips:.0f} pairs/s; "
+          f"VGG part (LPIPS minus prep and heads) {t_vgg * 1e3:.1f} ms = {vgg_flops / t_vgg / 1e12:.1f} TF/s (pools included: {t_pool * 1e3:.2f} ms)")
     print(f"apart from the convs: prep {t_prep * 1e3:.2f} ms, five heads {t_heads * 1e3:.2f} ms, SSIM {t_ssim * 1e3:.2f} ms, "
           f"quantise + PSNR {t_quant * 1e3:.2f} ms = {100 * res['non_conv_share_of_vgg']:.1f} % of the VGG time")
 
