@@ -548,6 +548,48 @@ int ldmae_prof_collect(double* total_ms, double* total_flops, long* launches);  
 #define LDMAE_COUNT_TN_F16 8
 int ldmae_launch_counts(long* counts, int n, int reset);
 
+/* ---- MXFP8 sampling mode: block-scaled fp8 GEMMs for the DiT block (opt-in, forward-only) ----------
+ * THE ARITHMETIC CONTRACT.
+ *  MX block quantisation.  A row of length K (K % 128 == 0) is cut into blocks of 32 consecutive elements.  Per block: amax = max |x| =
+ *   m * 2^x with m in [1, 2); scale exponent e = x - 8 if m <= 1.75, else x - 7 (the smallest e with amax * 2^-e <= 448: nothing
+ *   saturates), clamped to [-127, 127], e = -127 for amax == 0; computed from the exponent and mantissa bits in integer arithmetic.  The
+ *   scale is stored as the E8M0 byte e + 127 (0xFF is never produced), the elements as OCP e4m3fn (not fnuz) bytes: round-to-nearest-even
+ *   of x * 2^-e (a multiplication by a power of two: exact).  +0 and -0 are one value.  Non-finite and f32-subnormal inputs: unspecified.
+ *  Operands.  Weights are quantised from the f32 master weight along K (their input dimension); activations from the bf16 value that the
+ *   bf16 path would have fed to the same GEMM.  The mode is "the bf16 forward with a quantiser in front of four GEMMs".
+ *  Product.  Exact products of the dequantised values, accumulated in f32 on the scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4), the
+ *   128-deep K-steps in order, no split-K: run-to-run bitwise reproducible.  Everything after the accumulator is the epilogue code of the
+ *   bf16 kernels with its roundings.
+ * The mode's effect on FID has not been measured.  It needs a trained checkpoint.
+ *
+ * q [M, K] e4m3 bytes and scales [M, K/32] E8M0 bytes, both row-major and dense, from rows of f32 or bf16 (src_dtype) `ld` elements apart. */
+int ldmae_mx8_quantize(int src_dtype, const void* src, int ld, void* q, void* scales, int M, int K, void* stream);
+/* The arithmetic of ldmae_rmsnorm_modulate_fwd with a bf16 output (RMSNorm weight w given; shift and / or scale may be NULL) up to and
+ * including its bf16 rounding, quantised in the same kernel: q [M, D], scales [M, D/32] and rstd [M] (may be NULL) are bitwise what that
+ * entry point followed by the quantiser writes.  D % 128 == 0, D <= 2048. */
+int ldmae_rmsnorm_modulate_fwd_mx8(const float* x, const float* w, const float* shift, const float* scale, int mod_ld, void* q,
+                                   void* scales, float* rstd, int M, int D, int rows_per_batch, float eps, void* stream);
+/* C[M,N] = dequant(Aq, As)[M,K] . dequant(Wq, Ws)[N,K]^T with the epilogues LDMAE_EPI_BIAS / LDMAE_EPI_GATE_RES / LDMAE_EPI_SWIGLU (and
+ * LDMAE_EPI_TILE_LAUNCH or'ed in) exactly as the bf16 kernel writes them; out_dtype LDMAE_BF16 or LDMAE_F32 (SwiGLU: bf16).  lda / ldb are
+ * the row strides of the element operands in bytes; the scale operands are dense [rows, K/32].  Covers M, N multiples of 8, K / lda / ldb
+ * multiples of 128, element operands on 128-B lines, SwiGLU N % 256 == 0; the predicate says whether a shape is covered. */
+int ldmae_gemm_nt_mx8_ok(int M, int N, int K, int lda, int ldb);
+int ldmae_gemm_nt_mx8(int out_dtype, int epi, const void* Aq, const void* As, int lda, const void* Wq, const void* Ws, int ldb, void* C,
+                      int ldc, int M, int N, int K, const float* bias, const float* xin, float* xout, const float* gate, int gate_ld,
+                      int rows_per_batch, void* stream);
+/* The qkv Linear with the QK-RMSNorm + RoPE epilogue of the bf16 kernel on the same operands (head dim 64; store_raw_qk = 0: only the v
+ * third of qkv is written). */
+int ldmae_gemm_nt_qkv_rope_mx8_ok(int B, int N, int H, int hd, int K, int lda, int ldb);
+int ldmae_gemm_nt_qkv_rope_mx8(const void* Aq, const void* As, int lda, const void* Wq, const void* Ws, int ldb, const float* bias, void* qkv,
+                               void* q2, void* k2, const float* wq, const float* wk, const float* cos, const float* sin, int B, int N,
+                               int H, int hd, int K, float eps, int store_raw_qk, int tile_launch, void* stream);
+/* Launch counts of this mode since the last reset, separate from the nine family slots above: counts[0] = quantise passes, counts[1] =
+ * norm + quantise passes, counts[2] = block-scaled GEMMs.  n <= 3. */
+#define LDMAE_MX8_COUNT_QUANTIZE 0
+#define LDMAE_MX8_COUNT_NORM_QUANTIZE 1
+#define LDMAE_MX8_COUNT_GEMM 2
+int ldmae_mx8_launch_counts(long* counts, int n, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,13 @@ SIGNATURES = {
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),
+    "ldmae_mx8_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "ldmae_rmsnorm_modulate_fwd_mx8": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "ldmae_gemm_nt_mx8_ok": (_i, [_i, _i, _i, _i, _i]),
+    "ldmae_gemm_nt_mx8": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "ldmae_gemm_nt_qkv_rope_mx8_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "ldmae_gemm_nt_qkv_rope_mx8": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "ldmae_mx8_launch_counts": (_i, [C.POINTER(_l), _i, _i]),
 }
 # csrc/probe/ldmae_diag.h: present only in the diagnostic build (LDMAE_HIP_LIB=.../libldmae_hip_diag.so, used by tools/)
 DIAG_SIGNATURES = {
@@ -245,3 +252,13 @@ def launch_counts(reset: bool = False) -> dict:
     arr = (C.c_long * 9)()
     call("ldmae_launch_counts", arr, 9, 1 if reset else 0)
     return dict(zip(COUNT_NAMES, [int(v) for v in arr]))
+
+
+MX8_COUNT_NAMES = ("quantize", "norm_quantize", "gemm")
+
+
+def mx8_launch_counts(reset: bool = False) -> dict:
+    """Launch counts of the MXFP8 sampling mode since the last reset (ldmae_mx8_launch_counts; separate from launch_counts)."""
+    arr = (C.c_long * 3)()
+    call("ldmae_mx8_launch_counts", arr, 3, 1 if reset else 0)
+    return dict(zip(MX8_COUNT_NAMES, [int(v) for v in arr]))

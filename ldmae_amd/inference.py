@@ -157,7 +157,23 @@ def latent_stats(cfg, device):
     return mean.to(device), std.to(device)
 
 
-def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", cfg_scale=None, demo=False):
+GEMM_PRECISIONS = (None, "mxfp8")
+MX8_NOTICE = ("gemm_precision=mxfp8: the four GEMMs of every DiT block run in MXFP8 (block-scaled OCP e4m3, one E8M0 scale per 32 along K); "
+              "the mode's effect on FID has not been measured")
+
+
+def resolve_gemm_precision(cfg, flag=None):
+    """The block-GEMM arithmetic of the sampler: the --gemm_precision flag when given, else the YAML key sample.gemm_precision, else None (the
+    activation type's own GEMMs, as before the key existed)."""
+    mode = flag if flag is not None else (cfg.get('sample') or {}).get('gemm_precision')
+    if mode in ("", "none", "None"):
+        mode = None
+    if mode not in GEMM_PRECISIONS:
+        raise SystemExit(f"gemm_precision={mode!r}: 'mxfp8', or absent for the activation type's own GEMMs")
+    return mode
+
+
+def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", cfg_scale=None, demo=False, gemm_precision=None):
     """inference.py:40-300.  `out_dir=None` -> <train.output_dir>/<train.exp_name>/<sample_folder_name> as the reference; a folder that already
     holds more than `fid_num` PNGs is left alone (:69-77).  `demo=True`: the eight fixed classes, guidance on every step, unshifted grid, one
     2 x 4 sheet under ./demo_images (:54-57, :219-262) written by rank 0; returns None as the reference does."""
@@ -178,6 +194,12 @@ def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", 
     ck = torch.load(ckpt_path, map_location='cpu')
     model.load_state_dict(ck["ema"] if "ema" in ck else ck)
     model = model.to(device).eval()
+    if gemm_precision is None:
+        gemm_precision = resolve_gemm_precision(cfg)
+    if gemm_precision is not None:
+        model.set_gemm_precision(gemm_precision)
+        if rank == 0:
+            print(MX8_NOTICE)
     if demo:                                                  # :54-57 -- the demo sheet is drawn with guidance on every step of the unshifted grid
         cfg = dict(cfg, sample=dict(s, cfg_interval_start=0, timestep_shift=0))
         s = cfg['sample']
@@ -235,13 +257,19 @@ def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", 
     return out_dir
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', type=str, default='configs/lightningdit_b_ldmvae_f16d16.yaml')           # inference.py:318
     ap.add_argument('--demo', action='store_true', default=False)                                          # inference.py:319
     ap.add_argument('--ckpt', type=str, default=None, help="default: the config's ckpt_path (inference.py:324-327)")
     ap.add_argument('--out', type=str, default=None, help="default: <output_dir>/<exp_name>/<the reference's folder name>")
-    a = ap.parse_args(argv)
+    ap.add_argument('--gemm_precision', type=str, default=None, choices=['mxfp8', 'none'],
+                    help="block-GEMM arithmetic of the DiT (overrides the YAML key sample.gemm_precision); mxfp8: MX block-scaled fp8, forward-only bf16")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     c = yaml.safe_load(open(a.config))
     if a.ckpt is None:
         assert 'ckpt_path' in c, "ckpt_path must be specified in config"
@@ -252,7 +280,10 @@ def main(argv=None):
     precision = {"no": "fp32"}.get(precision, precision)
     if precision not in ("bf16", "fp32"):
         raise SystemExit(f"PRECISION={precision!r}: the sampler runs in bf16 or fp32")
-    folder = do_sample(c, a.ckpt or c['ckpt_path'], a.out, demo=a.demo, precision=precision)
+    gemm_precision = resolve_gemm_precision(c, a.gemm_precision)
+    if a.gemm_precision == "none":            # the flag overrides the YAML in both directions
+        c = dict(c, sample={k: v for k, v in c['sample'].items() if k != 'gemm_precision'})
+    folder = do_sample(c, a.ckpt or c['ckpt_path'], a.out, demo=a.demo, precision=precision, gemm_precision=gemm_precision)
     if not a.demo and int(os.environ.get("RANK", 0)) == 0:
         # inference.py:352-367: an Inception FID of the samples against data.fid_reference_file (tools/calculate_fid.py -> ldmae_amd.fid), run
         # when that file exists (a relative path is taken from the working directory) and the user's Inception weights resolve

@@ -293,12 +293,40 @@ class _AdaLNAllFn(torch.autograd.Function):
         return (dsc, None) + tuple(dW_all[i * rows:(i + 1) * rows] for i in range(n)) + tuple(db_all[i * rows:(i + 1) * rows] for i in range(n))
 
 
+_MX8_FWD_ONLY = ("ldmae_amd LightningDiT: gemm_precision='mxfp8' is forward-only bf16 (sampling under torch.no_grad() with bfloat16 activations); "
+                 "call set_gemm_precision(None) for a grad-enabled or float32 forward")
+
+
+def _block_fwd_mx8(x2, B, N, D, H, hd, eps, cos, sin, sh1, s1, g1, sh2, s2, g2, n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, w12, b12, w3, b3):
+    """The forward-only bf16 block with the MX quantiser (include/ldmae_hip.h: the contract) in front of its four GEMMs: weights quantised
+    from the f32 master weights (cached), activations from the bf16 values the bf16 path feeds to the same GEMMs.  Attention, the adaLN
+    vectors and the f32 residual stream are the bf16 path's."""
+    M = B * N
+    Wqkv, Wp, W12, W3 = (ops.cached_weight_mx8(w) for w in (qkvw, pw, w12, w3))
+    # attention branch
+    a1q, a1s, _ = ops.rmsnorm_modulate_fwd_mx8(x2, n1w, sh1, s1, N, eps)
+    if ops.gemm_nt_qkv_rope_mx8_ok(a1q, Wqkv[0], B, N, H, hd):
+        qkv, q, k = ops.gemm_nt_qkv_rope_mx8(a1q, a1s, Wqkv[0], Wqkv[1], qkvb, qnw, knw, cos, sin, B, N, H, hd, eps, store_raw_qk=False)
+    else:                                  # XL's head dim 72, token counts off the fused epilogue's grid
+        qkv = ops.gemm_nt_mx8(a1q, a1s, Wqkv[0], Wqkv[1], qkvb)
+        q, k, _ = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps, copy_v=False)
+    o, _ = ops.attention_fwd_pv(q, k, qkv, hd ** -0.5, bound=ops.qk_score_bound(qnw, knw, hd, hd ** -0.5) if qnw is not None else None)
+    oq, osc = ops.mx8_quantize(o.view(M, D))
+    xmid, _ = ops.gemm_nt_gate_res_mx8(oq, osc, Wp[0], Wp[1], pb, x2, g1, N)
+    # MLP branch
+    a2q, a2s, _ = ops.rmsnorm_modulate_fwd_mx8(xmid, n2w, sh2, s2, N, eps)
+    _, hid = ops.gemm_nt_swiglu_mx8(a2q, a2s, W12[0], W12[1], b12)
+    hq, hsc = ops.mx8_quantize(hid)
+    xout, _ = ops.gemm_nt_gate_res_mx8(hq, hsc, W3[0], W3[1], b3, xmid, g2, N)
+    return xout.view(B, N, D)
+
+
 class _DiTBlockFn(torch.autograd.Function):
     """LightningDiTBlock.forward (:239-250) with RMSNorm, QK-norm, RoPE, SwiGLU, shift."""
 
     @staticmethod
     def forward(ctx, x, sc, cos, sin, H, eps, dtype, inplace, chain, idx, direct, fwd_only, mod_all, swiglu,
-                n1w, qkvw, qkvb, qnw, knw, qnb, knb, pw, pb, n2w, w12, b12, w3, b3, adaw, adab, input_only=False):
+                n1w, qkvw, qkvb, qnw, knw, qnb, knb, pw, pb, n2w, w12, b12, w3, b3, adaw, adab, input_only=False, gemm_precision=None):
         """n1w / n2w None: LayerNorm without affine parameters (use_rmsnorm=False).  qnw / knw None: no QK-norm; with qnb / knb: nn.LayerNorm
         QK-norm (use_qknorm without use_rmsnorm).  swiglu False: w12 / b12 / w3 / b3 are fc1 / fc2 of the timm Mlp with tanh-GELU (use_swiglu=False)."""
         B, N, D = x.shape
@@ -320,6 +348,10 @@ class _DiTBlockFn(torch.autograd.Function):
         # weight copies, the pre-gate branch outputs y1 / y2 and h12 = [x1 | x2] of the SwiGLU (1.6 GB per XL/1 block at batch 128).
         # The flag comes from the module (grad mode is always off in here and needs_input_grad ignores torch.no_grad()).
         bwd = not fwd_only and any(ctx.needs_input_grad)
+        if gemm_precision == "mxfp8":      # LightningDiT.set_gemm_precision: the four block GEMMs on block-scaled fp8 operands (forward-only)
+            if not fwd_only or dtype != torch.bfloat16:
+                raise RuntimeError(_MX8_FWD_ONLY)
+            return _block_fwd_mx8(x2, B, N, D, H, hd, eps, cos, sin, sh1, s1, g1, sh2, s2, g2, n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, w12, b12, w3, b3)
         Wqkv, WqkvT = _wcopies(qkvw, dtype, bwd)
         Wp, WpT = _wcopies(pw, dtype, bwd)
         ctx.hs = None
@@ -790,6 +822,7 @@ class LightningDiTBlock(nn.Module):
         self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, (4 if wo_shift else 6) * hidden_size, bias=True))
         self.wo_shift = wo_shift
         self.precision = None
+        self.gemm_precision = None     # LightningDiT.set_gemm_precision
 
     def forward(self, x, c, feat_rope=None, _silu_c=None, _dtype=None, _inplace_grad=False, _chain=None, _idx=0, _direct=False, _mod_all=None,
                 _input_only=False):
@@ -799,12 +832,16 @@ class LightningDiTBlock(nn.Module):
         _, qnw, knw, qnb, knb = a.norm_args()
         swiglu = isinstance(m, SwiGLUFFN)
         l1, l2 = (m.w12, m.w3) if swiglu else (m.fc1, m.fc2)
-        return _DiTBlockFn.apply(
-            x.float(), sc, cos, sin, a.num_heads, self.norm1.eps, _dtype or _act_dtype(self.precision),
-            _inplace_grad, _chain, _idx, _direct, not torch.is_grad_enabled(), _mod_all, swiglu,
-            self.norm1.weight, a.qkv.weight, a.qkv.bias, qnw, knw, qnb, knb, a.proj.weight, a.proj.bias,
-            self.norm2.weight, l1.weight, l1.bias, l2.weight, l2.bias,
-            self.adaLN_modulation[1].weight, self.adaLN_modulation[1].bias, _input_only)
+        args = (x.float(), sc, cos, sin, a.num_heads, self.norm1.eps, _dtype or _act_dtype(self.precision),
+                _inplace_grad, _chain, _idx, _direct, not torch.is_grad_enabled(), _mod_all, swiglu,
+                self.norm1.weight, a.qkv.weight, a.qkv.bias, qnw, knw, qnb, knb, a.proj.weight, a.proj.bias,
+                self.norm2.weight, l1.weight, l1.bias, l2.weight, l2.bias,
+                self.adaLN_modulation[1].weight, self.adaLN_modulation[1].bias, _input_only)
+        if self.gemm_precision is not None:          # forward-only mode: the extra argument never reaches a backward
+            if torch.is_grad_enabled():
+                raise RuntimeError(_MX8_FWD_ONLY)
+            return _DiTBlockFn.apply(*args, self.gemm_precision)
+        return _DiTBlockFn.apply(*args)
 
 
 class FinalLayer(nn.Module):
@@ -868,6 +905,7 @@ class LightningDiT(nn.Module):
         self.final_layer = FinalLayer(hidden_size, patch_size, self.out_channels, use_rmsnorm=use_rmsnorm)
         self.precision = None          # None: follow torch.autocast; or torch.float32 / torch.bfloat16
         self._input_grad_only = False  # see input_grad_only()
+        self.gemm_precision = None     # see set_gemm_precision()
         self.initialize_weights()
 
     def set_precision(self, dtype):
@@ -878,6 +916,35 @@ class LightningDiT(nn.Module):
         self.final_layer.precision = dtype
         return self
 
+    def set_gemm_precision(self, mode):
+        """None (default: every path as it is, bit for bit) or "mxfp8": under torch.no_grad() with bf16 activations the four GEMMs of every block
+        (qkv, attention projection, SwiGLU w12, w3) run on MX block-scaled fp8 operands (OCP e4m3 elements, one E8M0 scale per 32 along K;
+        the contract is in include/ldmae_hip.h and DESIGN.md section 19).  Patch embedding, the embedders, the batched adaLN GEMM, attention and
+        the final layer stay as they are.  Forward-only: a grad-enabled or f32 forward with the mode set raises.  The mode's effect on FID has
+        not been measured.  It needs a trained checkpoint."""
+        if mode is not None:
+            if mode != "mxfp8":
+                raise ValueError(f"gemm_precision {mode!r}: None or 'mxfp8'")
+            blk = self.blocks[0] if len(self.blocks) else None
+            why = None
+            if blk is not None and blk.attn.norm_args()[3] is not None:
+                why = "an nn.LayerNorm QK-norm (use_qknorm without use_rmsnorm)"
+            elif not self.use_rmsnorm:
+                why = "use_rmsnorm=False (the LayerNorm blocks have no norm + quantise kernel)"
+            elif blk is not None and not isinstance(blk.mlp, SwiGLUFFN):
+                why = "use_swiglu=False (the timm Mlp blocks have no block-scaled GEMM epilogue)"
+            elif self.hidden_size % 128 != 0:
+                why = f"hidden size {self.hidden_size} is not a multiple of 128"
+            elif blk is not None and blk.mlp.w3.weight.shape[1] % 128 != 0:
+                why = (f"SwiGLU width {blk.mlp.w3.weight.shape[1]} is not a multiple of 128 (the padded 2730 / 4778 widths of LightningDiT-L and "
+                       "LightningDiT-1p6B are not built in this mode)")
+            if why is not None:
+                raise NotImplementedError("ldmae_amd LightningDiT: gemm_precision='mxfp8' is not implemented for " + why)
+        self.gemm_precision = mode
+        for b in self.blocks:
+            b.gemm_precision = mode
+        return self
+
     @contextlib.contextmanager
     def input_grad_only(self, on=True):
         """Inside this context a grad-enabled forward builds a graph whose backward returns the gradient with respect to the input x ALONE:
@@ -885,6 +952,8 @@ class LightningDiT(nn.Module):
         on x -- and the backward launches no weight-gradient GEMM, no side stream and no bias / norm-weight reduction it can avoid.  dx has the
         bits of the full backward.  For vector-Jacobian products with frozen weights (likelihood evaluation: transport.Sampler.
         sample_ode_likelihood); off by default, training never enters it."""
+        if on and self.gemm_precision is not None:
+            raise RuntimeError(_MX8_FWD_ONLY)
         was, self._input_grad_only = self._input_grad_only, bool(on)
         try:
             yield self
@@ -932,6 +1001,8 @@ class LightningDiT(nn.Module):
         dtype = _act_dtype(self.precision)
         if dtype != torch.float32 and self.hidden_size % 64 != 0:
             dtype = torch.float32         # the 16-bit MFMA GEMMs contract in steps of 64: other widths (no registry entry has one) keep f32 activations
+        if self.gemm_precision is not None and (torch.is_grad_enabled() or dtype != torch.bfloat16):
+            raise RuntimeError(_MX8_FWD_ONLY)
         io = self._input_grad_only and torch.is_grad_enabled()
         if io and self.use_checkpoint:
             raise NotImplementedError("ldmae_amd LightningDiT: input_grad_only with use_checkpoint is not implemented (nothing to recompute for: no parameter gradients)")

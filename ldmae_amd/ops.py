@@ -16,6 +16,7 @@ from . import _lib as L
 from ._lib import (BF16, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_POS, EPI_F16_INF, EPI_GATE_RES, EPI_GELU_BWD, EPI_HALF_LINES, EPI_SWIGLU, EPI_SWIGLU_BWD, EPI_TILE_LAUNCH, F32, call, dt,
                    ptr, stream)
 
+mx8_launch_counts = L.mx8_launch_counts      # the MXFP8 sampling mode's own counters (quantise, norm + quantise, GEMM)
 launch_counts = L.launch_counts      # launch counts by kernel family (which arithmetic type, which GEMM form the calls were dispatched to)
 
 _ws = {}
@@ -282,6 +283,123 @@ def gemm_nt_qkv_rope(a, w, bias, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, store_
     k2 = torch.empty_like(q2)
     call("ldmae_gemm_nt_qkv_rope", ptr(a), _ld(a), ptr(w), _ld(w), ptr(bias), ptr(qkv), ptr(q2), ptr(k2), ptr(wq), ptr(wk), ptr(cos), ptr(sin),
          B, N, H, hd, K, eps, 1 if store_raw_qk else 0, 1 if (_launch_flag() & EPI_TILE_LAUNCH) else 0, stream())
+    return qkv, q2, k2
+
+
+# ----------------------------------------------------------------------------- MXFP8 sampling mode (include/ldmae_hip.h: the contract)
+def mx8_quantize(x):
+    """(q [M,K] uint8 e4m3fn bytes, scales [M,K/32] uint8 E8M0 bytes) of the rows of x (f32 or bf16; K % 128 == 0; rows may be strided)."""
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 2:
+        raise RuntimeError(f"mx8_quantize: a 2-D float32 or bfloat16 tensor, got {tuple(x.shape)} {x.dtype}")
+    x = _arg(x, "mx8_quantize x", rows=True)
+    M, K = x.shape
+    if K % 128:
+        raise RuntimeError(f"mx8_quantize: K={K} is not a multiple of 128")
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    sc = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
+    call("ldmae_mx8_quantize", dt(x.dtype), ptr(x), _ld(x), ptr(q), ptr(sc), M, K, stream())
+    return q, sc
+
+
+def rmsnorm_modulate_fwd_mx8(x, w, shift, scale, rows_per_batch, eps=1e-6):
+    """(q, scales, rstd): rmsnorm_modulate_fwd(..., torch.bfloat16) and mx8_quantize of its output in one kernel, bitwise the pair."""
+    M, D = x.shape
+    if w is None:
+        raise RuntimeError("rmsnorm_modulate_fwd_mx8: needs the RMSNorm weight (the LayerNorm form is not built in this mode)")
+    if D % 128:
+        raise RuntimeError(f"rmsnorm_modulate_fwd_mx8: D={D} is not a multiple of 128")
+    q = torch.empty(M, D, dtype=torch.uint8, device=x.device)
+    sc = torch.empty(M, D // 32, dtype=torch.uint8, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    ld = shift.stride(0) if shift is not None else (scale.stride(0) if scale is not None else 0)
+    call("ldmae_rmsnorm_modulate_fwd_mx8", ptr(x), ptr(w), ptr(shift), ptr(scale), ld, ptr(q), ptr(sc), ptr(rstd), M, D, rows_per_batch, eps, stream())
+    return q, sc, rstd
+
+
+def _mx8_pair(aq, asc, wq, wsc, what):
+    """The operands of a block-scaled NT product: uint8 elements [M,K] / [N,K] read as rows, dense uint8 scales [M,K/32] / [N,K/32]."""
+    for t, name in ((aq, "aq"), (asc, "a scales"), (wq, "wq"), (wsc, "w scales")):
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise RuntimeError(f"{what} {name}: a 2-D uint8 tensor, got {tuple(t.shape)} {t.dtype}")
+    if wq.shape[1] != aq.shape[1] or aq.shape[1] % 128:
+        raise RuntimeError(f"{what}: operands {tuple(aq.shape)} and {tuple(wq.shape)} must be [M,K] and [N,K] with K % 128 == 0")
+    K = aq.shape[1]
+    aq, wq = _arg(aq, what + " aq", rows=True), _arg(wq, what + " wq", rows=True)
+    asc = _arg(asc, what + " a scales", torch.uint8, (aq.shape[0], K // 32))
+    wsc = _arg(wsc, what + " w scales", torch.uint8, (wq.shape[0], K // 32))
+    return aq, asc, wq, wsc
+
+
+def gemm_nt_mx8(aq, asc, wq, wsc, bias=None, out_dtype=torch.bfloat16, out=None):
+    """out[M,N] = dequant(aq, asc) @ dequant(wq, wsc)^T + bias on the block-scaled fp8 MFMA; out bf16 or f32."""
+    aq, asc, wq, wsc = _mx8_pair(aq, asc, wq, wsc, "gemm_nt_mx8")
+    M, K = aq.shape
+    N = wq.shape[0]
+    bias = _arg(bias, "gemm_nt_mx8 bias", torch.float32, (N,))
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype, device=aq.device)
+    else:
+        _arg(out, "gemm_nt_mx8 out", out_dtype, (M, N), rows=True, out=True)
+    call("ldmae_gemm_nt_mx8", dt(out.dtype), EPI_BIAS | (_launch_flag() & EPI_TILE_LAUNCH), ptr(aq), ptr(asc), _ld(aq), ptr(wq), ptr(wsc), _ld(wq), ptr(out), _ld(out),
+         M, N, K, ptr(bias), None, None, None, 0, 0, stream())
+    return out
+
+
+def gemm_nt_gate_res_mx8(aq, asc, wq, wsc, bias, xin, gate, rows_per_batch, save_y=False, xout=None, y_dtype=torch.bfloat16):
+    """gemm_nt_gate_res on block-scaled fp8 operands: y = dequant(a) @ dequant(w)^T + bias ; xout = xin + gate[batch] * y (y rounded to y_dtype)."""
+    aq, asc, wq, wsc = _mx8_pair(aq, asc, wq, wsc, "gemm_nt_gate_res_mx8")
+    M, K = aq.shape
+    N = wq.shape[0]
+    if rows_per_batch <= 0 or M % rows_per_batch:
+        raise RuntimeError(f"gemm_nt_gate_res_mx8: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
+    bias = _arg(bias, "gemm_nt_gate_res_mx8 bias", torch.float32, (N,))
+    xin = _arg(xin, "gemm_nt_gate_res_mx8 xin", torch.float32, numel=M * N)
+    gate = _arg(gate, "gemm_nt_gate_res_mx8 gate", torch.float32, (M // rows_per_batch, N), rows=True)
+    y = torch.empty(M, N, dtype=y_dtype, device=aq.device) if save_y else None
+    if xout is None:
+        xout = torch.empty(M, N, dtype=torch.float32, device=aq.device)
+    else:
+        _arg(xout, "gemm_nt_gate_res_mx8 xout", torch.float32, out=True, numel=M * N)
+    call("ldmae_gemm_nt_mx8", dt(y_dtype), EPI_GATE_RES | (_launch_flag() & EPI_TILE_LAUNCH), ptr(aq), ptr(asc), _ld(aq), ptr(wq), ptr(wsc), _ld(wq), ptr(y), N,
+         M, N, K, ptr(bias), ptr(xin), ptr(xout), ptr(gate), _ld(gate) if gate is not None else 0, rows_per_batch, stream())
+    return xout, y
+
+
+def gemm_nt_swiglu_mx8(aq, asc, w12q, w12sc, b12, save_h12=False):
+    """(h12 or None, hid) of gemm_nt_swiglu on block-scaled fp8 operands (bf16 outputs; N = 2 Hs a multiple of 256)."""
+    aq, asc, w12q, w12sc = _mx8_pair(aq, asc, w12q, w12sc, "gemm_nt_swiglu_mx8")
+    M, K = aq.shape
+    N = w12q.shape[0]
+    if N % 256:
+        raise RuntimeError(f"gemm_nt_swiglu_mx8: N={N} (2 * hidden) is not a multiple of 256")
+    b12 = _arg(b12, "gemm_nt_swiglu_mx8 bias", torch.float32, (N,))
+    h12 = torch.empty(M, N, dtype=torch.bfloat16, device=aq.device) if save_h12 else None
+    hid = torch.empty(M, N // 2, dtype=torch.bfloat16, device=aq.device)
+    call("ldmae_gemm_nt_mx8", BF16, EPI_SWIGLU | (_launch_flag() & EPI_TILE_LAUNCH), ptr(aq), ptr(asc), _ld(aq), ptr(w12q), ptr(w12sc), _ld(w12q), ptr(h12), N,
+         M, N, K, ptr(b12), None, ptr(hid), None, 0, 0, stream())
+    return h12, hid
+
+
+def gemm_nt_qkv_rope_mx8_ok(aq, wq, B, N, H, hd):
+    """Does the block-scaled qkv GEMM with the QK-norm / RoPE epilogue cover this call?  (head dim 64, B*N % 256 == 0, N % 128 == 0)"""
+    if aq.dtype != torch.uint8 or wq.dtype != torch.uint8 or aq.dim() != 2 or wq.dim() != 2:
+        return False
+    if aq.data_ptr() % 128 or wq.data_ptr() % 128 or wq.shape[0] != 3 * H * hd or aq.stride(1) != 1 or wq.stride(1) != 1:
+        return False
+    return bool(L.load().ldmae_gemm_nt_qkv_rope_mx8_ok(B, N, H, hd, aq.shape[1], aq.stride(0), wq.stride(0)))
+
+
+def gemm_nt_qkv_rope_mx8(aq, asc, wq, wsc, bias, nwq, nwk, cos, sin, B, N, H, hd, eps=1e-6, store_raw_qk=False):
+    """(qkv, q2, k2) of gemm_nt_qkv_rope on block-scaled fp8 operands (nwq / nwk: the QK-norm weights, None: RoPE only).  Call
+    gemm_nt_qkv_rope_mx8_ok first."""
+    aq, asc, wq, wsc = _mx8_pair(aq, asc, wq, wsc, "gemm_nt_qkv_rope_mx8")
+    M, K = aq.shape
+    bias = _arg(bias, "gemm_nt_qkv_rope_mx8 bias", torch.float32, (3 * H * hd,))
+    qkv = torch.empty(M, 3 * H * hd, dtype=torch.bfloat16, device=aq.device)
+    q2 = torch.empty(B, H, N, hd, dtype=torch.bfloat16, device=aq.device)
+    k2 = torch.empty_like(q2)
+    call("ldmae_gemm_nt_qkv_rope_mx8", ptr(aq), ptr(asc), _ld(aq), ptr(wq), ptr(wsc), _ld(wq), ptr(bias), ptr(qkv), ptr(q2), ptr(k2), ptr(nwq), ptr(nwk),
+         ptr(cos), ptr(sin), B, N, H, hd, K, eps, 1 if store_raw_qk else 0, 1 if (_launch_flag() & EPI_TILE_LAUNCH) else 0, stream())
     return qkv, q2, k2
 
 
@@ -730,6 +848,21 @@ def cached_weight_copy(w, dtype):
     if len(_WCACHE) > 4096:
         _WCACHE.clear()
     c = cast_weight(w, dtype, transposed=False, straight=True)[0]
+    _WCACHE[key] = (weakref.ref(w), stamp, c)
+    return c
+
+
+def cached_weight_mx8(w):
+    """(q, scales) of the f32 master weight `w` [N, K], MX-quantised along K, for FORWARD-ONLY use: cached under the rule of
+    cached_weight_copy (storage pointer, torch's version counter, WEIGHT_EPOCH; weak reference against a recycled id())."""
+    key = (id(w), "mx8")
+    stamp = (w.data_ptr(), w._version, WEIGHT_EPOCH)
+    hit = _WCACHE.get(key)
+    if hit is not None and hit[0]() is w and hit[1] == stamp:
+        return hit[2]
+    if len(_WCACHE) > 4096:
+        _WCACHE.clear()
+    c = mx8_quantize(w)
     _WCACHE[key] = (weakref.ref(w), stamp, c)
     return c
 
