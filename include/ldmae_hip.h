@@ -528,6 +528,20 @@ int ldmae_rademacher_f32(float* out, long n, unsigned long long seed, unsigned l
 long ldmae_rowdot_partials(int B, long m);
 int ldmae_rowdot_f32(const float* a, const float* b, float* out, int B, long m, float* partial, void* stream);
 int ldmae_likelihood_finish_f32(const float* sumsq, const float* delta, float c, float* logp, int B, void* stream);
+/* SDE sampler (transport.Sampler.sample_sde: Euler-Maruyama / Heun on the linear path), f32, 16-byte accesses, grid a function of n alone.
+ * normal: out[i] = a standard normal from Philox4x32-10, key and counter words as rademacher (block v = i / 4).  Word w_j of the block gives
+ * u_j = ((w_j >> 9) + 0.5) 2^-23 (exact in f32; strictly inside (0, 1)); Box-Muller on (u0, u1) and (u2, u3): r = sqrt(-2 ln u_a),
+ * (r cos(2 pi u_b), r sin(2 pi u_b)); element i takes value i % 4 of its block.  |out[i]| <= sqrt(48 ln 2) = 5.77.
+ * sde_combine: out = sum_{j < m} coef[j] in_j + noise_coef * z, m in 1..4 (coef: m host floats; in_j unused for j >= m), accumulated left to
+ * right: coef[0] in_0 rounded, then one fma per further term, the noise term last.  noise_mode 0: no noise term; 1: z is a tensor; 2: z is the
+ * draw normal(seed, counter), generated in the same pass and never stored (bit for bit what mode 1 gives on ldmae_normal_f32's output).
+ * mean_out (or NULL) receives the sum without the noise term.  t_out (or NULL): t_out[0..nt) = t_next.  Every tensor 16-byte aligned
+ * (t_out 4-byte).  out and mean_out may each BE one of the inputs or z (in place); a partial overlap is refused (LDMAE_ERR_INVALID), as is
+ * out overlapping mean_out, or t_out overlapping anything. */
+int ldmae_normal_f32(float* out, long n, unsigned long long seed, unsigned long long counter, void* stream);
+int ldmae_sde_combine_f32(const float* in0, const float* in1, const float* in2, const float* in3, const float* coef, int m, const float* z,
+                          float noise_coef, int noise_mode, unsigned long long seed, unsigned long long counter, float* out, float* mean_out,
+                          long n, float t_next, float* t_out, int nt, void* stream);
 
 /* ---- optional per-kernel timing hook used by bench.py for the roofline line ------------------- */
 /* When enabled, ldmae_gemm_nt brackets each launch with HIP events on the launch stream. */

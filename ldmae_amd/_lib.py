@@ -156,6 +156,8 @@ SIGNATURES = {
     "ldmae_rowdot_partials": (_l, [_i, _l]),
     "ldmae_rowdot_f32": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
     "ldmae_likelihood_finish_f32": (_i, [_vp, _vp, _f, _vp, _i, _vp]),
+    "ldmae_normal_f32": (_i, [_vp, _l, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "ldmae_sde_combine_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _vp, _f, _i, C.c_ulonglong, C.c_ulonglong, _vp, _vp, _l, _f, _vp, _i, _vp]),
     "ldmae_prof_enable": (_i, [_i]),
     "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
     "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),

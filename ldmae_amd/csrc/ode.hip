@@ -17,6 +17,10 @@
 // Likelihood evaluation (transport.Sampler.sample_ode_likelihood) adds the Hutchinson probe and its reductions at the end of this file: the
 // Rademacher draw from Philox4x32-10 (Salmon et al., SC'11: a counter-based generator, so the draw is a function of (seed, counter, element)
 // alone), the per-sample dot product of two [B, m] tensors, and the last line of the log-likelihood.  Same rules: f32, no atomics, fixed order.
+//
+// The SDE sampler (transport.Sampler.sample_sde) adds the standard-normal draw from the same generator (Box-Muller on its words) and the one
+// launch between two model evaluations of an Euler-Maruyama / Heun step: a linear combination of up to four tensors plus a multiple of the
+// draw, the draw generated in the same pass.  Its coefficients come from the host by value: nothing is read back.
 #include "common.h"
 
 namespace {
@@ -332,6 +336,124 @@ __global__ void likelihood_finish_kernel(const float* __restrict__ sumsq, const 
   if (i < B) logp[i] = __fsub_rn(__fsub_rn(c, __fmul_rn(sumsq[i], 0.5f)), delta[i]);
 }
 
+// ---------------------------------------------------------------- SDE sampler: the standard-normal draw and the step's linear combination
+// One Philox block = four words = four normals.  Word w gives u = ((w >> 9) + 0.5) 2^-23 = (2 (w >> 9) + 1) 2^-24: an odd 24-bit integer times
+// a power of two, exact in f32 and strictly inside (0, 1).  Box-Muller on (u0, u1) and (u2, u3): r = sqrt(-2 ln u_a), the angle 2 pi u_b rounded
+// once, z = (r cos, r sin).  Every product is a named rounding (no contraction), so the draw has the same bits wherever it is inlined.
+constexpr float SDE_TWO_PI = 6.283185307179586f;
+
+__device__ __forceinline__ float philox_u01(unsigned w) { return (float)(((w >> 9) << 1) | 1u) * 0x1p-24f; }
+
+__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float& z0, float& z1) {
+  const float r = sqrtf(__fmul_rn(-2.f, logf(philox_u01(wa))));
+  float s, c;
+  sincosf(__fmul_rn(SDE_TWO_PI, philox_u01(wb)), &s, &c);
+  z0 = __fmul_rn(r, c);
+  z1 = __fmul_rn(r, s);
+}
+
+// the four normals of elements 4 v .. 4 v + 3 of the draw (seed = (k0, k1), counter = (c0, c1))
+__device__ __forceinline__ void philox_normal4(long v, unsigned k0, unsigned k1, unsigned c0, unsigned c1, float (&z)[4]) {
+  unsigned c[4] = {c0, c1, (unsigned)((unsigned long)v & 0xffffffffu), (unsigned)((unsigned long)v >> 32)};
+  philox4x32_10(c, k0, k1);
+  box_muller(c[0], c[1], z[0], z[1]);
+  box_muller(c[2], c[3], z[2], z[3]);
+}
+
+__global__ __launch_bounds__(ODE_THREADS) void normal_kernel(float* __restrict__ out, long n, unsigned k0, unsigned k1, unsigned c0, unsigned c1, int vec) {
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v > nvec || (v == nvec && (n & 3) == 0)) continue;
+    float z[4];
+    philox_normal4(v, k0, k1, c0, c1, z);
+    if (v < nvec && vec) {
+      ((float4*)out)[v] = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+      const long e0 = v << 2;
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j < n) out[e0 + j] = z[j];
+    }
+  }
+}
+
+// out = sum_{j < M} coef_j in_j (+ noise_coef z); mean_out (optional) = the sum without the noise term.  NOISE 0: none, 1: z read from memory,
+// 2: z drawn here (philox_normal4) and never stored.  out / mean_out may BE one of the inputs (an item is read whole before it is written, and
+// no other thread touches it), hence no __restrict__ on them or on the inputs.
+struct SdeIn { const float* p[4]; float c[4]; };
+enum { SDE_NOISE_NONE = 0, SDE_NOISE_TENSOR = 1, SDE_NOISE_PHILOX = 2 };
+
+template <int M> __device__ __forceinline__ float sde_sum(const float (&x)[4], const SdeIn& a) {
+  float acc = __fmul_rn(a.c[0], x[0]);
+#pragma unroll
+  for (int j = 1; j < M; ++j) acc = __builtin_fmaf(a.c[j], x[j], acc);
+  return acc;
+}
+
+template <int M, int NOISE>
+__global__ __launch_bounds__(ODE_THREADS) void sde_combine_kernel(SdeIn a, const float* zt, float noise_coef, unsigned k0, unsigned k1, unsigned c0,
+                                                                  unsigned c1, float* out, float* mean_out, long n, float t_next,
+                                                                  float* __restrict__ t_out, int nt) {
+  if (t_out && blockIdx.x == 0)                                 // the time vector of the NEXT model evaluation, one value per sample
+    for (int i = threadIdx.x; i < nt; i += ODE_THREADS) t_out[i] = t_next;
+  const long nvec = n >> 2;
+  const long base = (long)blockIdx.x * ODE_BLOCK_ITEMS + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < ODE_UNROLL; ++u) {
+    const long v = base + (long)u * ODE_THREADS;
+    if (v > nvec || (v == nvec && (n & 3) == 0)) continue;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (NOISE == SDE_NOISE_PHILOX) philox_normal4(v, k0, k1, c0, c1, z);
+    if (v < nvec) {
+      float4 x[M];
+#pragma unroll
+      for (int j = 0; j < M; ++j) x[j] = ((const float4*)a.p[j])[v];
+      if (NOISE == SDE_NOISE_TENSOR) {
+        const float4 zz = ((const float4*)zt)[v];
+        z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w;
+      }
+      float xa[4] = {0.f, 0.f, 0.f, 0.f}, xb[4] = {0.f, 0.f, 0.f, 0.f}, xc[4] = {0.f, 0.f, 0.f, 0.f}, xd[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < M; ++j) { xa[j] = x[j].x; xb[j] = x[j].y; xc[j] = x[j].z; xd[j] = x[j].w; }
+      const float4 m = make_float4(sde_sum<M>(xa, a), sde_sum<M>(xb, a), sde_sum<M>(xc, a), sde_sum<M>(xd, a));
+      if (mean_out) ((float4*)mean_out)[v] = m;
+      ((float4*)out)[v] = NOISE == SDE_NOISE_NONE ? m : make_float4(__builtin_fmaf(noise_coef, z[0], m.x), __builtin_fmaf(noise_coef, z[1], m.y),
+                                                                    __builtin_fmaf(noise_coef, z[2], m.z), __builtin_fmaf(noise_coef, z[3], m.w));
+    } else {
+      const long e0 = nvec << 2;
+      for (int e = 0; e < 4; ++e) {
+        const long i = e0 + e;
+        if (i >= n) break;
+        float xi[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < M; ++j) xi[j] = a.p[j][i];
+        const float zi = NOISE == SDE_NOISE_TENSOR ? zt[i] : z[e];
+        const float m = sde_sum<M>(xi, a);
+        if (mean_out) mean_out[i] = m;
+        out[i] = NOISE == SDE_NOISE_NONE ? m : __builtin_fmaf(noise_coef, zi, m);
+      }
+    }
+  }
+}
+
+template <int M>
+void launch_sde_combine(int noise, const SdeIn& a, const float* z, float noise_coef, unsigned long long seed, unsigned long long counter, float* out,
+                        float* mean_out, long n, float t_next, float* t_out, int nt, hipStream_t st) {
+  const unsigned k0 = (unsigned)(seed & 0xffffffffu), k1 = (unsigned)(seed >> 32), c0 = (unsigned)(counter & 0xffffffffu), c1 = (unsigned)(counter >> 32);
+  const dim3 grid(ode_grid(n)), block(ODE_THREADS);
+  if (noise == SDE_NOISE_NONE)
+    hipLaunchKernelGGL((sde_combine_kernel<M, SDE_NOISE_NONE>), grid, block, 0, st, a, z, noise_coef, k0, k1, c0, c1, out, mean_out, n, t_next, t_out, nt);
+  else if (noise == SDE_NOISE_TENSOR)
+    hipLaunchKernelGGL((sde_combine_kernel<M, SDE_NOISE_TENSOR>), grid, block, 0, st, a, z, noise_coef, k0, k1, c0, c1, out, mean_out, n, t_next, t_out, nt);
+  else
+    hipLaunchKernelGGL((sde_combine_kernel<M, SDE_NOISE_PHILOX>), grid, block, 0, st, a, z, noise_coef, k0, k1, c0, c1, out, mean_out, n, t_next, t_out, nt);
+}
+
+// [a, a + n) and [b, b + n) floats: identical or disjoint
+inline bool same_or_disjoint(const float* a, const float* b, long n) { return a == b || a + n <= b || b + n <= a; }
+
 template <int M>
 void launch_stage(const float* y, const float* k, long ld, const RkCoef& cf, const float* h_dev, float* out, long n, const float* t_dev, float ct,
                   float* t_out, int nt, hipStream_t st) {
@@ -419,6 +541,53 @@ extern "C" int ldmae_rademacher_f32(float* out, long n, unsigned long long seed,
   hipLaunchKernelGGL(rademacher_kernel, dim3(ode_grid(n)), dim3(ODE_THREADS), 0, as_stream(stream), out, n, (unsigned)(seed & 0xffffffffu),
                      (unsigned)(seed >> 32), (unsigned)(counter & 0xffffffffu), (unsigned)(counter >> 32), al16(out) ? 1 : 0);
   LDMAE_CHECK_LAUNCH("rademacher");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_normal_f32(float* out, long n, unsigned long long seed, unsigned long long counter, void* stream) {
+  LDMAE_REQUIRE(out && n > 0 && ((uintptr_t)out & 3) == 0, "normal: bad arguments (n = %ld)", n);
+  LDMAE_REQUIRE(ode_items(n) <= 0x7fffffffL * ODE_BLOCK_ITEMS, "normal: n too large");
+  hipLaunchKernelGGL(normal_kernel, dim3(ode_grid(n)), dim3(ODE_THREADS), 0, as_stream(stream), out, n, (unsigned)(seed & 0xffffffffu),
+                     (unsigned)(seed >> 32), (unsigned)(counter & 0xffffffffu), (unsigned)(counter >> 32), al16(out) ? 1 : 0);
+  LDMAE_CHECK_LAUNCH("normal");
+  return LDMAE_OK;
+}
+
+extern "C" int ldmae_sde_combine_f32(const float* in0, const float* in1, const float* in2, const float* in3, const float* coef, int m, const float* z,
+                                     float noise_coef, int noise_mode, unsigned long long seed, unsigned long long counter, float* out,
+                                     float* mean_out, long n, float t_next, float* t_out, int nt, void* stream) {
+  LDMAE_REQUIRE(coef && out && n > 0 && m >= 1 && m <= 4, "sde_combine: bad arguments (m = %d, n = %ld)", m, n);
+  LDMAE_REQUIRE(noise_mode >= SDE_NOISE_NONE && noise_mode <= SDE_NOISE_PHILOX, "sde_combine: noise_mode %d (0 none, 1 tensor, 2 Philox)", noise_mode);
+  LDMAE_REQUIRE((noise_mode == SDE_NOISE_TENSOR) == (z != nullptr), "sde_combine: z is given exactly when noise_mode is 1");
+  LDMAE_REQUIRE(!t_out || (nt > 0 && ((uintptr_t)t_out & 3) == 0), "sde_combine: t_out needs nt > 0 and 4-byte alignment");
+  LDMAE_REQUIRE(ode_items(n) <= 0x7fffffffL * ODE_BLOCK_ITEMS, "sde_combine: n too large");
+  SdeIn a;
+  const float* in[4] = {in0, in1, in2, in3};
+  for (int j = 0; j < 4; ++j) {
+    a.p[j] = j < m ? in[j] : nullptr;
+    a.c[j] = j < m ? coef[j] : 0.f;
+    LDMAE_REQUIRE(j >= m || (in[j] && al16(in[j])), "sde_combine: input %d is null or not 16-byte aligned", j);
+  }
+  LDMAE_REQUIRE(al16(out) && al16(mean_out) && al16(z), "sde_combine: out, mean_out and z must be 16-byte aligned");
+  // in place is allowed (out or mean_out IS an input); a partial overlap would let one thread read what another has already written
+  LDMAE_REQUIRE(!mean_out || (mean_out + n <= out || out + n <= mean_out), "sde_combine: out and mean_out overlap");
+  for (int j = 0; j < m; ++j)
+    LDMAE_REQUIRE(same_or_disjoint(out, in[j], n) && (!mean_out || same_or_disjoint(mean_out, in[j], n)),
+                  "sde_combine: an output partially overlaps input %d (in place means the same pointer)", j);
+  LDMAE_REQUIRE(!z || (same_or_disjoint(out, z, n) && (!mean_out || same_or_disjoint(mean_out, z, n))), "sde_combine: an output partially overlaps z");
+  if (t_out) {
+    const float* all[7] = {in0, in1, in2, in3, z, out, mean_out};
+    for (int j = 0; j < 7; ++j)
+      LDMAE_REQUIRE(!all[j] || (j < 4 && j >= m) || t_out + nt <= all[j] || all[j] + n <= t_out, "sde_combine: t_out overlaps a tensor of the step");
+  }
+  hipStream_t st = as_stream(stream);
+  switch (m) {
+    case 1: launch_sde_combine<1>(noise_mode, a, z, noise_coef, seed, counter, out, mean_out, n, t_next, t_out, nt, st); break;
+    case 2: launch_sde_combine<2>(noise_mode, a, z, noise_coef, seed, counter, out, mean_out, n, t_next, t_out, nt, st); break;
+    case 3: launch_sde_combine<3>(noise_mode, a, z, noise_coef, seed, counter, out, mean_out, n, t_next, t_out, nt, st); break;
+    default: launch_sde_combine<4>(noise_mode, a, z, noise_coef, seed, counter, out, mean_out, n, t_next, t_out, nt, st); break;
+  }
+  LDMAE_CHECK_LAUNCH("sde_combine");
   return LDMAE_OK;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Sampling driver -- counterpart of the reference's LDMAE/inference.py (`run_inference.sh`): EMA checkpoint -> shifted-grid
-ODE (sample.sampling_method: euler / heun / midpoint / dopri5) with classifier-free guidance (CFG on the first three channels, interval
+ODE (sample.sampling_method: euler / heun / midpoint / dopri5), or with sample.mode SDE the Euler-Maruyama / Heun SDE, with classifier-free guidance (CFG on the first three channels, interval
 gate) -> latent de-normalisation -> VMAE ``decode_to_images`` -> PNGs.  Ranks are independent replicas (seed = global_seed * world + rank, inference.py:87)."""
 import argparse
 import math
@@ -25,10 +25,42 @@ def build_sampler(cfg):
     t, s = cfg['transport'], cfg['sample']
     tr = create_transport(t['path_type'], t['prediction'], t['loss_weight'], t['train_eps'], t['sample_eps'],
                           use_cosine_loss=t.get('use_cosine_loss', False), use_lognorm=t.get('use_lognorm', False))
+    if s['mode'] == "SDE":
+        return build_sde_sampler(cfg, tr)
     if s['mode'] != "ODE":
         raise NotImplementedError(f"Sampling mode {s['mode']} is not supported.")
     return Sampler(tr).sample_ode(sampling_method=s['sampling_method'], num_steps=s['num_sampling_steps'], atol=s['atol'], rtol=s['rtol'],
                                   reverse=s['reverse'], timestep_shift=s.get('timestep_shift', 0))
+
+
+SDE_DEFAULTS = dict(diffusion_form="sigma", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04)
+SDE_METHOD_NAMES = {"euler": "Euler", "heun": "Heun"}
+
+
+def sde_options(cfg):
+    """The keyword arguments of Sampler.sample_sde from the YAML's sample.* keys: sampling_method (the ODE's key; 'euler' / 'heun' in any case),
+    num_sampling_steps, and the optional diffusion_form (default 'sigma': finite at t0 = 0, unlike the sampler's own default SBDM),
+    diffusion_norm, last_step ('None' / null for no last step), last_step_size."""
+    s = cfg['sample']
+    method = SDE_METHOD_NAMES.get(str(s['sampling_method']).lower())
+    if method is None:
+        raise NotImplementedError(f"sample.mode SDE: sampling_method {s['sampling_method']!r} is not supported: 'euler' or 'heun'")
+    kw = {k: s.get(k, d) for k, d in SDE_DEFAULTS.items()}
+    if kw['last_step'] in ("None", "none"):
+        kw['last_step'] = None
+    return dict(kw, sampling_method=method, num_steps=s['num_sampling_steps'])
+
+
+def build_sde_sampler(cfg, tr):
+    """sample.mode SDE.  create_transport forces sample_eps = 0 for the velocity model; the SBDM diffusion needs t0 = sample_eps > 0, so for that
+    form the transport takes the YAML's transport.sample_eps (null or 0: Sampler.sample_sde refuses, saying why).  Every rank draws its own
+    noise: seed = global_seed * world + rank, the rule of torch.manual_seed in do_sample."""
+    kw = sde_options(cfg)
+    if kw['diffusion_form'] == "SBDM":
+        tr.sample_eps = cfg['transport'].get('sample_eps') or 0
+    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    seed = (cfg.get('train') or {}).get('global_seed', 0) * world + rank
+    return Sampler(tr).sample_sde(seed=seed, keep_trajectory=False, **kw)
 
 
 @torch.no_grad()
@@ -121,7 +153,8 @@ DEMO_LABELS = [975, 3, 207, 387, 388, 88, 979, 279]          # inference.py:223
 def sample_folder_name(cfg, ckpt_path, cfg_scale=None):
     """The directory name rule of inference.py:45-52 (the FID tooling downstream finds the PNGs by it)."""
     s = cfg['sample']
-    name = f"{cfg['model']['model_type'].replace('/', '-')}-ckpt-{ckpt_path.split('/')[-1].split('.')[0]}-{s['sampling_method']}-{s['num_sampling_steps']}".lower()
+    method = ("sde-" if s.get('mode') == "SDE" else "") + s['sampling_method']          # the SDE's euler is not the ODE's: its own folder
+    name = f"{cfg['model']['model_type'].replace('/', '-')}-ckpt-{ckpt_path.split('/')[-1].split('.')[0]}-{method}-{s['num_sampling_steps']}".lower()
     cfg_scale = s['cfg_scale'] if cfg_scale is None else cfg_scale
     if cfg_scale > 1.0:
         name += f"-interval{s.get('cfg_interval_start', 0):.2f}" + f"-cfg{cfg_scale:.2f}" + f"-shift{s.get('timestep_shift', 0):.2f}"
@@ -249,6 +282,8 @@ def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", 
             solver = getattr(sample_fn, "__self__", None)
             if it == 0 and rank == 0 and getattr(solver, "sampler_type", None) == "dopri5":
                 print(f"dopri5 (atol {solver.atol:g}, rtol {solver.rtol:g}): nfe {solver.nfe}, accepted {solver.accepted}, rejected {solver.rejected}")
+            if it == 0 and rank == 0 and hasattr(sample_fn, "model_calls"):
+                print(f"SDE ({sample_fn.sde.sampler_type}, {len(sample_fn.sde.t)} steps): {sample_fn.model_calls} model calls per batch")
             imgs = decode(lat)
             writer.put(imgs, [f"{out_dir}/{i * world + rank + done:06d}.png" for i in range(len(imgs))])   # index rule: inference.py:294
             done += n * world
@@ -265,12 +300,17 @@ def build_parser():
     ap.add_argument('--out', type=str, default=None, help="default: <output_dir>/<exp_name>/<the reference's folder name>")
     ap.add_argument('--gemm_precision', type=str, default=None, choices=['mxfp8', 'none'],
                     help="block-GEMM arithmetic of the DiT (overrides the YAML key sample.gemm_precision); mxfp8: MX block-scaled fp8, forward-only bf16")
+    ap.add_argument('--mode', type=str, default=None, choices=['ODE', 'SDE'],
+                    help="overrides the YAML key sample.mode; SDE: Euler-Maruyama / Heun with the optional keys sample.diffusion_form (default "
+                         "sigma), diffusion_norm, last_step, last_step_size")
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     c = yaml.safe_load(open(a.config))
+    if a.mode is not None:
+        c = dict(c, sample=dict(c['sample'], mode=a.mode))
     if a.ckpt is None:
         assert 'ckpt_path' in c, "ckpt_path must be specified in config"
     # run_inference.sh passes --mixed_precision $PRECISION (default bf16) to the launcher, which exports ACCELERATE_MIXED_PRECISION; the

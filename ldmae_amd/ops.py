@@ -1889,3 +1889,41 @@ def likelihood_finish(sumsq, delta, m):
     out = torch.empty(B, dtype=torch.float32, device=sumsq.device)
     call("ldmae_likelihood_finish_f32", ptr(sumsq), ptr(delta), -m / 2.0 * math.log(2 * math.pi), ptr(out), B, stream())
     return out
+
+
+# ----------------------------------------------------------------------------- SDE sampler (csrc/ode.hip), f32
+def normal(shape, seed, counter, device, out=None):
+    """Standard normals of the given shape from Philox4x32-10 keyed by `seed`, counter words (counter, element index / 4), Box-Muller on the four
+    words of a block (include/ldmae_hip.h).  A function of (seed, counter, element index) alone; transport/probe.normal restates it in f64."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    if out.numel() == 0:
+        raise RuntimeError("normal: empty shape")
+    _ode_vec(out, "normal out", out.numel())
+    call("ldmae_normal_f32", ptr(out), out.numel(), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), stream())
+    return out
+
+
+def sde_combine(ins, coef, out, noise_coef=0.0, z=None, seed=None, counter=0, mean_out=None, t_next=0.0, t_out=None):
+    """out = sum_j coef[j] * ins[j] + noise_coef * z in one pass (1 to 4 inputs, fixed left-to-right fma order, the noise term last).  z: a tensor,
+    or None with `seed` given: the draw normal(seed, counter), generated inside the kernel and never stored; neither: no noise term.
+    mean_out: the sum without the noise term.  t_out (f32 [B]): every element = t_next as well, the time vector of the next model evaluation.
+    out / mean_out may be one of the inputs (in place).  Returns out."""
+    n, m = out.numel(), len(ins)
+    if not 1 <= m <= 4 or len(coef) != m:
+        raise RuntimeError(f"sde_combine: 1 to 4 inputs with one coefficient each, got {m} inputs and {len(coef)} coefficients")
+    for j, t in enumerate(ins):
+        _ode_vec(t, f"sde_combine input {j}", n)
+    _ode_vec(out, "sde_combine out", n)
+    if z is not None:
+        _ode_vec(z, "sde_combine z", n)
+    if mean_out is not None:
+        _ode_vec(mean_out, "sde_combine mean_out", n)
+    if t_out is not None:
+        _ode_vec(t_out, "sde_combine t_out", t_out.numel())
+    mode = 1 if z is not None else (2 if seed is not None else 0)
+    p = [ptr(t) for t in ins] + [None] * (4 - m)
+    cf = (ctypes.c_float * 4)(*([float(c) for c in coef] + [0.0] * (4 - m)))
+    call("ldmae_sde_combine_f32", p[0], p[1], p[2], p[3], cf, m, ptr(z), float(noise_coef), mode, int(seed or 0) & (2 ** 64 - 1),
+         int(counter) & (2 ** 64 - 1), ptr(out), ptr(mean_out), n, float(t_next), ptr(t_out), 0 if t_out is None else t_out.numel(), stream())
+    return out

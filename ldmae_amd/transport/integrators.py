@@ -1,6 +1,7 @@
 """ODE integrators on the sampler's shifted grid (reference: LDMAE/transport/integrators.py:77-125, which hands `sampler_type` to
 torchdiffeq.odeint).  No torchdiffeq here: the fixed-step solvers (euler / heun / midpoint) are written out, and the adaptive `dopri5` follows
-torchdiffeq's published algorithm (rk_common.py / dopri5.py) with its own arithmetic in HIP kernels (csrc/ode.hip)."""
+torchdiffeq's published algorithm (rk_common.py / dopri5.py) with its own arithmetic in HIP kernels (csrc/ode.hip).  The SDE integrator (class
+`sde`, reference integrators.py:8-75: Euler-Maruyama / Heun) is at the end of the file: one HIP launch between two model evaluations."""
 import torch as th
 
 
@@ -200,3 +201,119 @@ class ode:
         if logp is not None:
             return traj[:, :nx].reshape((len(grid),) + tuple(shape)), traj[:, nx:].contiguous()
         return traj
+
+
+SDE_METHODS = ("Euler", "Heun")
+
+
+def _f32(v, what):
+    """One rounding of a host f64 coefficient to f32, as a Python float; a coefficient that is not finite is an error, not a sample."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        r = float(np.float32(v))
+    if not np.isfinite(r):
+        raise ValueError(f"ldmae_amd sde: the coefficient {what} is not finite ({v}); the grid touches a singular point of the diffusion form")
+    return r
+
+
+def sde_drift_terms(t, w):
+    """(alpha, beta) of the reference's SDE drift v + w score = beta v - alpha x for a velocity model on the linear path: the score is
+    (t v - x) / var with var = (1-t)^2 + t (1-t) (path.score_from_velocity), so alpha = w / var and beta = 1 + w t / var.  Host f64."""
+    from .path import score_from_velocity
+    a, b = score_from_velocity(t)
+    return -w * b, 1 + w * a
+
+
+class sde:
+    """Euler-Maruyama / Heun on the fixed grid linspace(t0, t1, num_steps) (reference: integrators.py:8-75) for a velocity model on the linear
+    path.  The reference's constructor keywords; where it takes the SDE drift and the diffusion as tensor functions, this takes
+
+        drift      (x, t, model, **kw) -> v, the model's velocity (Transport.get_drift()): ONE model call per drift evaluation,
+        diffusion  t -> w(t), the diffusion coefficient at one time on the host (f64),
+
+    and builds the SDE drift beta v - alpha x from them (sde_drift_terms).  Every step is then a fixed linear combination of at most four
+    tensors plus a multiple of a standard-normal draw: one ops.sde_combine launch between two model evaluations, with coefficients computed
+    here in f64 from the f32 grid values, rounded once to f32 and passed by value.  The loop reads nothing back from the device.
+
+    seed / noise / keep_trajectory: the draw of step k of call number c is normal(seed, (c << 32) | k), generated inside the kernel;
+    noise(k, shape) -> tensor replaces it; keep_trajectory=False updates two buffers in place and returns only the last state."""
+
+    def __init__(self, drift, diffusion, *, t0, t1, num_steps, sampler_type, seed=0, noise=None, keep_trajectory=True):
+        assert t0 < t1, "SDE sampler has to be in forward time"
+        if sampler_type not in SDE_METHODS:
+            raise NotImplementedError(f"ldmae_amd: SDE samplers Euler / Heun only, got {sampler_type!r}")
+        if num_steps < 2:
+            raise ValueError(f"ldmae_amd sde: num_steps must be at least 2, got {num_steps}")
+        self.num_timesteps = num_steps
+        self.t = th.linspace(t0, t1, num_steps)
+        self.dt = self.t[1] - self.t[0]
+        self.drift, self.diffusion, self.sampler_type = drift, diffusion, sampler_type
+        self.seed, self.noise, self.keep_trajectory = seed, noise, keep_trajectory
+        self.calls = 0
+        self.plan = [self.step_coefficients(k) for k in range(num_steps - 1)]       # raises here, not mid-loop, on a singular grid
+
+    def step_coefficients(self, k):
+        """The f32 coefficients of step k as a dict.  Euler: x' = cx x + cv v + cz z.  Heun: xhat = x + cz z; xp = px xhat + pv v1;
+        x' = cx xhat + cv1 v1 + cxp xp + cv2 v2, with v1 = model(xhat, t), v2 = model(xp, t2), t2 = t + dt in f32 as the reference adds it."""
+        import math
+        import numpy as np
+        t, dt = float(self.t[k]), float(self.dt)
+        w = self.diffusion(t)
+        al, be = sde_drift_terms(t, w)
+        c = {"t": t, "t_next": float(self.t[k + 1]), "cz": _f32(math.sqrt(2 * w * dt), f"sqrt(2 w dt) at t = {t}")}
+        if self.sampler_type == "Euler":
+            c.update(cx=_f32(1 - dt * al, f"1 - dt alpha at t = {t}"), cv=_f32(dt * be, f"dt beta at t = {t}"))
+            return c
+        t2 = float(np.float32(t) + np.float32(dt))
+        al2, be2 = sde_drift_terms(t2, self.diffusion(t2))
+        c.update(t2=t2, px=_f32(1 - dt * al, f"1 - dt alpha at t = {t}"), pv=_f32(dt * be, f"dt beta at t = {t}"),
+                 cx=_f32(1 - dt / 2 * al, f"1 - dt/2 alpha at t = {t}"), cv1=_f32(dt / 2 * be, f"dt/2 beta at t = {t}"),
+                 cxp=_f32(-dt / 2 * al2, f"dt/2 alpha at t = {t2}"), cv2=_f32(dt / 2 * be2, f"dt/2 beta at t = {t2}"))
+        return c
+
+    def sample(self, init, model, **model_kwargs):
+        """The num_steps - 1 states after each step, as a list (the reference's return value), or [last state] with keep_trajectory=False."""
+        from .. import ops
+        if not init.is_cuda:
+            raise RuntimeError("ldmae_amd sde: the draw and the step are HIP kernels: the state must be on a HIP device (no CPU fallback); got "
+                               + str(init.device))
+        call, self.calls = self.calls, self.calls + 1
+        shape, dev = init.shape, init.device
+        x = init.float().contiguous()
+        if not self.keep_trajectory:
+            x = x.clone() if x.data_ptr() == init.data_ptr() else x              # updated in place below: never the caller's tensor
+        tvec = th.full((shape[0],), self.plan[0]["t"], dtype=th.float32, device=dev)
+        heun = self.sampler_type == "Heun"
+        xp = th.empty_like(x) if heun else None
+        xhat = th.empty_like(x) if heun and self.keep_trajectory else None
+
+        def f(xin):
+            return self.drift(xin, tvec, model, **model_kwargs).float().contiguous()
+
+        def draw(k):
+            """Keyword arguments of the noise term of step k: a given tensor, or the (seed, counter) of the inline draw."""
+            if self.noise is not None:
+                z = self.noise(k, shape).to(device=dev, dtype=th.float32).contiguous()
+                if z.shape != shape:
+                    raise ValueError(f"ldmae_amd sde: noise({k}, {tuple(shape)}) returned shape {tuple(z.shape)}")
+                return {"z": z}
+            return {"seed": self.seed, "counter": (call << 32) | k}
+
+        samples = []
+        with th.no_grad():
+            for k, c in enumerate(self.plan):
+                out = th.empty_like(x) if self.keep_trajectory else x
+                if not heun:
+                    v = f(x)
+                    ops.sde_combine((x, v), (c["cx"], c["cv"]), out, noise_coef=c["cz"], t_next=c["t_next"], t_out=tvec, **draw(k))
+                else:
+                    xh = xhat if self.keep_trajectory else x
+                    ops.sde_combine((x,), (1.0,), xh, noise_coef=c["cz"], **draw(k))
+                    v1 = f(xh)
+                    ops.sde_combine((xh, v1), (c["px"], c["pv"]), xp, t_next=c["t2"], t_out=tvec)
+                    v2 = f(xp)
+                    ops.sde_combine((xh, v1, xp, v2), (c["cx"], c["cv1"], c["cxp"], c["cv2"]), out, t_next=c["t_next"], t_out=tvec)
+                x = out
+                if self.keep_trajectory:
+                    samples.append(x)
+        return samples if self.keep_trajectory else [x]

@@ -6,7 +6,7 @@ import numpy as np
 import torch as th
 
 from . import path
-from .integrators import ode
+from .integrators import ode, sde, sde_drift_terms, SDE_METHODS, _f32
 from .utils import mean_flat
 
 
@@ -45,10 +45,14 @@ class Transport:
 
     def check_interval(self, train_eps, sample_eps, *, diffusion_form="SBDM", sde=False, reverse=False, eval=False,
                        last_step_size=0.0):
-        """transport.py:84-111 for the velocity model on the linear path: the whole unit interval."""
+        """transport.py:84-111 for the velocity model on the linear path: the whole unit interval, except for the SDE sampler, which starts at
+        eps under the SBDM diffusion (infinite at t = 0) and stops one last step short of 1 (at 1 - eps when last_step_size is 0)."""
+        t0, t1 = 0, 1
         if sde:
-            raise NotImplementedError("ldmae_amd Transport: SDE sampling is out of scope (SURVEY.md 2.1 #7)")
-        return (1, 0) if reverse else (0, 1)
+            eps = sample_eps if eval else train_eps
+            t0 = eps if diffusion_form == "SBDM" else 0
+            t1 = 1 - eps if last_step_size == 0 else 1 - last_step_size
+        return (1 - t0, 1 - t1) if reverse else (t0, t1)
 
     def sample_logit_normal(self, mu, sigma, size=1):
         """transport.py:113-123.  The reference calls scipy.stats.norm.rvs with no random_state, i.e.
@@ -114,7 +118,7 @@ class Transport:
 
 
 class Sampler:
-    """transport.py:270-502, ODE sampler and likelihood evaluation (the SDE sampler is out of scope, SURVEY.md 2.1 #7)."""
+    """transport.py:270-502: the ODE sampler, the SDE sampler and likelihood evaluation."""
 
     def __init__(self, transport):
         self.transport = transport
@@ -127,8 +131,82 @@ class Sampler:
         return ode(drift=drift, t0=t0, t1=t1, sampler_type=sampling_method, num_steps=num_steps, atol=atol, rtol=rtol,
                    timestep_shift=timestep_shift).sample
 
-    def sample_sde(self, **_):
-        raise NotImplementedError("ldmae_amd Sampler: SDE sampling is out of scope (SURVEY.md 2.1 #7); run_inference.sh uses sample_ode")
+    def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04,
+                   num_steps=250, seed=0, noise=None, keep_trajectory=True):
+        """transport.py:336-396: a function (init, model, **model_kwargs) -> the list of the num_steps states after each step, the last one
+        produced by `last_step` at t1 (None / "Mean" / "Tweedie" / "Euler"); with keep_trajectory=False a list holding only that last state.
+        Euler-Maruyama or Heun (integrators.sde) under the diffusion coefficient w(t) = path.diffusion(t, diffusion_form, diffusion_norm).
+
+        Where this departs from the reference: the network runs ONCE per drift evaluation (the reference's drift(x, t) + w score(x, t) calls it
+        twice; for a velocity model on the linear path the score is affine in (v, x), so the SDE drift is beta v - alpha x, sde_drift_terms);
+        every step is one HIP launch with host-computed coefficients; and the noise is a named draw: step k of call number c of the returned
+        function draws normal(seed, (c << 32) | k) (Philox4x32-10, generated inside the step kernel), so a sample is a function of
+        (init, seed, call index).  fn.calls is that call index: readable and resettable.  noise(k, shape) -> tensor replaces the draw (tests).
+
+        The default form SBDM is infinite at t = 0, and a Transport from create_transport has sample_eps = 0, so t0 = 0: the reference then
+        returns non-finite samples; here that combination is refused when the sampler is built."""
+        if sampling_method not in SDE_METHODS:
+            raise NotImplementedError(f"ldmae_amd Sampler: SDE sampling_method {sampling_method!r} is not supported: 'Euler' or 'Heun'")
+        if diffusion_form not in path.DIFFUSION_FORMS:
+            raise NotImplementedError(f"ldmae_amd Sampler: diffusion_form {diffusion_form!r} is not supported: one of "
+                                      + ", ".join(repr(f) for f in path.DIFFUSION_FORMS))
+        if last_step not in (None, "Mean", "Tweedie", "Euler"):
+            raise NotImplementedError(f"ldmae_amd Sampler: last_step {last_step!r} is not supported: None, 'Mean', 'Tweedie' or 'Euler'")
+        if last_step is None:
+            last_step_size = 0.0
+        t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, diffusion_form=diffusion_form, sde=True,
+                                               eval=True, reverse=False, last_step_size=last_step_size)
+        if diffusion_form == "SBDM" and not t0:
+            raise NotImplementedError("ldmae_amd Sampler: SDE sampling is out of scope for diffusion_form='SBDM' with t0 == 0: the SBDM diffusion "
+                                      "(1-t)^2 / t + (1-t) is infinite there and the samples would not be finite.  Build the Transport with "
+                                      "sample_eps > 0 (create_transport forces 0 for the velocity model; in the YAML driver set "
+                                      "transport.sample_eps), or choose another diffusion_form, e.g. 'sigma' (SURVEY.md 2.1 #7)")
+
+        def w(t):
+            return path.diffusion(t, diffusion_form, diffusion_norm)
+
+        _sde = sde(self.drift, w, t0=t0, t1=t1, num_steps=num_steps, sampler_type=sampling_method, seed=seed, noise=noise,
+                   keep_trajectory=keep_trajectory)
+        # the last step at t1 (f32, as the reference's th.ones * t1): x' = lx x + lv v
+        tl, s = float(_sde.t[-1]), float(last_step_size)
+        if last_step == "Mean":
+            al, be = sde_drift_terms(tl, w(tl))
+            last = (_f32(1 - s * al, "1 - s alpha at t1"), _f32(s * be, "s beta at t1"))
+        elif last_step == "Tweedie":                       # x / t + (1-t)^2 / t score, score = a v + b x
+            a, b = path.score_from_velocity(tl)
+            last = (_f32(1 / tl + (1 - tl) ** 2 / tl * b, "the Tweedie x coefficient"), _f32((1 - tl) ** 2 / tl * a, "the Tweedie v coefficient"))
+        elif last_step == "Euler":
+            last = (1.0, _f32(s, "last_step_size"))
+        else:
+            last = None
+
+        def _sample(init, model, **model_kwargs):
+            from .. import ops
+            if not init.is_cuda:
+                raise RuntimeError("ldmae_amd sample_sde: the draw and the steps are HIP kernels: the state must be on a HIP device (no CPU "
+                                   "fallback); got " + str(init.device))
+            _sde.calls = _sample.calls
+            xs = _sde.sample(init, model, **model_kwargs)
+            _sample.calls = _sde.calls
+            x = xs[-1]
+            if last is not None:
+                with th.no_grad():
+                    ts = th.full((x.size(0),), tl, dtype=th.float32, device=x.device)
+                    v = self.drift(x, ts, model, **model_kwargs).float().contiguous()
+                    x = ops.sde_combine((x, v), last, x if not keep_trajectory else th.empty_like(x))
+            if not keep_trajectory:
+                return [x]
+            xs.append(x)
+            assert len(xs) == num_steps, "Samples does not match the number of steps"
+            return xs
+
+        _sample.calls = 0
+        _sample.sde = _sde
+        _sample.options = dict(sampling_method=sampling_method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm, last_step=last_step,
+                               last_step_size=last_step_size, num_steps=num_steps, seed=seed, keep_trajectory=keep_trajectory)
+        _sample.last_coefficients = last
+        _sample.model_calls = (num_steps - 1) * (2 if sampling_method == "Heun" else 1) + (last is not None)
+        return _sample
 
     def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, seed=0, noise=None):
         """transport.py:445-502: a function (x, model, **model_kwargs) -> (logp, z).  The probability-flow ODE is integrated from data to noise
