@@ -3,9 +3,12 @@
 // gather / scatter, affine LayerNorm and exact-erf GELU.
 #include "common.h"
 
-// order-preserving map f32 -> u32 (handles negatives; noise is in [0,1) but be general)
+// order-preserving map f32 -> u32 (handles negatives; noise is in [0,1) but be general).  -0.0 and +0.0 compare equal in the stable argsort
+// this restates, so both get the key of +0.0 (an integer compare-and-select: `+ 0.0f` could be folded away).  NaN noise is out of scope:
+// its key follows the bit pattern, not numpy's "NaN sorts last".
 __device__ __forceinline__ unsigned f32_ordered(float f) {
   unsigned u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;                        // -0.0 -> +0.0
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

@@ -67,7 +67,7 @@ __device__ __forceinline__ f32x16 zero16() {
   for (int t = 0; t < 16; ++t) o[t] = 0.f;
   return o;
 }
-// exact-erf GELU with erf by Abramowitz-Stegun 7.1.26 (common.h: erf_as -- the bf16 per-layer kernels use the same function)
+// exact-erf GELU (common.h: gelu_act, erff -- the bf16 per-layer kernels use the same function)
 __device__ __forceinline__ float gelu_erf(float y) { return gelu_act<bf16>(y); }
 }  // namespace
 

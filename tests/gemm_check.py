@@ -18,7 +18,8 @@ rounding to a 16-bit output adds at most half an ulp of the stored value, whose 
 
 Nonlinear epilogues are checked in two steps: the stored pre-activation (pre, h12) with the bound above, then the activation output
 against the f64 activation of what the kernel fed it, allowing 1 ulp of the output, the documented approximation error of the device
-functions in csrc/common.h (erf_as: Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7; erff: 2 ulp; fast_sigmoid: __expf and a
+functions in csrc/common.h (16-bit GELU: 1.5e-7, the figure stated for the Abramowitz-Stegun erf these types used before erf_act
+became erff for every type -- erff meets it; erff: 2 ulp; fast_sigmoid: __expf and a
 reciprocal, 1 ulp each plus the rounding of the exponent argument), and -- where the kernel applies the activation to the UNROUNDED f32
 value but stores the pre-activation rounded -- the slope of the activation times half an ulp of the pre-activation.
 """
@@ -30,7 +31,7 @@ import torch
 
 U = 2.0 ** -24          # unit roundoff of f32
 C_ACC = 2.0             # see the module docstring
-ERF_AS = 1.5e-7         # csrc/common.h erf_as (A-S 7.1.26)
+ERF_AS = 1.5e-7         # erf of the 16-bit GELU epilogues (stated for the former A-S 7.1.26 evaluation; erff, which they call now, meets it)
 ERF_LIBM = 2 * 2.0 ** -24   # erff: 2 ulp of a value in [-1, 1]
 
 # (explicit mantissa bits, smallest normal exponent; subnormals share its spacing)
