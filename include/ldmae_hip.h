@@ -273,6 +273,25 @@ int ldmae_patch_gather(int tok_dtype, const float* img, const long long* ids, co
  * plain latent [B, C, HW] and noise is ignored.  lat_mean / lat_std [C] (latents_stats.pt) or both NULL (latent_norm off).  HW % 4 == 0. */
 int ldmae_latent_prologue(const float* moments, const float* noise, const float* lat_mean, const float* lat_std, float multiplier,
                           float* out, int B, int C, int HW, int sample, void* stream);
+/* Training transform of the packed image input on the device, per batch (datasets/packed_images.py; the host counterpart is
+ * vmae_pretrain.RandomResizedCropFlip per item): crop, antialiased bicubic resize to S x S, horizontal flip, ToTensor and Normalize in one launch.
+ * SOURCE.  Sample b reads the ch x cw crop at (top, left) of the h x w x 3 uint8 image (HWC, rows of 3 w bytes, no padding) at blob + offset[b];
+ *   offset [B] i64 and geom [B, 8] i32 = (h, w, top, left, ch, cw, flip, 0) are DEVICE tables.  Any byte offset is accepted.
+ * RESAMPLING.  PIL's crop(box).resize((S, S), BICUBIC): separable, horizontal pass then vertical, Keys cubic with a = -0.5, antialiased.  Per axis,
+ *   input size n (cw, then ch): scale = n / S, fs = max(scale, 1), support = 2 fs; output index i has center = (i + 0.5) scale, taps
+ *   x in [max(int(center - support + 0.5), 0), min(int(center + support + 0.5), n)) and weights cubic((x - center + 0.5) / fs) divided by their sum.
+ *   Taps are clipped at the CROP BOX, not at the image: a pixel outside the box has no influence.  The tap count grows with scale without limit.
+ * ARITHMETIC.  f32 throughout.  Tap bounds and the numerator / denominator of a weight's argument are formed in integers (exact), the argument
+ *   is their f32 quotient; weights are normalised by their f32 sum taken in ascending tap order; each output is an ascending fma chain.  The
+ *   horizontal result is clamped to [0, 255], then the vertical result is; nothing is rounded to integers (PIL rounds to 8 bits after each pass:
+ *   the result differs from PIL's by at most (0.5 sum|w_v| + 0.5) / 255 of the pixel range).  out = (v / 255 - mean) / std
+ *   with true divisions, each operation rounded once; out_bf16 = 1 stores that f32 value rounded to nearest even.  flip != 0 mirrors the columns.
+ * MEMORY.  Only bytes inside [blob, blob + blob_bytes) are read: the kernel trusts its tables (ops.crop_resize_flip checks the host copy), and a
+ *   row that fails the range check (box outside the image, image outside the blob, a crop side above 16384, h or w above 2^24) leaves its sample unwritten.  out
+ *   [B, 3, S, S] f32 or bf16.  No atomics; the grid is a function of (B, S) alone; two launches give the same bits.
+ * LDMAE_ERR_INVALID: B < 1, S < 1 or S > 16384, std == 0, a null pointer, an empty blob. */
+int ldmae_crop_resize_flip_u8(const unsigned char* blob, long blob_bytes, const long* offset, const int* geom, void* out, int out_bf16, int B,
+                              int S, float mean, float std, void* stream);
 /* out[n,j,:] = x[n, ids[n,j], :]  (torch.gather on dim 1, :486); bwd scatters (ids unique per n) */
 int ldmae_gather_rows(const float* x, const long long* ids, float* out, int N, int L, int keep, int D, void* stream);
 int ldmae_scatter_rows(const float* dout, const long long* ids, float* dx, int N, int L, int keep, int D, void* stream);

@@ -933,6 +933,55 @@ def latent_prologue(moments, noise=None, lat_mean=None, lat_std=None, multiplier
     return out
 
 
+def check_crop_table(offsets, geom, blob_bytes):
+    """The range checks ldmae_crop_resize_flip_u8 leaves to its caller, on the HOST copy of the tables: offsets [B] i64, geom [B, 8] i32 =
+    (h, w, top, left, ch, cw, flip, 0).  Raises ValueError naming the first bad sample."""
+    if geom.dim() != 2 or geom.shape[1] != 8:
+        raise ValueError(f"crop_resize_flip: geom must be [B, 8] (h, w, top, left, ch, cw, flip, 0), got {tuple(geom.shape)}")
+    if offsets.dim() != 1 or offsets.shape[0] != geom.shape[0] or geom.shape[0] < 1:
+        raise ValueError(f"crop_resize_flip: offsets {tuple(offsets.shape)} does not go with geom {tuple(geom.shape)}")
+    g, off = geom.to(torch.int64), offsets.to(torch.int64)
+    h, w, top, left, ch, cw = (g[:, i] for i in range(6))
+    checks = (((h < 1) | (w < 1), "an empty image"), ((ch < 1) | (cw < 1), "an empty crop box (ch, cw >= 1)"),
+              ((top < 0) | (left < 0) | (top + ch > h) | (left + cw > w), "a crop box that leaves the image"),
+              ((ch > 16384) | (cw > 16384), "a crop side above 16384"),
+              ((off < 0) | (off + 3 * h * w > int(blob_bytes)), f"an image that ends past the blob ({int(blob_bytes)} bytes)"))
+    for bad, what in checks:
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0])
+            raise ValueError(f"crop_resize_flip: sample {b} has {what}: offset {int(off[b])}, geom {geom[b].tolist()}")
+
+
+def crop_resize_flip(blob, offsets, geom, S, mean=0.5, std=0.5, out_dtype=torch.float32, out=None):
+    """RandomResizedCrop's resample + flip + ToTensor + Normalize of a batch of packed uint8 images in one launch (ldmae_crop_resize_flip_u8):
+    blob uint8 [n] on the device; offsets [B] i64 and geom [B, 8] i32 -> [B, 3, S, S] f32 or bf16.  HOST tables are checked (check_crop_table) and
+    uploaded here; DEVICE tables are used as they are -- the kernel trusts them, so their host copy must have gone through check_crop_table
+    (datasets/packed_images.py does that before its own upload)."""
+    if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
+        raise ValueError("crop_resize_flip: blob must be a contiguous 1-D uint8 tensor")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"crop_resize_flip: out_dtype {out_dtype} (float32 or bfloat16)")
+    if int(S) < 1 or float(std) == 0.0:
+        raise ValueError(f"crop_resize_flip: S={S} must be positive and std={std} non-zero")
+    if not offsets.is_cuda or not geom.is_cuda:
+        if offsets.is_cuda or geom.is_cuda:
+            raise ValueError("crop_resize_flip: offsets and geom must both be host tensors or both device tensors")
+        check_crop_table(offsets, geom, blob.numel())
+        offsets, geom = offsets.to(blob.device, torch.int64), geom.to(blob.device, torch.int32)
+    elif geom.dim() != 2 or geom.shape[1] != 8 or offsets.shape != geom.shape[:1]:
+        raise ValueError(f"crop_resize_flip: geom must be [B, 8] and offsets [B], got {tuple(geom.shape)} and {tuple(offsets.shape)}")
+    if offsets.dtype != torch.int64 or geom.dtype != torch.int32 or not offsets.is_contiguous() or not geom.is_contiguous():
+        raise ValueError("crop_resize_flip: device tables must be contiguous int64 offsets and int32 geom")
+    B = geom.shape[0]
+    if out is None:
+        out = torch.empty(B, 3, S, S, dtype=out_dtype, device=blob.device)
+    elif out.shape != (B, 3, S, S) or out.dtype != out_dtype or not out.is_contiguous() or out.device != blob.device:
+        raise ValueError(f"crop_resize_flip: out must be a contiguous {out_dtype} [{B}, 3, {S}, {S}] tensor on {blob.device}")
+    call("ldmae_crop_resize_flip_u8", ptr(blob), blob.numel(), ptr(offsets), ptr(geom), ptr(out), 1 if out_dtype == torch.bfloat16 else 0,
+         B, int(S), float(mean), float(std), stream())
+    return out
+
+
 def gather_rows(x, ids):
     N, Lq, D = x.shape
     keep = ids.shape[1]

@@ -17,6 +17,9 @@ cd "$(dirname "$0")" || exit 1
 stage1=(--batch_size 128 --no_cls --accum_iter 2 --num_workers 12 --smooth_output --fixed_std 1e-3 --model mae_for_ldmae_f8d16_prev --input_size 128
         --mask_ratio 0.25 --visible_loss_ratio 0.75 --epochs 400 --warmup_epochs 10 --blr 1.0e-4 --weight_decay 0.05 --kl_loss_weight 1e-6 --precision fp16
         --data_path "$DATA_PATH" --output_dir "$OUT" --log_dir "$OUT")
+# PACKED_DATA_128 / PACKED_DATA_256: packs of DATA_PATH written by `python -m ldmae_amd.pack_images` (--short_side 160 / 320: README) -- the
+# training transform then runs on the device (vmae_pretrain.py --packed_data) instead of in DataLoader workers; unset = the image folder as before
+[ -n "$PACKED_DATA_128" ] && stage1+=(--packed_data "$PACKED_DATA_128")
 echo "Stage 1: VMAE pre-training (128 x 128, mask ratio 0.25)"
 python -m torch.distributed.run --nproc-per-node "$GPUS_PER_NODE" --nnodes 1 --node-rank 0 --master-addr 127.0.0.1 vmae_pretrain.py "${stage1[@]}" "$@" || exit 1
 
@@ -27,6 +30,7 @@ OUT3=${OUT3:-./work_dir/vmae}
 stage3=(--no_cls --tune_decoder --perceptual_loss_ratio 10.0 --batch_size 16 --accum_iter 16 --smooth_output --num_workers 12 --model mae_for_ldmae_f8d16_prev
         --input_size 256 --mask_ratio 0.0 --visible_loss_ratio 0.5 --epochs 10 --save_epochs 1 --warmup_epochs 0 --blr 1.0e-5 --weight_decay 0.05 --kl_loss_weight 0.0
         --precision fp16 --data_path "$DATA_PATH" --output_dir "$OUT3" --log_dir "$OUT3" --resume "$OUT/checkpoint-90.pth")
+[ -n "$PACKED_DATA_256" ] && stage3+=(--packed_data "$PACKED_DATA_256")
 [ -n "$LPIPS_VGG" ] && stage3+=(--lpips_vgg "$LPIPS_VGG")
 [ -n "$LPIPS_LIN" ] && stage3+=(--lpips_lin "$LPIPS_LIN")
 # LPIPS_PRECISION=fp16: the VGG in 16 bits (fp16 forward, bf16 data gradient; models/lpips.py); default f32 = exact

@@ -6,6 +6,8 @@ checkpoint save / resume with the position-embedding resize (VMAE/util/misc.py:4
     python ldmae_amd/vmae_pretrain.py --data_path /data/imagenet --output_dir out --batch_size 64          # <data_path>/train/<class>/*.JPEG
     python ldmae_amd/vmae_pretrain.py --data_path /data/my_pngs --output_dir out                          # any tree of images
     python -m torch.distributed.run --nproc-per-node 8 ldmae_amd/vmae_pretrain.py --data_path ...          # one rank per GPU over RCCL
+    python ldmae_amd/vmae_pretrain.py --packed_data /data/imagenet_160 --input_size 128 --output_dir out    # a pack of `python -m ldmae_amd.pack_images`: the
+                                                                    # crop / resize / flip / normalise transform runs on the device (datasets/packed_images.py)
     python ldmae_amd/vmae_pretrain.py --synthetic --epochs 1 --steps-per-epoch 10 --batch_size 64
     python ldmae_amd/vmae_pretrain.py --tune_decoder --perceptual_loss_ratio 10.0 --mask_ratio 0.0 --input_size 256 --batch_size 16 --accum_iter 16 \
         --kl_loss_weight 0.0 --resume out/checkpoint-90.pth --lpips_vgg vgg16-397923af.pth --lpips_lin vgg.pth --data_path ...     # stage 3
@@ -224,15 +226,17 @@ class RandomResizedCropFlip:
     def __init__(self, size, scale=(0.75, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
         self.size, self.scale, self.ratio = int(size), scale, ratio
 
-    def _box(self, w, h):
+    def _box(self, w, h, generator=None):
+        """-> (top, left, ch, cw).  generator: a torch.Generator for the draws (datasets/packed_images.py); None = the global RNG."""
         area = w * h
         lr = (math.log(self.ratio[0]), math.log(self.ratio[1]))
+        u = torch.empty(1)                  # one buffer for the draws (the same values as a fresh tensor per draw, at half the host time)
         for _ in range(10):
-            ta = area * float(torch.empty(1).uniform_(self.scale[0], self.scale[1]))
-            ar = math.exp(float(torch.empty(1).uniform_(lr[0], lr[1])))
+            ta = area * u.uniform_(self.scale[0], self.scale[1], generator=generator).item()
+            ar = math.exp(u.uniform_(lr[0], lr[1], generator=generator).item())
             cw, ch = int(round(math.sqrt(ta * ar))), int(round(math.sqrt(ta / ar)))
             if 0 < cw <= w and 0 < ch <= h:
-                return int(torch.randint(0, h - ch + 1, (1,))), int(torch.randint(0, w - cw + 1, (1,))), ch, cw
+                return int(torch.randint(0, h - ch + 1, (1,), generator=generator)), int(torch.randint(0, w - cw + 1, (1,), generator=generator)), ch, cw
         r = w / h
         if r < self.ratio[0]:
             cw, ch = w, int(round(w / self.ratio[0]))
@@ -286,6 +290,9 @@ def get_dataset(args):
     """main_pretrain.py:111-192: 'imagenet' in the path -> ImageFolder(<path>/train) with the random-resized-crop transform; 'laion' -> the same
     transform over the image tree (the reference's HuggingFace 'imagefolder' loader falls back to exactly that); anything else -> the
     tree resized to a square."""
+    if getattr(args, "packed_data", ""):
+        from ldmae_amd.datasets.packed_images import PackedImages
+        return PackedImages(args.packed_data)
     if args.synthetic:
         return _SyntheticImages(args.batch_size * args.steps_per_epoch * max(1, int(os.environ.get("WORLD_SIZE", 1))), args.input_size)
     if "imagenet" in args.data_path:
@@ -392,6 +399,8 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--steps-per-epoch", type=int, default=100)
     ap.add_argument("--data_path", default="", help="'imagenet' in the path: <path>/train/<class>/<image>; otherwise any tree of images")
+    ap.add_argument("--packed_data", default="", help="a pack written by `python -m ldmae_amd.pack_images` (replaces --data_path): uint8 shards, the random-resized-crop "
+                    "/ flip / normalise transform runs on the device, one kernel per batch (datasets/packed_images.py)")
     ap.add_argument("--output_dir", default="./output_dir")
     ap.add_argument("--save_epochs", type=int, default=10)
     ap.add_argument("--resume", default="")
@@ -424,8 +433,20 @@ def parse_args(argv=None):
     ap.add_argument("--dist_url", default="env://", help="accepted and ignored")
     ap.add_argument("--pin_mem", action="store_true", dest="pin_mem_flag", help="accepted (pinning is the default here; --no_pin_mem turns it off)")
     args = ap.parse_args(argv)
-    if not args.synthetic and not args.data_path:
-        ap.error("--data_path (an image folder) or --synthetic")
+    if not args.synthetic and not args.data_path and not args.packed_data:
+        ap.error("--data_path (an image folder), --packed_data (a pack of one) or --synthetic")
+    if args.packed_data:
+        if args.synthetic:
+            ap.error("--packed_data and --synthetic exclude each other")
+        import json
+        from ldmae_amd.pack_images import INDEX, META
+        if not os.path.exists(os.path.join(args.packed_data, INDEX)) or not os.path.exists(os.path.join(args.packed_data, META)):
+            ap.error(f"--packed_data {args.packed_data} is not a pack (no {INDEX} / {META}): write one with `python -m ldmae_amd.pack_images`")
+        with open(os.path.join(args.packed_data, META)) as f:
+            short = int(json.load(f)["short_side"])
+        if short < args.input_size:
+            ap.error(f"--packed_data {args.packed_data} was packed with --short_side {short}, smaller than --input_size {args.input_size}: every crop would be "
+                     f"upscaled; re-pack with --short_side {args.input_size * 5 // 4} or more")
     stage3 = args.tune_decoder and args.perceptual_loss_ratio is not None
     refused = [n for n in ("pred_with_conv", "gradual_resol") if getattr(args, n)]
     if not stage3:
@@ -472,7 +493,11 @@ def main(argv=None):
     log(f"actual lr: {args.lr:.2e}  accumulate grad iterations: {args.accum_iter}  effective batch size: {eff}")
     dataset = get_dataset(args)
     sampler = torch.utils.data.DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True)    # :204-207
-    if args.synthetic:
+    if args.packed_data:
+        # uint8 shards: a thread stages each batch, one kernel crops / resizes / flips / normalises it on the device (no worker processes)
+        from ldmae_amd.datasets.packed_images import PackedBatchLoader
+        loader = PackedBatchLoader(dataset, sampler, args.batch_size, args.input_size, args.seed, torch.device("cuda", local))
+    elif args.synthetic:
         # device-resident batches (the kernels' own speed, not the host's: collating 256 x 3 x 256 x 256 floats per step kept the GPU idle 90 % of the time)
         loader = _SyntheticLoader(args.steps_per_epoch, args.batch_size, args.input_size, args.seed + rank)
     else:
