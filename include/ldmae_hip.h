@@ -143,6 +143,22 @@ int ldmae_rmsnorm_modulate_bwd_gate(int dtype, const void* dout, const float* x,
                                     const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, float* dw,
                                     float beta_w, const void* y, const float* gate, int gate_ld, void* dy, float* dgate, int dgate_ld,
                                     float* dbias, int M, int D, int rows_per_batch, float* workspace, void* stream);
+/* ldmae_rmsnorm_modulate_bwd_gate for a norm whose input row was never stored (the forward ran ldmae_res_rmsnorm_modulate_fwd): `x` is the
+ * residual stream BEFORE the gated residual under the norm, and the row that was normalised is rebuilt in registers as x + gate[b] * y from
+ * the y and gate the pass reads anyway.  Every output is bitwise what ldmae_rmsnorm_modulate_bwd_gate gives with that row materialised.
+ * dtype LDMAE_BF16 only; workspace: ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes. */
+int ldmae_rmsnorm_modulate_bwd_gate_recompute(int dtype, const void* dout, const float* x, const float* w, const float* scale, int mod_ld,
+                                              const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld,
+                                              float* dw, float beta_w, const void* y, const float* gate, int gate_ld, void* dy, float* dgate,
+                                              int dgate_ld, float* dbias, int M, int D, int rows_per_batch, float* workspace, void* stream);
+/* The gated residual(s) of a block and the norm behind them in one pass over the rows (lightningdit.py:248-249): r = x + gate_a[b] * ya, and
+ * r += gate_b[b] * yb when yb / gate_b are given; ya / yb are Linear outputs AS STORED in `dtype` (LDMAE_BF16 or LDMAE_F16), the gates [batch,
+ * gate_ld] f32 views.  xout (optional, f32, not x) = r; out (optional, `dtype`) / rstd (optional) = ldmae_rmsnorm_modulate_fwd of r.  At least
+ * one of xout / out.  Bitwise the LDMAE_EPI_GATE_RES epilogue (per residual) followed by ldmae_rmsnorm_modulate_fwd, without the f32 round
+ * trip between them.  Every tensor 16-byte aligned, D % 4 == 0, M % rows_per_batch == 0. */
+int ldmae_res_rmsnorm_modulate_fwd(int dtype, const float* x, const void* ya, const float* gate_a, int gate_a_ld, const void* yb,
+                                   const float* gate_b, int gate_b_ld, float* xout, const float* w, const float* shift, const float* scale,
+                                   int mod_ld, void* out, float* rstd, int M, int D, int rows_per_batch, float eps, void* stream);
 /* The three entry points above for blocks built with use_rmsnorm=False: nn.LayerNorm(hidden, elementwise_affine=False, eps=1e-6) + modulate
  * (lightningdit.py:200-201,257; modulate :26-30).  y = (x - mean) * rstd * (1 + scale[b]) + shift[b]; rstd [M] = rsqrt(var + eps) is saved, the
  * backward recomputes the row mean from x.  No weight, no weight gradient; workspaces: ldmae_rmsnorm_modulate_bwd(_gate)_workspace_bytes. */

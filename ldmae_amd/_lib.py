@@ -45,6 +45,9 @@ SIGNATURES = {
     "ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes": (_l, [_i, _i, _i]),
     "ldmae_rmsnorm_modulate_bwd_gate": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _f, _vp, _vp, _i, _vp, _vp, _i, _vp,
                                              _i, _i, _i, _vp, _vp]),
+    "ldmae_rmsnorm_modulate_bwd_gate_recompute": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _f, _vp, _vp, _i, _vp, _vp, _i,
+                                                       _vp, _i, _i, _i, _vp, _vp]),
+    "ldmae_res_rmsnorm_modulate_fwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
     "ldmae_qknorm_rope_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "ldmae_qknorm_rope_bwd_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "ldmae_qknorm_rope_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _f, _vp, _vp]),

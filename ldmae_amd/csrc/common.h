@@ -173,6 +173,12 @@ __device__ __forceinline__ float4 rope_apply(float4 t, float4 c, float4 s) {
   return make_float4(t.x * c.x - t.y * s.x, t.y * c.y + t.x * s.y, t.z * c.z - t.w * s.z, t.w * c.w + t.z * s.w);
 }
 
+// The gated residual x + gate * y on four adjacent channels, y AS STORED in the activation type (already widened to f32).  One definition
+// for the GEMM epilogues of gemm_nt_common.h and the residual + norm row kernels of elementwise.hip: they agree bit for bit.
+__device__ __forceinline__ float4 gate_res4(float4 x, float4 g, float4 y) {
+  return make_float4(fmaf(g.x, y.x, x.x), fmaf(g.y, y.y, x.y), fmaf(g.z, y.z, x.z), fmaf(g.w, y.w, x.w));
+}
+
 // XCD-aware bijective block remap (8 XCDs, blocks dealt round-robin): consecutive
 // logical tiles land on one XCD so neighbours share that XCD's L2.
 __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {

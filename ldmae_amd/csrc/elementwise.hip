@@ -21,6 +21,10 @@ template <> __device__ __forceinline__ void store4<bf16>(bf16* p, float4 v) {
   bf16x4 o; o[0] = (bf16)v.x; o[1] = (bf16)v.y; o[2] = (bf16)v.z; o[3] = (bf16)v.w;
   __builtin_nontemporal_store(o, (bf16x4*)p);
 }
+template <> __device__ __forceinline__ void store4<f16>(f16* p, float4 v) {
+  f16x4 o; o[0] = from_f<f16>(v.x); o[1] = from_f<f16>(v.y); o[2] = from_f<f16>(v.z); o[3] = from_f<f16>(v.w);
+  *(f16x4*)p = o;
+}
 __device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
 __device__ __forceinline__ float4 operator+(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 operator-(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
@@ -164,13 +168,125 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_kernel(const float* __res
   }
 }
 
+// x^2 + y^2 + z^2 + w^2 with the roundings the GUARDED form of rmsnorm_mod_fwd_kernel has.  Its `ss += hsum(xv * xv)` sits in a loop of
+// conditional loads, one basic block per chunk, and is contracted there as fma(x, x, y * y) + fma(z, z, w * w) -- except with a single chunk
+// (NCH == 1), where the products are formed as a packed multiply and nothing is contracted.  A kernel that forms the row in registers has
+// another block structure and would get another contraction (1 ulp in rstd), so the guarded form of the residual + norm kernel spells the
+// roundings out.  (The unguarded forms of the two kernels have the same structure and compile to the same sequence; both are covered
+// bitwise by tests/test_gpu_resnorm_fused.py.)
+template <bool FMA> __device__ __forceinline__ float sumsq4_guarded(float4 a) {
+#pragma clang fp contract(off)
+  if constexpr (FMA) return fmaf(a.x, a.x, a.y * a.y) + fmaf(a.z, a.z, a.w * a.w);
+  else return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
+}
+
+// The gated residual(s) in front of the norm, formed in registers: r = gate_res4(x, gate_a[b], ya), then r = gate_res4(r, gate_b[b], yb) when
+// yb is given (the second residual of a block, whose first was never stored).  r is written to xout (f32) and / or normalised + modulated into
+// `out` exactly as rmsnorm_mod_fwd_kernel does with a row it loads: same row-to-wave mapping, same order of the sum of squares, same output
+// arithmetic, statement for statement -- xout / out / rstd have the bits of the EPI_GATE_RES epilogue followed by that kernel.  ya / yb are the
+// branch outputs AS STORED in the activation type (what the epilogue adds).  Everything a row needs from HBM is requested before its first use.
+template <int NCH, typename T, bool FULL = false>
+__global__ __launch_bounds__(256) void res_rmsnorm_mod_fwd_kernel(const float* __restrict__ x, const T* __restrict__ ya,
+                                                                  const float* __restrict__ ga, int ga_ld, const T* __restrict__ yb,
+                                                                  const float* __restrict__ gb, int gb_ld, float* __restrict__ xout,
+                                                                  const float* __restrict__ w, const float* __restrict__ shift,
+                                                                  const float* __restrict__ scale, int mod_ld, T* __restrict__ out,
+                                                                  float* __restrict__ rstd, int M, int D, int rpb, float eps) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nch = D >> 2;
+  float4 wv[NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) { const int c = lane + 64 * i; wv[i] = (c < nch && out) ? *(const float4*)(w + 4 * c) : f4(0.f); }
+  if constexpr (FULL) {
+    const int m0 = (blockIdx.x * 4 + wave) * 4, b = m0 / rpb;
+    float4 sc1[NCH], sh[NCH], gav[NCH], gbv[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      sc1[i] = scale ? f4(1.f) + *(const float4*)(scale + (size_t)b * mod_ld + 4 * lane + 256 * i) : f4(1.f);
+      sh[i] = shift ? *(const float4*)(shift + (size_t)b * mod_ld + 4 * lane + 256 * i) : f4(0.f);
+      gav[i] = *(const float4*)(ga + (size_t)b * ga_ld + 4 * lane + 256 * i);
+      gbv[i] = yb ? *(const float4*)(gb + (size_t)b * gb_ld + 4 * lane + 256 * i) : f4(0.f);
+    }
+    for (int r = 0; r < 4; ++r) {
+      const int m = m0 + r;
+      const size_t ro = (size_t)m * D + 4 * lane;
+      float4 xv[NCH], yav[NCH], ybv[NCH];
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) xv[i] = *(const float4*)(x + ro + 256 * i);
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) { yav[i] = load4<T>(ya + ro + 256 * i); ybv[i] = yb ? load4<T>(yb + ro + 256 * i) : f4(0.f); }
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        xv[i] = gate_res4(xv[i], gav[i], yav[i]);
+        if (yb) xv[i] = gate_res4(xv[i], gbv[i], ybv[i]);
+        if (xout) *(float4*)(xout + ro + 256 * i) = xv[i];
+      }
+      if (!out) continue;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) ss += hsum(xv[i] * xv[i]);
+      ss = wave_sum(ss);
+      const float rs = rsqrtf(ss / (float)D + eps);
+      if (lane == 0 && rstd) rstd[m] = rs;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        float4 y = (xv[i] * rs) * wv[i];
+        if (scale) y = y * sc1[i];
+        if (shift) y = y + sh[i];
+        store4<T>(out + ro + 256 * i, y);
+      }
+    }
+    return;
+  }
+  for (int r = 0; r < 4; ++r) {
+    const int m = (blockIdx.x * 4 + wave) * 4 + r;
+    if (m >= M) return;
+    const int b = m / rpb;
+    float4 xv[NCH], yav[NCH], ybv[NCH];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = lane + 64 * i;
+      xv[i] = c < nch ? *(const float4*)(x + (size_t)m * D + 4 * c) : f4(0.f);
+      yav[i] = c < nch ? load4<T>(ya + (size_t)m * D + 4 * c) : f4(0.f);
+      ybv[i] = (c < nch && yb) ? load4<T>(yb + (size_t)m * D + 4 * c) : f4(0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nch) {
+        xv[i] = gate_res4(xv[i], *(const float4*)(ga + (size_t)b * ga_ld + 4 * c), yav[i]);
+        if (yb) xv[i] = gate_res4(xv[i], *(const float4*)(gb + (size_t)b * gb_ld + 4 * c), ybv[i]);
+        if (xout) *(float4*)(xout + (size_t)m * D + 4 * c) = xv[i];
+      }
+      ss += sumsq4_guarded<(NCH > 1)>(xv[i]);
+    }
+    if (!out) continue;
+    ss = wave_sum(ss);
+    const float rs = rsqrtf(ss / (float)D + eps);
+    if (lane == 0 && rstd) rstd[m] = rs;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = lane + 64 * i;
+      if (c < nch) {
+        float4 y = (xv[i] * rs) * wv[i];
+        if (scale) y = y * (f4(1.f) + *(const float4*)(scale + (size_t)b * mod_ld + 4 * c));
+        if (shift) y = y + *(const float4*)(shift + (size_t)b * mod_ld + 4 * c);
+        store4<T>(out + (size_t)m * D + 4 * c, y);
+      }
+    }
+  }
+}
+
 // partials P[wg][3][D] = {sum dout, sum dout*y, sum dy*n} over the workgroup's rows (one sample)
 // GATE: the gated-residual backward of the branch BELOW this norm (the attention branch under norm2) rides along: the updated residual
 // gradient is consumed while it is in registers -- dy = dx_new * gate[b] (rounded to T), dgate partials sum dx_new * y, bias-gradient
 // partials sum dy -- instead of being re-read by a separate gate_bwd pass (805 MB per block).  Same arithmetic, same partial layout
 // and same summation order as gate_bwd_kernel.
-struct GateBwdArgs { const void* y; const float* gate; int gate_ld; void* dy; float* Pg; float* Pb; int dx_overwrite; int center; };
-template <int NCH, typename T, bool GATE, bool FULL = false>
+// RECOMP (GATE only): `x` is the residual stream BEFORE the gated residual under this norm and the row that was normalised is rebuilt in
+// registers, gate_res4(x, gate[b], y) -- the very expression that formed it in the forward (res_rmsnorm_mod_fwd_kernel) -- from the y row and
+// the gate constants this kernel reads anyway: that row never has to be stored.  Only the source of the f32 row changes.
+struct GateBwdArgs { const void* y; const float* gate; int gate_ld; void* dy; float* Pg; float* Pb; int dx_overwrite; int center; int recompute; };
+template <int NCH, typename T, bool GATE, bool FULL = false, bool RECOMP = false>
 __global__ __launch_bounds__(256) void rmsnorm_mod_bwd_kernel(const T* __restrict__ dout, const float* __restrict__ x,
                                                               const float* __restrict__ w, const float* __restrict__ scale, int mod_ld,
                                                               const float* __restrict__ rstd, float* __restrict__ dx, float* __restrict__ P,
@@ -215,11 +331,14 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_bwd_kernel(const T* __restric
       const size_t ro = (size_t)m * D + 4 * lane;
       float4 g[NCH], nv[NCH], dold[NCH], yv[GATE ? NCH : 1];
 #pragma unroll
-      for (int i = 0; i < NCH; ++i) { g[i] = load4<T>(dout + ro + 256 * i); nv[i] = *(const float4*)(x + ro + 256 * i); }
+      for (int i = 0; i < NCH; ++i) {
+        g[i] = load4<T>(dout + ro + 256 * i); nv[i] = *(const float4*)(x + ro + 256 * i);
+        if constexpr (RECOMP) yv[i] = load4<T>(gy + ro + 256 * i);          // needed before the first use of nv: with the first batch
+      }
 #pragma unroll
       for (int i = 0; i < NCH; ++i) {
         dold[i] = ga.dx_overwrite ? f4(0.f) : *(const float4*)(dx + ro + 256 * i);
-        if constexpr (GATE) yv[i] = load4<T>(gy + ro + 256 * i);
+        if constexpr (GATE && !RECOMP) yv[i] = load4<T>(gy + ro + 256 * i);
       }
       const float rs = rstd[m];
       float4 dn[NCH];
@@ -228,6 +347,7 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_bwd_kernel(const T* __restric
       for (int i = 0; i < NCH; ++i) {
         const int c = lane + 64 * i;
         const float4 wc = GATE ? *(const float4*)(cw + 4 * c) : wv[i], sc = GATE ? *(const float4*)(cs + 4 * c) : sc1[i];
+        if constexpr (RECOMP) nv[i] = gate_res4(nv[i], *(const float4*)(cg + 4 * c), yv[i]);
         nv[i] = nv[i] * rs;
         const float4 dy = g[i] * sc;
         a_sh[i] = a_sh[i] + g[i];
@@ -273,7 +393,9 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_bwd_kernel(const T* __restric
       if (c < nch) {
         const float4 g = load4<T>(dout + (size_t)m * D + 4 * c);
         const float4 wc = GATE ? *(const float4*)(cw + 4 * c) : wv[i], sc = GATE ? *(const float4*)(cs + 4 * c) : sc1[i];
-        nv[i] = (*(const float4*)(x + (size_t)m * D + 4 * c) - f4(mean)) * rs;
+        float4 xr = *(const float4*)(x + (size_t)m * D + 4 * c);
+        if constexpr (RECOMP) xr = gate_res4(xr, *(const float4*)(cg + 4 * c), load4<T>(gy + (size_t)m * D + 4 * c));
+        nv[i] = (xr - f4(mean)) * rs;
         const float4 dy = g * sc;
         a_sh[i] = a_sh[i] + g;
         a_sc[i] = a_sc[i] + g * (nv[i] * wc);
@@ -404,6 +526,35 @@ extern "C" int ldmae_rmsnorm_modulate_fwd(int out_dtype, const float* x, const f
                                           int mod_ld, void* out, float* rstd, int M, int D, int rows_per_batch, float eps, void* stream) {
   return norm_modulate_fwd(out_dtype, x, w, shift, scale, mod_ld, out, rstd, M, D, rows_per_batch, eps, 0, stream);
 }
+// r = x + gate_a[b] * ya (+ gate_b[b] * yb when yb is given); xout = r (optional); out / rstd = rmsnorm_modulate_fwd of r (optional; at least
+// one of xout / out).  dtype: the 16-bit activation type of ya / yb / out.
+extern "C" int ldmae_res_rmsnorm_modulate_fwd(int dtype, const float* x, const void* ya, const float* gate_a, int gate_a_ld, const void* yb,
+                                              const float* gate_b, int gate_b_ld, float* xout, const float* w, const float* shift,
+                                              const float* scale, int mod_ld, void* out, float* rstd, int M, int D, int rows_per_batch, float eps,
+                                              void* stream) {
+  LDMAE_REQUIRE(dtype == LDMAE_BF16 || dtype == LDMAE_F16, "res_rmsnorm_modulate_fwd: dtype %d (bf16 or fp16 activations only)", dtype);
+  LDMAE_REQUIRE(x && ya && gate_a && (xout || out) && M > 0 && D > 0, "res_rmsnorm_modulate_fwd: null pointer or empty");
+  LDMAE_REQUIRE((yb != nullptr) == (gate_b != nullptr), "res_rmsnorm_modulate_fwd: yb and gate_b go together");
+  LDMAE_REQUIRE(!out || w, "res_rmsnorm_modulate_fwd: the norm needs its weight");
+  LDMAE_REQUIRE(out || (!rstd && !shift && !scale), "res_rmsnorm_modulate_fwd: rstd / shift / scale without a norm output");
+  LDMAE_REQUIRE(xout != x, "res_rmsnorm_modulate_fwd: xout must not alias x");
+  LDMAE_REQUIRE(D % 4 == 0 && gate_a_ld % 4 == 0 && (!yb || gate_b_ld % 4 == 0) && (mod_ld % 4 == 0 || (!shift && !scale)),
+                "res_rmsnorm_modulate_fwd: D=%d gate_ld=%d/%d mod_ld=%d must be multiples of 4", D, gate_a_ld, gate_b_ld, mod_ld);
+  LDMAE_REQUIRE(rows_per_batch > 0 && M % rows_per_batch == 0, "res_rmsnorm_modulate_fwd: M=%d %% rows_per_batch=%d != 0", M, rows_per_batch);
+  const uintptr_t al = (uintptr_t)x | (uintptr_t)ya | (uintptr_t)gate_a | (uintptr_t)yb | (uintptr_t)gate_b | (uintptr_t)xout | (uintptr_t)w |
+                       (uintptr_t)shift | (uintptr_t)scale | (uintptr_t)out;
+  LDMAE_REQUIRE(al % 16 == 0, "res_rmsnorm_modulate_fwd: every tensor must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const unsigned grid = cdiv(M, 16);
+  // (fp16 keeps the guarded form: ldmae_rmsnorm_modulate_fwd has no fp16 output, and the f32 output it is compared with runs the guarded form)
+  const bool full = dtype == LDMAE_BF16 && D % 256 == 0 && M % 16 == 0 && rows_per_batch % 16 == 0;
+#define RES_LAUNCH(T, FULLV) DISPATCH_NCH(D, hipLaunchKernelGGL((res_rmsnorm_mod_fwd_kernel<NCH, T, FULLV>), dim3(grid), dim3(256), 0, st, x, (const T*)ya, gate_a, gate_a_ld, (const T*)yb, gate_b, gate_b_ld, xout, w, shift, scale, mod_ld, (T*)out, rstd, M, D, rows_per_batch, eps))
+  if (dtype == LDMAE_BF16) { if (full) { RES_LAUNCH(bf16, true); } else { RES_LAUNCH(bf16, false); } }
+  else { RES_LAUNCH(f16, false); }
+#undef RES_LAUNCH
+  LDMAE_CHECK_LAUNCH("res_rmsnorm_modulate_fwd");
+  return LDMAE_OK;
+}
 // LayerNorm(elementwise_affine=False) + modulate: the norm of the blocks built with use_rmsnorm=False (lightningdit.py:200-201,257; eps 1e-6).
 // rstd [M] = rsqrt(var + eps) (the backward recomputes the row mean from x).
 extern "C" int ldmae_layernorm_modulate_fwd(int out_dtype, const float* x, const float* shift, const float* scale, int mod_ld, void* out,
@@ -443,7 +594,15 @@ static int rmsnorm_modulate_bwd_core(int dtype, const void* dout, const float* x
   if (center && !dw) dw = P;             // LayerNorm without affine parameters: no weight gradient; the last reduce (stream-ordered behind the consumers of P) writes its [D] sums there
 #define LAUNCH(T, GATE) DISPATCH_NCH(D, hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NCH, T, GATE>), dim3(G), dim3(256), lds, st, (const T*)dout, x, w, scale, mod_ld, rstd, dx_accum, P, M, D, rows_per_batch, rw, ga))
 #define LAUNCH_FULL(T, GATE) DISPATCH_NCH(D, hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NCH, T, GATE, true>), dim3(G), dim3(256), lds, st, (const T*)dout, x, w, scale, mod_ld, rstd, dx_accum, P, M, D, rows_per_batch, rw, ga))
-  if (dtype == LDMAE_BF16 && D % 256 == 0 && !center) { if (gate) { LAUNCH_FULL(bf16, true); } else { LAUNCH_FULL(bf16, false); } }
+  if (gate && gate->recompute) {
+    LDMAE_REQUIRE(dtype == LDMAE_BF16 && !center, "rmsnorm_modulate_bwd_gate_recompute: bf16 activations and the RMSNorm form only");
+    if (D % 256 == 0) {
+      DISPATCH_NCH(D, hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NCH, bf16, true, true, true>), dim3(G), dim3(256), lds, st, (const bf16*)dout, x, w, scale, mod_ld, rstd, dx_accum, P, M, D, rows_per_batch, rw, ga));
+    } else {
+      DISPATCH_NCH(D, hipLaunchKernelGGL((rmsnorm_mod_bwd_kernel<NCH, bf16, true, false, true>), dim3(G), dim3(256), lds, st, (const bf16*)dout, x, w, scale, mod_ld, rstd, dx_accum, P, M, D, rows_per_batch, rw, ga));
+    }
+  }
+  else if (dtype == LDMAE_BF16 && D % 256 == 0 && !center) { if (gate) { LAUNCH_FULL(bf16, true); } else { LAUNCH_FULL(bf16, false); } }
   else if (dtype == LDMAE_BF16) { if (gate) { LAUNCH(bf16, true); } else { LAUNCH(bf16, false); } }
   else { if (gate) { LAUNCH(float, true); } else { LAUNCH(float, false); } }
 #undef LAUNCH
@@ -483,6 +642,19 @@ extern "C" int ldmae_rmsnorm_modulate_bwd_gate(int dtype, const void* dout, cons
   LDMAE_REQUIRE(y && gate && dy && dgate && dbias, "rmsnorm_modulate_bwd_gate: null pointer");
   LDMAE_REQUIRE(gate_ld % 4 == 0, "rmsnorm_modulate_bwd_gate: gate_ld=%d must be a multiple of 4", gate_ld);
   const GateBwdArgs ga{y, gate, gate_ld, dy, nullptr, nullptr, 0, 0};
+  return rmsnorm_modulate_bwd_core(dtype, dout, x, w, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, dw, beta_w, M, D, rows_per_batch,
+                                   workspace, &ga, dgate, dgate_ld, dbias, stream);
+}
+// ldmae_rmsnorm_modulate_bwd_gate for a norm whose input row was never stored: `x` is the residual stream BEFORE the gated residual under
+// the norm and the kernel rebuilds the normalised row as x + gate[b] * y (RECOMP above).  Every output has the bits ldmae_rmsnorm_modulate_bwd_gate
+// produces when it is handed that row materialised.  bf16 only.
+extern "C" int ldmae_rmsnorm_modulate_bwd_gate_recompute(int dtype, const void* dout, const float* x, const float* w, const float* scale, int mod_ld,
+                                                         const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld,
+                                                         float* dw, float beta_w, const void* y, const float* gate, int gate_ld, void* dy, float* dgate,
+                                                         int dgate_ld, float* dbias, int M, int D, int rows_per_batch, float* workspace, void* stream) {
+  LDMAE_REQUIRE(y && gate && dy && dgate && dbias, "rmsnorm_modulate_bwd_gate_recompute: null pointer");
+  LDMAE_REQUIRE(gate_ld % 4 == 0, "rmsnorm_modulate_bwd_gate_recompute: gate_ld=%d must be a multiple of 4", gate_ld);
+  const GateBwdArgs ga{y, gate, gate_ld, dy, nullptr, nullptr, 0, 0, 1};
   return rmsnorm_modulate_bwd_core(dtype, dout, x, w, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, dw, beta_w, M, D, rows_per_batch,
                                    workspace, &ga, dgate, dgate_ld, dbias, stream);
 }

@@ -60,9 +60,6 @@ int ldmae_launch_nt_p8(int epi, int out_bf16, const void* A, const void* B, int 
 // lightningdit.py:248-249); every kernel that forms it -- the fused epilogues here, the deferred units of gemm_nt_defer.hip --
 // uses this one definition, so they agree bit for bit.
 template <typename OutT> __device__ __forceinline__ float act_round(float y) { return to_f<OutT>(from_f<OutT>(y)); }
-__device__ __forceinline__ float4 gate_res4(float4 x, float4 g, float4 y) {
-  return make_float4(fmaf(g.x, y.x, x.x), fmaf(g.y, y.y, x.y), fmaf(g.z, y.z, x.z), fmaf(g.w, y.w, x.w));
-}
 template <typename OutT> __device__ __forceinline__ float4 act_round4(float4 y) {
   return make_float4(act_round<OutT>(y.x), act_round<OutT>(y.y), act_round<OutT>(y.z), act_round<OutT>(y.w));
 }

@@ -230,6 +230,10 @@ class _GradChain:
 
     def __init__(self):
         self.up, self.pre = {}, {}
+        # the forward mirror image (ops.FUSED_RESNORM): `nxt[j]` = norm1 weight of member j+1, registered by LightningDiT.forward; `fwd[j+1]` =
+        # (data pointer of member j's output, xm1, rstd1): member j's last row pass already normalised its output for member j+1's norm1,
+        # which consumes the entry once and falls back to its own norm if it is handed a different buffer
+        self.nxt, self.fwd = {}, {}
         self.dmod_all, self.mod_cols = None, 0      # batched adaLN (_AdaLNAllFn): ONE [B, depth * 6D] gradient buffer, a column slice per block
 
     def dmod(self, j, mod):
@@ -360,8 +364,19 @@ class _DiTBlockFn(torch.autograd.Function):
             ctx.hs = (Hs_, Hp_)
         W12, W12T = _wcopies(w12, dtype, bwd)
         W3, W3T = _wcopies(w3, dtype, bwd)
+        # The gated residuals formed in the norms' row passes instead of the GEMM epilogues (ops.res_rmsnorm_modulate_fwd; bitwise the same
+        # block): the proj / w3 GEMMs write only y1 / y2, the mid-block residual stream is never stored, and this block's last row pass
+        # normalises its output for the next block's norm1.  Training through the block chain with batched adaLN only (the next block's
+        # shift / scale are known up front); everything else keeps the epilogue + norm pair.
+        resnorm = (ops.FUSED_RESNORM and dtype == torch.bfloat16 and n1w is not None and n2w is not None and mod_all is not None and
+                   chain is not None and bwd and not input_only)
+        ctx.resnorm = resnorm
         # attention branch (:248)
-        xm1, rstd1 = ops.rmsnorm_modulate_fwd(x2, n1w, sh1, s1, N, dtype, eps)
+        handed = chain.fwd.pop(idx, None) if chain is not None else None
+        if handed is not None and handed[0] == x2.data_ptr():
+            xm1, rstd1 = handed[1], handed[2]
+        else:
+            xm1, rstd1 = ops.rmsnorm_modulate_fwd(x2, n1w, sh1, s1, N, dtype, eps)
         qk_saved = None
         fused_qkv = qnb is None and dtype == torch.bfloat16 and ops.gemm_nt_qkv_rope_ok(xm1, Wqkv, B, N, H, hd)
         if not fused_qkv:
@@ -382,15 +397,31 @@ class _DiTBlockFn(torch.autograd.Function):
         else:
             q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps)
             o, lse = ops.attention_fwd(q, k, v, hd ** -0.5)
-        xmid, y1 = ops.gemm_nt_gate_res(o.view(M, D), Wp, pb, x2, g1, N, save_y=bwd)
+        if resnorm:
+            y1 = ops.gemm_nt(o.view(M, D), Wp, pb)
+            _, xm2, rstd2 = ops.res_rmsnorm_modulate_fwd(x2, y1, g1, None, None, n2w, sh2, s2, N, eps)
+            xmid = x2                    # its slot in saved_tensors: norm2's backward rebuilds the row from (x2, y1, g1)
+        else:
+            xmid, y1 = ops.gemm_nt_gate_res(o.view(M, D), Wp, pb, x2, g1, N, save_y=bwd)
+            xm2, rstd2 = ops.rmsnorm_modulate_fwd(xmid, n2w, sh2, s2, N, dtype, eps)
         # MLP branch (:249)
-        xm2, rstd2 = ops.rmsnorm_modulate_fwd(xmid, n2w, sh2, s2, N, dtype, eps)
         if swiglu:
             h12, hid = ops.gemm_nt_swiglu(xm2, W12, b12, save_h12=bwd)
         else:                            # timm Mlp (:219-224): fc1 -> GELU(tanh) -> fc2; h12 = fc1's pre-activation, hid = the activation
             h12 = ops.gemm_nt(xm2, W12, b12)
             hid = ops.gelu_tanh_fwd(h12)
-        xout, y2 = ops.gemm_nt_gate_res(hid, W3, b3, xmid, g2, N, save_y=bwd)
+        if resnorm:
+            y2 = ops.gemm_nt(hid, W3, b3)
+            n1w_next = chain.nxt.get(idx)
+            if n1w_next is not None:     # the next block's norm1 rides along (its column slice of mod_all: shift_msa, scale_msa first)
+                modn = mod_all[:, (idx + 1) * nmod * D:(idx + 2) * nmod * D]
+                shn, sn = (modn[:, :D], modn[:, D:2 * D]) if nmod == 6 else (None, modn[:, :D])
+                xout, xm1n, rstd1n = ops.res_rmsnorm_modulate_fwd(x2, y1, g1, y2, g2, n1w_next, shn, sn, N, eps, want_xout=True)
+                chain.fwd[idx + 1] = (xout.data_ptr(), xm1n, rstd1n)
+            else:                        # last block: the final layer keeps its own norm
+                xout, _, _ = ops.res_rmsnorm_modulate_fwd(x2, y1, g1, y2, g2, rows_per_batch=N, want_xout=True, want_norm=False)
+        else:
+            xout, y2 = ops.gemm_nt_gate_res(hid, W3, b3, xmid, g2, N, save_y=bwd)
         if not bwd:
             return xout.view(B, N, D)
         ctx.input_only = bool(input_only)
@@ -508,8 +539,9 @@ class _DiTBlockFn(torch.autograd.Function):
         dW12, r = _dw_into_grad(sg, dh12, xm2, w12_p, ctx.direct); notify.append((r, w12_p))
         dxm2 = ops.gemm_nt(dh12, W12T)
         # norm2 backward and the attention branch's gate backward in one pass (the updated dx is consumed from registers)
+        # (ctx.resnorm: the mid-block row was never stored -- `xmid` is x2 and the kernel rebuilds the row from (x2, y1, g1))
         dn2, dy1, dbp = ops.rmsnorm_modulate_bwd_gate(dxm2, xmid, n2w, s2, rstd2, dx, col(dmod, c_sh2), col(dmod, c_s2),
-                                                      y1, g1, col(dmod, c_g1), N, dtype)
+                                                      y1, g1, col(dmod, c_g1), N, dtype, recompute=ctx.resnorm)
         # ---- attention branch
         dWp, r = _dw_into_grad(sg, dy1, o.view(M, D), pw_p, ctx.direct); notify.append((r, pw_p))
         do = ops.gemm_nt(dy1, WpT)
@@ -1041,6 +1073,9 @@ class LightningDiT(nn.Module):
                     mod_all = _AdaLNAllFn.apply(sc, not torch.is_grad_enabled(), *[l.weight for l in lins], *[l.bias for l in lins])
                 if chain is not None:
                     chain.mod_cols = mod_all.shape[1]
+            if chain is not None and mod_all is not None and self.use_rmsnorm:      # forward hand-off of norm1 (see _GradChain.nxt)
+                for i in range(len(self.blocks) - 1):
+                    chain.nxt[i] = self.blocks[i + 1].norm1.weight
             for i, block in enumerate(self.blocks):
                 if self.use_checkpoint:
                     x = checkpoint(block, x, c, self.feat_rope, sc, dtype, not hooked[i], use_reentrant=True)

@@ -259,6 +259,9 @@ def gemm_nt_swiglu(a, w12, b12, save_h12=True):
 
 
 FUSED_QKV = os.environ.get("LDMAE_FUSED_QKV", "1") != "0"      # module switch for A/B runs (tools/bench_qkv_rope.py)
+# A/B switch, read at call time: 1 = the training block forms its gated residuals in the norm's row pass (res_rmsnorm_modulate_fwd) and never
+# stores the mid-block residual stream; 0 = the EPI_GATE_RES epilogue + rmsnorm_modulate_fwd pair.  Bitwise the same step either way.
+FUSED_RESNORM = os.environ.get("LDMAE_FUSED_RESNORM", "1") != "0"
 
 
 def gemm_nt_qkv_rope_ok(a, w, B, N, H, hd):
@@ -559,6 +562,38 @@ def rmsnorm_modulate_fwd(x, w, shift, scale, rows_per_batch, out_dtype, eps=1e-6
     return out, rstd
 
 
+def res_rmsnorm_modulate_fwd(x, ya, gate_a, yb=None, gate_b=None, w=None, shift=None, scale=None, rows_per_batch=0, eps=1e-6,
+                             want_xout=False, want_norm=True):
+    """The gated residual(s) of a block and the norm behind them in one pass over the rows: r = x + gate_a[b] * ya (+ gate_b[b] * yb);
+    -> (xout or None, xm or None, rstd or None) with xout = r (f32) and (xm, rstd) = rmsnorm_modulate_fwd(r, w, shift, scale) in ya's
+    type.  ya / yb: the Linear outputs as stored (bf16 / fp16); gates [B, D] f32 views (any row stride).  Bitwise gemm_nt_gate_res's
+    residual followed by rmsnorm_modulate_fwd."""
+    M, D = x.shape
+    if ya.dtype not in (torch.bfloat16, torch.float16) or (yb is not None and yb.dtype != ya.dtype):
+        raise RuntimeError("res_rmsnorm_modulate_fwd: bfloat16 or float16 branch outputs of one type expected")
+    if not (want_xout or want_norm):
+        raise RuntimeError("res_rmsnorm_modulate_fwd: nothing requested (want_xout / want_norm)")
+    if rows_per_batch <= 0 or M % rows_per_batch:
+        raise RuntimeError(f"res_rmsnorm_modulate_fwd: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
+    B = M // rows_per_batch
+    x = _arg(x, "res_rmsnorm_modulate_fwd x", torch.float32, (M, D))
+    ya = _arg(ya, "res_rmsnorm_modulate_fwd ya", None, (M, D))
+    yb = _arg(yb, "res_rmsnorm_modulate_fwd yb", None, (M, D))
+    gate_a = _arg(gate_a, "res_rmsnorm_modulate_fwd gate_a", torch.float32, (B, D), rows=True)
+    gate_b = _arg(gate_b, "res_rmsnorm_modulate_fwd gate_b", torch.float32, (B, D), rows=True)
+    xout = torch.empty(M, D, dtype=torch.float32, device=x.device) if want_xout else None
+    out = rstd = None
+    ld = 0
+    if want_norm:
+        out = torch.empty(M, D, dtype=ya.dtype, device=x.device)
+        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+        ld = shift.stride(0) if shift is not None else (scale.stride(0) if scale is not None else 0)
+    call("ldmae_res_rmsnorm_modulate_fwd", dt(ya.dtype), ptr(x), ptr(ya), ptr(gate_a), _ld(gate_a), ptr(yb), ptr(gate_b),
+         _ld(gate_b) if gate_b is not None else 0, ptr(xout), ptr(w) if want_norm else None, ptr(shift) if want_norm else None,
+         ptr(scale) if want_norm else None, ld, ptr(out), ptr(rstd), M, D, rows_per_batch, eps, stream())
+    return xout, out, rstd
+
+
 def rmsnorm_modulate_bwd(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows_per_batch, accumulate=True):
     """dx_accum += dx (in place; accumulate=False: dx_accum = dx, the buffer may be uninitialised); writes dshift/dscale views ([B,D], any
     row stride); returns dw [D]."""
@@ -576,10 +611,15 @@ def rmsnorm_modulate_bwd(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows
     return dw
 
 
-def rmsnorm_modulate_bwd_gate(dout, x, w, scale, rstd, dx_accum, dshift, dscale, y, gate, dgate, rows_per_batch, act_dtype, accumulate=True):
+def rmsnorm_modulate_bwd_gate(dout, x, w, scale, rstd, dx_accum, dshift, dscale, y, gate, dgate, rows_per_batch, act_dtype, accumulate=True,
+                              recompute=False):
     """rmsnorm_modulate_bwd followed by gate_bwd(dx_accum, y, gate, dgate, with_bias=True) in one pass over the rows.
-    Returns (dw [D], dy [M,D] act dtype, dbias [D])."""
+    Returns (dw [D], dy [M,D] act dtype, dbias [D]).  recompute: `x` is the residual stream BEFORE the gated residual under the norm (the
+    forward ran res_rmsnorm_modulate_fwd and never stored the normalised row); the kernel rebuilds that row as x + gate * y.  Bitwise the
+    plain form handed the row materialised; bf16, RMSNorm form."""
     M, D = x.shape
+    if recompute and (w is None or dout.dtype != torch.bfloat16):
+        raise RuntimeError("rmsnorm_modulate_bwd_gate(recompute=True): the RMSNorm form with bfloat16 activations only")
     dy = torch.empty(M, D, dtype=act_dtype, device=x.device)
     dbias = torch.empty(D, dtype=torch.float32, device=x.device)
     ws = workspace(L.load().ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes(M, D, rows_per_batch), x.device)
@@ -590,7 +630,8 @@ def rmsnorm_modulate_bwd_gate(dout, x, w, scale, rstd, dx_accum, dshift, dscale,
              ptr(dbias), M, D, rows_per_batch, ptr(ws), stream())
         return None, dy, dbias
     dw = torch.empty(D, dtype=torch.float32, device=x.device)
-    call("ldmae_rmsnorm_modulate_bwd_gate", dt(dout.dtype), ptr(dout), ptr(x), ptr(w), ptr(scale), scale.stride(0) if scale is not None else 0,
+    call("ldmae_rmsnorm_modulate_bwd_gate_recompute" if recompute else "ldmae_rmsnorm_modulate_bwd_gate", dt(dout.dtype), ptr(dout), ptr(x), ptr(w), ptr(scale),
+         scale.stride(0) if scale is not None else 0,
          ptr(rstd), ptr(dx_accum), 1.0 if accumulate else 0.0, ptr(dshift), ptr(dscale), (dshift if dshift is not None else dscale).stride(0) if (dshift is not None or dscale is not None) else 0, ptr(dw), 0.0,
          ptr(y), ptr(gate), gate.stride(0), ptr(dy), ptr(dgate), dgate.stride(0), ptr(dbias), M, D, rows_per_batch, ptr(ws), stream())
     return dw, dy, dbias
