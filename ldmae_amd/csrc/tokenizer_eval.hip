@@ -292,8 +292,11 @@ extern "C" int ldmae_ssim(const float* preds, const float* target, float* out, i
 // q(x) = (uint8) trunc(clamp(127.5 x + 128, 0, 255)) with the multiply and the add rounded separately, as torch evaluates the expression.
 // One thread per pixel: reads the three NCHW planes of both images, writes both NHWC uint8 pixels and adds (q(d) - q(r))^2 over the three
 // channels to its running sum; grid (blocks, B): the block sum goes to part[b * blocks + k] (64-bit), the final pass adds them in order.
+// (__fmul_rn / __fadd_rn are plain operators in the HIP headers and were contracted into one v_fma; the pragma is what keeps them apart.)
 __device__ __forceinline__ int png_quantize(float x) {
-  const float v = __fadd_rn(__fmul_rn(127.5f, x), 128.f);
+#pragma clang fp contract(off)
+  const float p = 127.5f * x;
+  const float v = p + 128.f;
   return (int)fminf(fmaxf(v, 0.f), 255.f);
 }
 
