@@ -4,8 +4,9 @@
  * Python module API (models/lightningdit.py, tokenizer/models_mae.py).  This header
  * is what a binding for that seam calls: one entry per fused region of the LightningDiT block /
  * VMAE encoder, each citing the reference lines whose arithmetic it replaces (paths relative to
- * /root/reference/LDMAE).  The ctypes binding lives in ldmae_amd/_lib.py; INTEGRATION.md shows the
- * stub a maintainer adds on the reference side.
+ * /root/reference/LDMAE).  The ctypes binding lives in ldmae_amd/_lib.py, which PARSES THIS FILE at import for every prototype's
+ * types: keep it to comments, preprocessor lines and plain C89 prototypes over int / long / long long / unsigned long long / float /
+ * double / pointers (anything else makes the import raise).  INTEGRATION.md shows the stub a maintainer adds on the reference side.
  *
  * Conventions
  *  - plain device pointers + explicit sizes, no torch types; `stream` is a hipStream_t (NULL = default).

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -17,168 +18,49 @@ LIB_PATH = os.environ.get("LDMAE_HIP_LIB", LIB_PATH)      # A/B builds of the sa
 F32, BF16, F16 = 0, 1, 2
 EPI_BIAS, EPI_GATE_RES, EPI_BIAS_POS, EPI_BIAS_GELU, EPI_SWIGLU, EPI_SWIGLU_BWD, EPI_GELU_BWD = 0, 1, 2, 3, 4, 5, 6
 
-_vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
+_SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "float": C.c_float,
+            "double": C.c_double}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char*": C.c_char_p})
 
-# name -> (restype, argtypes); mirrors include/ldmae_hip.h one to one
-SIGNATURES = {
-    "ldmae_last_error": (C.c_char_p, []),
-    "ldmae_version": (C.c_char_p, []),
-    "ldmae_arch": (C.c_char_p, []),
-    "ldmae_gemm_nt": (_i, [_i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
-    "ldmae_gemm_nt_qkv_rope_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "ldmae_gemm_nt_qkv_rope": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
-    "ldmae_gemm_tn_splits": (_i, [_i, _i, _i, _i]),
-    "ldmae_gemm_tn_workspace_bytes": (_l, [_i, _i, _i, _i]),
-    "ldmae_gemm_tn": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _l, _vp]),
-    "ldmae_colsum_workspace_bytes": (_l, [_i, _i]),
-    "ldmae_colsum": (_i, [_i, _vp, _i, _i, _i, _vp, _f, _vp, _vp]),
-    "ldmae_cast_weight": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
-    "ldmae_cast": (_i, [_i, _i, _vp, _vp, _l, _vp]),
-    "ldmae_cast_stack": (_i, [_i, _vp, _i, _l, _vp, _vp]),
-    "ldmae_multi_add": (_i, [_i, _vp, _vp, _vp, _vp]),
-    "ldmae_thin_nt": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_thin_tn_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_thin_tn": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _l, _vp]),
-    "ldmae_rmsnorm_modulate_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
-    "ldmae_rmsnorm_modulate_bwd_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_rmsnorm_modulate_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _f, _i, _i, _i, _vp, _vp]),
-    "ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_rmsnorm_modulate_bwd_gate": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _f, _vp, _vp, _i, _vp, _vp, _i, _vp,
-                                             _i, _i, _i, _vp, _vp]),
-    "ldmae_rmsnorm_modulate_bwd_gate_recompute": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _f, _vp, _vp, _i, _vp, _vp, _i,
-                                                       _vp, _i, _i, _i, _vp, _vp]),
-    "ldmae_res_rmsnorm_modulate_fwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
-    "ldmae_qknorm_rope_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_qknorm_rope_bwd_workspace_bytes": (_l, [_i, _i, _i, _i]),
-    "ldmae_qknorm_rope_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
-    "ldmae_rope": (_i, [_i, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
-    "ldmae_attention_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_attention_fwd_qkv": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_attention_bwd_qkv": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_attention_fwd_pv": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_k_norm_max": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_attention_fwd_qkv_bounded": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_attention_fwd_pv_bounded": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_qk_score_bound": (_i, [_vp, _vp, _i, _f, _vp, _vp]),
-    "ldmae_attention_bwd_pv": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_attention_bwd_pv_qknorm_workspace_bytes": (_l, [_i, _i, _i, _i]),
-    "ldmae_attention_bwd_pv_qknorm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
-                                           _f, _vp]),
-    "ldmae_swiglu_fwd": (_i, [_i, _vp, _vp, _i, _i, _vp]),
-    "ldmae_swiglu_bwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
-    "ldmae_gate_bwd_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_gate_bwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
-    "ldmae_timestep_embedding": (_i, [_vp, _vp, _i, _i, _f, _vp]),
-    "ldmae_silu_fwd": (_i, [_i, _vp, _vp, _l, _vp]),
-    "ldmae_silu_bwd": (_i, [_vp, _vp, _vp, _l, _vp]),
-    "ldmae_label_embed_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_label_embed_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_adamw_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _d, _d, _d, _d, _d, _d, _d, _vp]),
-    "ldmae_ema_only": (_i, [_vp, _vp, _l, _d, _vp]),
-    "ldmae_random_masking": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_patch_gather": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_latent_prologue": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_crop_resize_flip_u8": (_i, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
-    "ldmae_gather_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_scatter_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_restore_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_restore_tokens_bwd_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_restore_tokens_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ldmae_vmae_encoder_blob_bytes": (_l, [_i]),
-    "ldmae_vmae_encoder_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_vmae_encoder_fwd_tiled_workspace_bytes": (_l, [_i, _i]),
-    "ldmae_vmae_encoder_fwd_tiled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_vmae_encoder_fwd_tiled_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_layernorm_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
-    "ldmae_layernorm_bwd_workspace_bytes": (_l, [_i, _i]),
-    "ldmae_layernorm_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
-    "ldmae_mae_loss_groups": (_l, [_l]),
-    "ldmae_mae_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_mae_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_layernorm_bwd_cast": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
-    "ldmae_gelu_fwd": (_i, [_i, _vp, _vp, _l, _vp]),
-    "ldmae_gelu_bwd": (_i, [_i, _vp, _vp, _vp, _l, _vp]),
-    "ldmae_gelu_tanh_fwd": (_i, [_i, _vp, _vp, _l, _vp]),
-    "ldmae_gelu_tanh_bwd": (_i, [_i, _vp, _vp, _vp, _l, _vp]),
-    "ldmae_layernorm_modulate_fwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp]),
-    "ldmae_layernorm_modulate_bwd": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ldmae_layernorm_modulate_bwd_gate": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
-    "ldmae_conv3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_conv3x3_bwd_workspace_bytes": (_l, [_i]),
-    "ldmae_conv3x3_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ldmae_conv2d_nhwc_f32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_pool2d_nhwc_f32": (_i, [_i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_global_avgpool_nhwc_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
-    "ldmae_fid_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_fid_stats_accumulate": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "ldmae_adm_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_adm_spatial_tap": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp]),
-    "ldmae_row_sqnorms_f32": (_i, [_vp, _i, _i, _vp, _vp]),
-    "ldmae_pairwise_logits": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
-    "ldmae_knn_partials_bytes": (_l, [_i, _i]),
-    "ldmae_knn_radii": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
-    "ldmae_pr_flags": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ldmae_adm_is_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_adm_softmax_is": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "ldmae_lpips_prep": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_lpips_workspace_bytes": (_l, [_i, _i, _i]),
-    "ldmae_lpips_layer": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ldmae_ssim_workspace_bytes": (_l, [_i, _i, _i, _i]),
-    "ldmae_ssim": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
-    "ldmae_sse_workspace_bytes": (_l, [_i, _l]),
-    "ldmae_recon_quantize_psnr": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ldmae_sse_u8": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
-    "ldmae_conv3x3_relu_dgrad_nhwc_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_maxpool2x2_bwd_nhwc_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_lpips_layer_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_lpips_prep_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_lpips_prep_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_conv3x3_relu_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_maxpool2x2_nhwc_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_lpips_layer_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ldmae_conv3x3_relu_dgrad_nhwc_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_maxpool2x2_bwd_nhwc_xf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ldmae_lpips_layer_bwd_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_lpips_prep_bwd_c8": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_groupnorm_stats_nhwc_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "ldmae_groupnorm_apply_nhwc_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_conv3x3_vae_nhwc_f32": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_conv1x1_res_nhwc_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_softmax_rows_f32": (_i, [_vp, _i, _i, _i, _f, _vp]),
-    "ldmae_conv3x3_vae_nhwc_f16": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_conv1x1_res_nhwc_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ldmae_groupnorm_apply_nhwc_f16out": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ldmae_ode_partials": (_i, [_l]),
-    "ldmae_rk_stage_f32": (_i, [_vp, _vp, _l, C.POINTER(_f), _i, _vp, _vp, _l, _vp, _f, _vp, _i, _vp]),
-    "ldmae_dopri5_finish_f32": (_i, [_vp, _vp, _l, _vp, _f, _f, _vp, _vp, _vp, _l, _vp]),
-    "ldmae_rms_norm_scaled_f32": (_i, [_vp, _vp, _f, _f, _vp, _vp, _l, _vp]),
-    "ldmae_dopri5_interp_f32": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _f, _vp, _l, _vp]),
-    "ldmae_dopri5_advance": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "ldmae_dopri5_initial_step": (_i, [_vp, _i, _vp, _vp]),
-    "ldmae_rademacher_f32": (_i, [_vp, _l, C.c_ulonglong, C.c_ulonglong, _vp]),
-    "ldmae_rowdot_partials": (_l, [_i, _l]),
-    "ldmae_rowdot_f32": (_i, [_vp, _vp, _vp, _i, _l, _vp, _vp]),
-    "ldmae_likelihood_finish_f32": (_i, [_vp, _vp, _f, _vp, _i, _vp]),
-    "ldmae_normal_f32": (_i, [_vp, _l, C.c_ulonglong, C.c_ulonglong, _vp]),
-    "ldmae_sde_combine_f32": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_f), _i, _vp, _f, _i, C.c_ulonglong, C.c_ulonglong, _vp, _vp, _l, _f, _vp, _i, _vp]),
-    "ldmae_prof_enable": (_i, [_i]),
-    "ldmae_prof_collect": (_i, [C.POINTER(_d), C.POINTER(_d), C.POINTER(_l)]),
-    "ldmae_launch_counts": (_i, [C.POINTER(_l), _i, _i]),
-    "ldmae_mx8_quantize": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _vp]),
-    "ldmae_rmsnorm_modulate_fwd_mx8": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
-    "ldmae_gemm_nt_mx8_ok": (_i, [_i, _i, _i, _i, _i]),
-    "ldmae_gemm_nt_mx8": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "ldmae_gemm_nt_qkv_rope_mx8_ok": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "ldmae_gemm_nt_qkv_rope_mx8": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
-    "ldmae_mx8_launch_counts": (_i, [C.POINTER(_l), _i, _i]),
-}
+
+def parse_header(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every prototype in a C header that holds nothing but plain C89 prototypes, comments, preprocessor
+    lines and the extern "C" braces.  Scalars map to their ctypes type, every pointer parameter to c_void_p (device pointers are integers;
+    host arrays and byref() pass as well), a `const char*` return to c_char_p, a `void` return to None.  STRICT: a type outside that
+    list, or text that is no prototype, raises ValueError with the offending declaration -- nothing ever defaults to int."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)
+    sigs = {}
+    for decl in text.split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        m = re.fullmatch(r"([\w ]+?\*?) ?(\w+) ?\(([^()]*)\)", decl)
+        if m is None:
+            raise ValueError(f"not a C prototype: {decl!r}")
+        ret, name, params = m.group(1).strip().replace(" *", "*"), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise ValueError(f"return type {ret!r} has no ctypes mapping: {decl!r}")
+        args = []
+        for prm in ([] if params == "void" else params.split(",")):
+            ctype = " ".join(w for w in prm.split()[:-1] if w != "const")          # the last word is the parameter's name
+            if "*" not in prm and ctype not in _SCALARS:
+                raise ValueError(f"parameter {prm.strip()!r} has no ctypes mapping: {decl!r}")
+            args.append(C.c_void_p if "*" in prm else _SCALARS[ctype])
+        sigs[name] = (_RETURNS[ret], args)
+    return sigs
+
+
+def _parse_file(*parts):
+    with open(os.path.join(_HERE, *parts)) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, [argtypes]), derived from the headers at import: the headers are the only place a signature is written down
+SIGNATURES = _parse_file("..", "include", "ldmae_hip.h")
 # csrc/probe/ldmae_diag.h: present only in the diagnostic build (LDMAE_HIP_LIB=.../libldmae_hip_diag.so, used by tools/)
-DIAG_SIGNATURES = {
-    "ldmae_tune": (_i, [_i, _i]),
-    "ldmae_tune_query": (_i, [_i]),
-    "ldmae_debug_nt_stamps": (None, [_vp]),
-}
+DIAG_SIGNATURES = _parse_file("csrc", "probe", "ldmae_diag.h")
 EPI_TILE_LAUNCH = 0x100
 EPI_HALF_LINES = 0x200
 EPI_F16_INF = 0x400

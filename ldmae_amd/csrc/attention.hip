@@ -2034,8 +2034,6 @@ extern "C" int ldmae_attention_bwd_pv(int dtype, const void* q, const void* k, c
 // ---- attention backward + QK-RMSNorm / RoPE backward in one (LightningDiT block, bf16): dq / dk never exist head-major; the packed dqkv
 // comes out complete (q | k through the norm / rope backward in the epilogues, v as attention_bwd_pv), with the norm-weight gradients
 // and the qkv bias gradient.  Replaces ldmae_attention_bwd_pv + ldmae_qknorm_rope_bwd for head dims 64 / 128.
-extern "C" long ldmae_colsum_workspace_bytes(int M, int N);
-extern "C" int ldmae_colsum(int dtype, const void* X, int ldx, int M, int N, float* out, float beta, float* workspace, void* stream);
 // the diagnostic build's one-pass kernel: its shapes (f32 dQ scratch [B*H][N][hd] at the end of the workspace)
 #ifdef LDMAE_DIAG
 static bool attn_onepass_shape(int N, int hd) { return hd == 64 && N % 128 == 0; }

@@ -568,9 +568,6 @@ extern "C" long ldmae_rmsnorm_modulate_bwd_workspace_bytes(int M, int D, int row
   return ((long)(M / rw) * 3 * D + (long)(M / rows_per_batch) * D) * 4;
 }
 
-extern "C" long ldmae_colsum_workspace_bytes(int M, int N);
-extern "C" int ldmae_colsum(int dtype, const void* X, int ldx, int M, int N, float* out, float beta, float* workspace, void* stream);
-extern "C" long ldmae_gate_bwd_workspace_bytes(int M, int D, int rows_per_batch);
 
 static int rmsnorm_modulate_bwd_core(int dtype, const void* dout, const float* x, const float* w, const float* scale, int mod_ld,
                                      const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, float* dw,
@@ -998,8 +995,6 @@ static unsigned qk_bwd_grid(long items, int lpr, int H) {
   const unsigned m = (unsigned)(H / a);
   return g >= m ? g / m * m : m;
 }
-extern "C" long ldmae_colsum_workspace_bytes(int M, int N);
-extern "C" int ldmae_colsum(int dtype, const void* X, int ldx, int M, int N, float* out, float beta, float* workspace, void* stream);
 extern "C" long ldmae_qknorm_rope_bwd_workspace_bytes(int B, int N, int H, int hd) {
   const int lpr = hd <= 64 ? 16 : 32;
   const long grid = qk_bwd_grid((long)B * N * H, lpr, H), groups = grid * (256 / lpr);
@@ -1163,8 +1158,6 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
     for (int i = threadIdx.x; i < D; i += 256) Pb[(size_t)blockIdx.x * D + i] = (red[i] + red[D + i]) + (red[2 * D + i] + red[3 * D + i]);
   }
 }
-extern "C" long ldmae_colsum_workspace_bytes(int M, int N);
-extern "C" int ldmae_colsum(int dtype, const void* X, int ldx, int M, int N, float* out, float beta, float* workspace, void* stream);
 extern "C" long ldmae_gate_bwd_workspace_bytes(int M, int D, int rows_per_batch) {
   const int rw = pick_rows_per_wg(rows_per_batch);
   if (rw <= 0) return 0;

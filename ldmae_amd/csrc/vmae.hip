@@ -197,8 +197,6 @@ __global__ __launch_bounds__(256) void restore_tokens_bwd_kernel(const float* __
     P[(size_t)blockIdx.x * D + c] = s2;
   }
 }
-extern "C" long ldmae_colsum_workspace_bytes(int M, int N);
-extern "C" int ldmae_colsum(int dtype, const void* X, int ldx, int M, int N, float* out, float beta, float* workspace, void* stream);
 static unsigned restore_grid(long rows) { const long g = (rows + 15) / 16; return (unsigned)(g < 2048 ? (g > 0 ? g : 1) : 2048); }
 extern "C" int ldmae_restore_tokens(const float* x, const float* mask_token, const float* pos, const long long* ids_restore, float* out, int B, int L,
                                     int keep, int D, void* stream) {

@@ -543,7 +543,6 @@ extern "C" int ldmae_attention_fwd_qkv_bounded(int dtype, const void* qkv, void*
 extern "C" long ldmae_vmae_encoder_fwd_tiled_workspace_bytes(int B, int tokens) {
   return (long)B * tokens * (3 * VD + VD) * 2 + (long)B * VH * tokens * 4 + ((long)B * VH * 2 * 4 + 15) / 16 * 16 * 64;      // (up to 64 blocks)
 }
-extern "C" int ldmae_attention_fwd_qkv(int dtype, const void* qkv, void* o, float* lse, int B, int H, int N, int hd, float scale, void* stream);
 template <bool F16>
 static int encoder_fwd_tiled(const float* x, float* out, const void* blob, void* workspace, int B, int tokens, int dim, int heads,
                              int hidden, int nblocks, float eps, void* stream) {

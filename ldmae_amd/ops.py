@@ -39,30 +39,73 @@ def _c(t):
     return t if t is None or t.is_contiguous() else t.contiguous()
 
 
-def _arg(t, what, dtype=None, shape=None, rows=False, out=False, numel=None):
-    """Layout check of one tensor handed to a GEMM-family entry point (attributes only: no synchronisation, no device work).
-    rows=True: the kernel reads it row by row with a leading dimension (t.stride(0)): elements of a row must be adjacent, rows may be
-    further apart (a row slice of a wider buffer stays zero-copy).  rows=False: the kernel reads it densely.  An input of another layout
-    is copied; an output (out=True) must already have the layout, else RuntimeError.  dtype / shape mismatches always raise; numel= checks
-    the element count of a dense operand the kernel addresses as a flat [rows, N] block whatever its torch shape."""
+def _arg(t, what, dtype=None, shape=None, rows=False, out=False, numel=None, like=None, align=0, at_least=0, copy=True):
+    """THE check of one tensor argument of a wrapper (attributes only: no synchronisation, no device work); `what` = "<op> <argument>".
+    None passes (an optional argument).  dtype: one torch dtype, or a tuple of accepted ones.  shape: the exact shape; entries that are no
+    integers are wildcards and name the dimension in the message ((B, "Ho", "Wo", 3), or "NHWC" for four of them), so a shape fixes the rank.
+    numel= / at_least=: the element count (at least that many) of an operand the kernel addresses flat, whatever its torch shape.  like=: an
+    anchor tensor whose device t must share.  align=: the address must be a multiple of that many bytes.
+    LAYOUT.  rows=True: the kernel reads it row by row with a leading dimension (t.stride(0)): elements of a row must be adjacent, rows may be
+    further apart (a row slice of a wider buffer stays zero-copy).  rows=False: the kernel reads it densely.  An input of another layout is
+    copied, unless copy=False (the kernel must see this very tensor); an output (out=True) must already have the layout.
+    Everything that does not hold raises RuntimeError: the op and argument, what was found against what was expected, then the whole contract."""
     if t is None:
         return None
-    if dtype is not None and t.dtype != dtype:
-        raise RuntimeError(f"{what}: dtype {t.dtype}, expected {dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{what}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-    if numel is not None and t.numel() != numel:
-        raise RuntimeError(f"{what}: {t.numel()} elements (shape {tuple(t.shape)}), expected {numel}")
+    if (dtype is not None and t.dtype != dtype and (type(dtype) is not tuple or t.dtype not in dtype)
+            or shape is not None and t.shape != shape and not _shape_fits(t.shape, shape)
+            or numel is not None and t.numel() != numel
+            or at_least and t.numel() < at_least or like is not None and t.device != like.device or align and t.data_ptr() % align):
+        raise _refusal(t, what, dtype, shape, rows, out, numel, like, align, at_least, copy)
     if rows:
         ok = t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
     else:
         ok = t.is_contiguous()
     if ok:
         return t
-    if out:
-        form = "rows with adjacent elements (stride(1) == 1, stride(0) >= columns)" if rows else "a contiguous tensor"
-        raise RuntimeError(f"{what}: the kernel writes {form}; got strides {tuple(t.stride())} for shape {tuple(t.shape)}")
+    if out or not copy:
+        raise _refusal(t, what, dtype, shape, rows, out, numel, like, align, at_least, copy)
     return t.contiguous()
+
+
+def _refusal(t, what, dtype, shape, rows, out, numel, like, align, at_least, copy):
+    """The error of _arg, off its fast path: the first thing that does not hold (in _arg's order; none of them: the layout), then the contract."""
+    if dtype is not None and t.dtype != dtype and (type(dtype) is not tuple or t.dtype not in dtype):
+        why = f"dtype {t.dtype}, expected {' or '.join(map(str, dtype)) if type(dtype) is tuple else dtype}"
+    elif shape is not None and not _shape_fits(t.shape, shape):
+        why = f"shape {tuple(t.shape)}, expected {_shape_text(shape)}"
+    elif numel is not None and t.numel() != numel:
+        why = f"{t.numel()} elements (shape {tuple(t.shape)}), expected {numel}"
+    elif at_least and t.numel() < at_least:
+        why = f"{t.numel()} elements (shape {tuple(t.shape)}), expected at least {at_least}"
+    elif like is not None and t.device != like.device:
+        why = f"device {t.device}, expected {like.device}"
+    elif align and t.data_ptr() % align:
+        why = f"the tensor's storage must be {align}-byte aligned"
+    else:
+        form = "rows with adjacent elements (stride(1) == 1, stride(0) >= columns)" if rows else "a contiguous tensor"
+        why = f"the kernel {'writes' if out else 'reads'} {form}; got strides {tuple(t.stride())} for shape {tuple(t.shape)}"
+    need = ["a" if copy and not out else "a row-strided" if rows else "a contiguous"]
+    if dtype is not None:
+        need.append(" or ".join(str(d)[6:] for d in (dtype if type(dtype) is tuple else (dtype,))))
+    if shape is not None:
+        need.append(_shape_text(shape))
+    need.append("tensor")
+    if numel is not None or at_least:
+        need.append(f"of {numel} elements" if numel is not None else f"of at least {at_least} element(s)")
+    if like is not None:
+        need.append(f"on {like.device}")
+    if align:
+        need.append(f"in {align}-byte aligned storage")
+    return RuntimeError(f"{what}: {why} (need {' '.join(need)})")
+
+
+def _shape_fits(got, want):
+    """Slow path of _arg's shape check: `want` has wildcard entries (anything that is no int), or is no tuple."""
+    return len(got) == len(want) and all(not isinstance(w, int) or w == g for g, w in zip(got, want))
+
+
+def _shape_text(shape):
+    return shape if isinstance(shape, str) else "[" + ", ".join(map(str, shape)) + "]"
 
 
 def _ld(t):
@@ -1185,30 +1228,22 @@ def gelu_tanh_bwd(dout, pre):
 
 # ----------------------------------------------------------------------------- FID evaluation (csrc/inception.hip), NHWC f32
 # A channel slice is (tensor [B, H, W, Ctot], offset, C): the kernels read / write channels [offset, offset + C) of every pixel.
-
-def _nhwc(t, what):
-    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
-        raise RuntimeError(f"{what}: need a contiguous f32 NHWC tensor, got {tuple(t.shape)} {t.dtype}")
-    return t
-
+# From here to the end of the file the kernels work on the caller's tensors as they are: every _arg below says copy=False, or out=True for an output.
 
 def conv2d_nhwc(x, w, bias=None, stride=(1, 1), padding=(0, 0), relu=True, xoff=0, cin=None, out=None, ooff=0):
     """Implicit-GEMM convolution on the exact-f32 MFMA.  x [B, H, W, ldx] read at channels [xoff, xoff + cin); w [Cout, kh, kw, Cin] f32;
     out [B, Ho, Wo, ldo] written at channels [ooff, ooff + Cout) (allocated as [B, Ho, Wo, Cout] when None); bias + ReLU epilogue."""
-    _nhwc(x, "conv2d_nhwc")
+    _arg(x, "conv2d_nhwc x", torch.float32, "NHWC", copy=False)
     B, H, W, ldx = x.shape
+    _arg(w, "conv2d_nhwc weight", torch.float32, ("Cout", "kh", "kw", "Cin" if cin is None else cin), copy=False, like=x)
     Cout, kh, kw, Cin = w.shape
-    cin = Cin if cin is None else cin
-    if cin != Cin or w.dtype != torch.float32 or not w.is_contiguous():
-        raise RuntimeError(f"conv2d_nhwc: weight {tuple(w.shape)} {w.dtype} does not match {cin} input channels")
+    _arg(bias, "conv2d_nhwc bias", torch.float32, (Cout,), copy=False, like=x)
     sh, sw = stride
     ph, pw = padding
     Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
     if out is None:
         out = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
-    _nhwc(out, "conv2d_nhwc")
-    if tuple(out.shape[:3]) != (B, Ho, Wo):
-        raise RuntimeError(f"conv2d_nhwc: output {tuple(out.shape)} is not [{B}, {Ho}, {Wo}, *]")
+    _arg(out, "conv2d_nhwc out", torch.float32, (B, Ho, Wo, "ldo"), out=True, like=x)
     call("ldmae_conv2d_nhwc_f32", ptr(x), ldx, xoff, ptr(w), ptr(bias), ptr(out), out.shape[3], ooff, B, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw,
          1 if relu else 0, stream())
     return out
@@ -1216,23 +1251,20 @@ def conv2d_nhwc(x, w, bias=None, stride=(1, 1), padding=(0, 0), relu=True, xoff=
 
 def pool2d_nhwc(x, mode, k=3, stride=1, pad=0, xoff=0, c=None, out=None, ooff=0):
     """3x3-style pooling of channel slices: mode "max" (padding never wins) or "avg" (count_include_pad=False)."""
-    _nhwc(x, "pool2d_nhwc")
+    _arg(x, "pool2d_nhwc x", torch.float32, "NHWC", copy=False)
     B, H, W, ldx = x.shape
     c = ldx - xoff if c is None else c
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     if out is None:
         out = torch.empty(B, Ho, Wo, c, dtype=torch.float32, device=x.device)
-    _nhwc(out, "pool2d_nhwc")
-    if tuple(out.shape[:3]) != (B, Ho, Wo):
-        raise RuntimeError(f"pool2d_nhwc: output {tuple(out.shape)} is not [{B}, {Ho}, {Wo}, *]")
+    _arg(out, "pool2d_nhwc out", torch.float32, (B, Ho, Wo, "ldo"), out=True, like=x)
     call("ldmae_pool2d_nhwc_f32", {"max": 0, "avg": 1}[mode], ptr(x), ldx, xoff, ptr(out), out.shape[3], ooff, B, H, W, c, k, stride, pad, stream())
     return out
 
 
 def global_avgpool_nhwc(x, xoff=0, c=None):
     """[B, H, W, ldx] (or [B, HW, ldx]) -> [B, c]: the mean over all pixels of channels [xoff, xoff + c)."""
-    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() not in (3, 4):
-        raise RuntimeError(f"global_avgpool_nhwc: need a contiguous f32 [B, H, W, C] or [B, HW, C] tensor, got {tuple(x.shape)} {x.dtype}")
+    _arg(x, "global_avgpool_nhwc x", torch.float32, ("B", "HW", "C") if x.dim() == 3 else "NHWC", copy=False)
     B, ldx = x.shape[0], x.shape[-1]
     HW = x[0, ..., 0].numel()
     c = ldx - xoff if c is None else c
@@ -1241,49 +1273,40 @@ def global_avgpool_nhwc(x, xoff=0, c=None):
     return out
 
 
-def fid_preprocess(img, size=299):
-    """uint8 [B, H, W, 3] RGB -> f32 [B, size, size, 3] = F.interpolate(img / 255, (size, size), bilinear, align_corners=False) * 2 - 1."""
-    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
-        raise RuntimeError(f"fid_preprocess: need a contiguous uint8 [B, H, W, 3] tensor, got {tuple(img.shape)} {img.dtype}")
+def _preprocess(op, img, size):
+    """fid_preprocess / adm_preprocess: one wrapper, two resampling rules (entry point ldmae_<op>)."""
+    _arg(img, op + " img", torch.uint8, ("B", "H", "W", 3), copy=False)
     B, H, W, _ = img.shape
     out = torch.empty(B, size, size, 3, dtype=torch.float32, device=img.device)
-    call("ldmae_fid_preprocess", ptr(img), ptr(out), B, H, W, size, size, stream())
+    call("ldmae_" + op, ptr(img), ptr(out), B, H, W, size, size, stream())
     return out
+
+
+def fid_preprocess(img, size=299):
+    """uint8 [B, H, W, 3] RGB -> f32 [B, size, size, 3] = F.interpolate(img / 255, (size, size), bilinear, align_corners=False) * 2 - 1."""
+    return _preprocess("fid_preprocess", img, size)
 
 
 def fid_stats_accumulate(feats, shift, s1, s2):
     """s1 [D] += sum_r (f_r - shift); s2 [D, D] += sum_r (f_r - shift)(f_r - shift)^T, f64 accumulators on the device."""
-    if feats.dtype != torch.float32 or feats.dim() != 2 or not feats.is_contiguous():
-        raise RuntimeError(f"fid_stats_accumulate: need contiguous f32 [n, D] features, got {tuple(feats.shape)} {feats.dtype}")
+    _arg(feats, "fid_stats_accumulate feats", torch.float32, ("n", "D"), copy=False)
     n, D = feats.shape
-    if shift.shape != (D,) or shift.dtype != torch.float32 or s1.shape != (D,) or s2.shape != (D, D) or s1.dtype != torch.float64 \
-            or s2.dtype != torch.float64 or not s2.is_contiguous():
-        raise RuntimeError("fid_stats_accumulate: shift must be f32 [D], the accumulators f64 [D] and [D, D]")
+    _arg(shift, "fid_stats_accumulate shift", torch.float32, (D,), copy=False, like=feats)
+    _arg(s1, "fid_stats_accumulate s1", torch.float64, (D,), out=True, like=feats)
+    _arg(s2, "fid_stats_accumulate s2", torch.float64, (D, D), out=True, like=feats)
     call("ldmae_fid_stats_accumulate", ptr(feats), n, D, ptr(shift), ptr(s1), ptr(s2), stream())
 
 
 # ----------------------------------------------------------------------------- ADM evaluator (csrc/adm_eval.hip), f32
-def _rows_f32(t, what, cols=None):
-    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (cols is not None and t.shape[1] != cols):
-        want = f"[*, {cols}]" if cols is not None else "[rows, D]"
-        raise RuntimeError(f"{what}: need a contiguous f32 {want} tensor, got {tuple(t.shape)} {t.dtype}")
-    return t
-
-
 def adm_preprocess(img, size=299):
     """uint8 [B, H, W, 3] RGB -> f32 [B, size, size, 3] = (TF1 legacy ResizeBilinear(img) - 128) / 128: the ADM Inception graph's
     pre-processing (src = dst * in / out, no half-pixel centres)."""
-    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or not img.is_contiguous():
-        raise RuntimeError(f"adm_preprocess: need a contiguous uint8 [B, H, W, 3] tensor, got {tuple(img.shape)} {img.dtype}")
-    B, H, W, _ = img.shape
-    out = torch.empty(B, size, size, 3, dtype=torch.float32, device=img.device)
-    call("ldmae_adm_preprocess", ptr(img), ptr(out), B, H, W, size, size, stream())
-    return out
+    return _preprocess("adm_preprocess", img, size)
 
 
 def adm_spatial_tap(x, xoff=0, c=7):
     """[B, H, W, ldx] -> f32 [B, H * W * c]: channels [xoff, xoff + c) of every pixel, flattened in (h, w, c) order (TF's NHWC reshape)."""
-    _nhwc(x, "adm_spatial_tap")
+    _arg(x, "adm_spatial_tap x", torch.float32, "NHWC", copy=False)
     B, H, W, ldx = x.shape
     if xoff < 0 or c <= 0 or xoff + c > ldx:
         raise RuntimeError(f"adm_spatial_tap: channel slice [{xoff}, {xoff + c}) of {ldx}")
@@ -1294,7 +1317,7 @@ def adm_spatial_tap(x, xoff=0, c=7):
 
 def row_sqnorms(x):
     """f32 [M, D] -> f32 [M]: |x_m|^2 accumulated in f64, rounded once."""
-    _rows_f32(x, "row_sqnorms")
+    _arg(x, "row_sqnorms x", torch.float32, ("M", "D"), copy=False)
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     call("ldmae_row_sqnorms_f32", ptr(x), x.shape[0], x.shape[1], ptr(out), stream())
     return out
@@ -1302,8 +1325,8 @@ def row_sqnorms(x):
 
 def pairwise_logits(u, w):
     """u [M, D] . w [N, D]^T -> f32 [M, N] on the exact-f32 MFMA, no bias (the ADM softmax graph's MatMul)."""
-    _rows_f32(u, "pairwise_logits u")
-    _rows_f32(w, "pairwise_logits w", u.shape[1])
+    _arg(u, "pairwise_logits u", torch.float32, ("M", "D"), copy=False)
+    _arg(w, "pairwise_logits w", torch.float32, ("N", u.shape[1]), copy=False, like=u)
     out = torch.empty(u.shape[0], w.shape[0], dtype=torch.float32, device=u.device)
     call("ldmae_pairwise_logits", ptr(u), u.shape[0], u.shape[1], ptr(w), w.shape[0], ptr(out), stream())
     return out
@@ -1330,14 +1353,13 @@ def knn_radii(x, nhood_sizes=(3,), norms=None, nsplit=None):
     """f32 [N, D] -> f32 [N, len(nhood_sizes)]: column t is the value at sorted index nhood_sizes[t] of the row's squared distances
     max(|x_i|^2 - 2 x_i.x_j + |x_j|^2, 0) to every row (itself included), as np.partition(d, seq)[:, k].  nsplit: column splits of the
     pass (default default_col_splits); the result is bitwise the same for every nsplit."""
-    _rows_f32(x, "knn_radii")
+    _arg(x, "knn_radii x", torch.float32, ("N", "D"), copy=False)
     N, D = x.shape
     nh = _nhood(nhood_sizes)
     if N <= max(nh):
         raise RuntimeError(f"knn_radii: {N} rows hold no neighbour at sorted index {max(nh)}")
     norms = row_sqnorms(x) if norms is None else norms
-    if norms.dtype != torch.float32 or tuple(norms.shape) != (N,) or not norms.is_contiguous():
-        raise RuntimeError(f"knn_radii: norms must be contiguous f32 [{N}], got {tuple(norms.shape)} {norms.dtype}")
+    _arg(norms, "knn_radii norms", torch.float32, (N,), copy=False, like=x)
     nsplit = default_col_splits(N, N) if nsplit is None else int(nsplit)
     if nsplit < 1:
         raise RuntimeError(f"knn_radii: nsplit {nsplit} (>= 1)")
@@ -1352,20 +1374,19 @@ def knn_radii(x, nhood_sizes=(3,), norms=None, nsplit=None):
 def pr_flags(u, ru, v, rv, nu=None, nv=None, nsplit=None):
     """Manifold membership between u [M, D] (radii ru [M, K]) and v [N, D] (radii rv [N, K]): (u_in [M, K], v_in [N, K]) int32, with
     u_in[i, k] = any_j d(i, j) <= rv[j, k] and v_in[j, k] = any_i d(i, j) <= ru[i, k] (evaluator.py DistanceBlock.less_thans)."""
-    _rows_f32(u, "pr_flags u")
-    _rows_f32(v, "pr_flags v", u.shape[1])
+    _arg(u, "pr_flags u", torch.float32, ("M", "D"), copy=False)
     M, D = u.shape
+    _arg(v, "pr_flags v", torch.float32, ("N", D), copy=False, like=u)
     N = v.shape[0]
-    K = ru.shape[1] if ru.dim() == 2 else -1
-    _rows_f32(ru, "pr_flags ru")
-    _rows_f32(rv, "pr_flags rv", K)
-    if ru.shape[0] != M or rv.shape[0] != N or not 1 <= K <= 8:
-        raise RuntimeError(f"pr_flags: radii {tuple(ru.shape)} / {tuple(rv.shape)} do not match {M} / {N} rows (1..8 columns)")
+    _arg(ru, "pr_flags ru", torch.float32, (M, "K"), copy=False, like=u)
+    K = ru.shape[1]
+    _arg(rv, "pr_flags rv", torch.float32, (N, K), copy=False, like=u)
+    if not 1 <= K <= 8:
+        raise RuntimeError(f"pr_flags: radii {tuple(ru.shape)} / {tuple(rv.shape)}: 1..8 columns")
     nu = row_sqnorms(u) if nu is None else nu
     nv = row_sqnorms(v) if nv is None else nv
-    for t, n, what in ((nu, M, "nu"), (nv, N, "nv")):
-        if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise RuntimeError(f"pr_flags: {what} must be contiguous f32 [{n}], got {tuple(t.shape)} {t.dtype}")
+    _arg(nu, "pr_flags nu", torch.float32, (M,), copy=False, like=u)
+    _arg(nv, "pr_flags nv", torch.float32, (N,), copy=False, like=u)
     nsplit = default_col_splits(M, N) if nsplit is None else int(nsplit)
     if nsplit < 1:
         raise RuntimeError(f"pr_flags: nsplit {nsplit} (>= 1)")
@@ -1378,7 +1399,7 @@ def pr_flags(u, ru, v, rv, nu=None, nv=None, nsplit=None):
 def adm_softmax_is(logits, split=5000):
     """logits f32 [M, C] -> (h f64 [M], S f64 [ceil(M / split), C]): h[i] = sum_c p log p (0 log 0 = 0), S[s] = sum of p over rows
     [s * split, (s + 1) * split), p = softmax(logits) in f32; fixed-order sums (bitwise reproducible)."""
-    _rows_f32(logits, "adm_softmax_is")
+    _arg(logits, "adm_softmax_is logits", torch.float32, ("M", "C"), copy=False)
     M, Cc = logits.shape
     if split < 1:
         raise RuntimeError(f"adm_softmax_is: split {split} (>= 1)")
@@ -1390,86 +1411,97 @@ def adm_softmax_is(logits, split=5000):
 
 
 # ----------------------------------------------------------------------------- tokenizer evaluation (csrc/tokenizer_eval.hip), f32
-def _nchw(t, what, channels=None):
-    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or (channels is not None and t.shape[1] != channels):
-        want = f"[B, {channels}, H, W]" if channels is not None else "[B, C, H, W]"
-        raise RuntimeError(f"{what}: need a contiguous f32 NCHW {want} tensor, got {tuple(t.shape)} {t.dtype}")
-    return t
+# ... and LPIPS: forward, backward (csrc/lpips_bwd.hip: f32 NHWC, no atomics) and the 16-bit path (csrc/lpips_f16.hip: fp16 forward, bf16 data
+# gradient).  The C side serves an f32 entry point and its 16-bit twin from one template; so does this file: one private body per pair, named
+# after the f32 wrapper, with the facts that differ as parameters (op = the public name, and "ldmae_" + op the entry point unless given).
 
-
-def _same(a, b, what):
-    if tuple(a.shape) != tuple(b.shape) or a.device != b.device:
-        raise RuntimeError(f"{what}: {tuple(a.shape)} on {a.device} and {tuple(b.shape)} on {b.device} must match")
+def _lpips_prep(op, input, target, out_dtype, C):
+    _arg(input, op + " input", torch.float32, ("B", 3, "H", "W"), copy=False)
+    _arg(target, op + " target", torch.float32, input.shape, copy=False, like=input)
+    B, _, H, W = input.shape
+    out = torch.empty(2 * B, H, W, C, dtype=out_dtype, device=input.device)
+    call("ldmae_" + op, ptr(input), ptr(target), ptr(out), B, H, W, stream())
+    return out
 
 
 def lpips_prep(input, target):
     """LPIPS' ScalingLayer on both images: NCHW f32 [B, 3, H, W] x 2 -> NHWC f32 [2B, H, W, 4] = (x - shift) / scale, input first, channel 3
     zero (the Cin-4 VEC path of conv2d_nhwc)."""
-    _nchw(input, "lpips_prep input", 3)
-    _nchw(target, "lpips_prep target", 3)
-    _same(input, target, "lpips_prep")
-    B, _, H, W = input.shape
-    out = torch.empty(2 * B, H, W, 4, dtype=torch.float32, device=input.device)
-    call("ldmae_lpips_prep", ptr(input), ptr(target), ptr(out), B, H, W, stream())
+    return _lpips_prep("lpips_prep", input, target, torch.float32, 4)
+
+
+def _lpips_tap(op, f, lin_w, f_dtype, align):
+    """The tap f [2B, h, w, C] and its lin weight [C], common to the four lpips_layer wrappers -> (lin_w, B, h, w, C)."""
+    _arg(f, op + " f", f_dtype, "NHWC", copy=False, align=align)
+    n, h, w, C = f.shape
+    if n % 2 or C not in (64, 128, 256, 512):
+        raise RuntimeError(f"{op}: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
+    return _arg(lin_w, op + " lin_w", torch.float32, numel=C, like=f), n // 2, h, w, C
+
+
+def _lpips_layer(op, f, lin_w, out, f_dtype, align):
+    lin_w, B, h, w, C = _lpips_tap(op, f, lin_w, f_dtype, align)
+    _arg(out, op + " out", torch.float32, (B,), out=True, like=f)
+    ws = workspace(L.load().ldmae_lpips_workspace_bytes(B, h, w), f.device, "lpips")
+    call("ldmae_" + op, ptr(f), ptr(lin_w), ptr(out), B, h, w, C, ptr(ws), stream())
     return out
 
 
 def lpips_layer(f, lin_w, out):
     """One VGG tap f [2B, h, w, C] (C = 64, 128, 256, 512) and its lin weight [C]: out [B] += mean_hw sum_c w_c (f^_b - f^_(B+b))^2, f^ the
     channel-normalised features (f / (|f| + 1e-10)).  out is accumulated in place (f32 [B])."""
-    _nhwc(f, "lpips_layer")
-    n, h, w, C = f.shape
-    if n % 2 or C not in (64, 128, 256, 512):
-        raise RuntimeError(f"lpips_layer: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
-    B = n // 2
-    lin_w = _arg(lin_w, "lpips_layer lin_w", torch.float32, numel=C)
-    if out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous() or lin_w.device != f.device or out.device != f.device:
-        raise RuntimeError(f"lpips_layer: out must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(out.shape)} {out.dtype}")
-    ws = workspace(L.load().ldmae_lpips_workspace_bytes(B, h, w), f.device, "lpips")
-    call("ldmae_lpips_layer", ptr(f), ptr(lin_w), ptr(out), B, h, w, C, ptr(ws), stream())
-    return out
+    return _lpips_layer("lpips_layer", f, lin_w, out, torch.float32, 0)
 
 
-# ----------------------------------------------------------------------------- LPIPS backward (csrc/lpips_bwd.hip), f32 NHWC, no atomics
-def conv3x3_relu_dgrad_nhwc(dy, y, w_rot, out=None):
-    """Data gradient of y = relu(conv3x3(x, w) + b) (stride 1, pad 1): dx [B, H, W, Cx] = conv3x3(dy * [y > 0], w_rot) with dy, y [B, H, W, Cy] and
-    w_rot [Cx, 3, 3, Cy] (models.lpips.rotate_weight of the forward weight).  The ReLU mask is taken from y inside the operand gather."""
-    _nhwc(dy, "conv3x3_relu_dgrad_nhwc dy")
-    _nhwc(y, "conv3x3_relu_dgrad_nhwc y")
-    _same(dy, y, "conv3x3_relu_dgrad_nhwc")
-    B, H, W, Cy = dy.shape
-    if w_rot.dtype != torch.float32 or w_rot.dim() != 4 or tuple(w_rot.shape[1:]) != (3, 3, Cy) or not w_rot.is_contiguous() or w_rot.device != dy.device:
-        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc: rotated weight {tuple(w_rot.shape)} {w_rot.dtype} on {w_rot.device} is not a contiguous f32 "
-                           f"[Cx, 3, 3, {Cy}] tensor on {dy.device}")
-    if Cy % 4:
-        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc: {Cy} gradient channels (a multiple of 4)")
+def _conv3x3_relu_dgrad(op, entry, dy, y, w_rot, out, y_dtype, w_dtype, multiple, align):
+    _arg(y, op + " y", y_dtype, "NHWC", copy=False, align=align)
+    B, H, W, Cy = y.shape
+    _arg(dy, op + " dy", torch.float32, y.shape, copy=False, like=y, align=align)
+    _arg(w_rot, op + " rotated weight", w_dtype, ("Cx", 3, 3, Cy), copy=False, like=y, align=align)
+    if Cy % multiple or dy.numel() == 0:
+        raise RuntimeError(f"{op}: {Cy} gradient channels (a multiple of {multiple}) of a non-empty tensor")
     Cx = w_rot.shape[0]
     if out is None:
         out = torch.empty(B, H, W, Cx, dtype=torch.float32, device=dy.device)
-    _nhwc(out, "conv3x3_relu_dgrad_nhwc out")
-    if tuple(out.shape) != (B, H, W, Cx) or out.device != dy.device:
-        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc: out {tuple(out.shape)} on {out.device} is not [{B}, {H}, {W}, {Cx}] on {dy.device}")
-    call("ldmae_conv3x3_relu_dgrad_nhwc_f32", ptr(dy), ptr(y), ptr(w_rot), ptr(out), B, H, W, Cy, Cx, stream())
+    _arg(out, op + " out", torch.float32, (B, H, W, Cx), out=True, like=y)
+    call(entry, ptr(dy), ptr(y), ptr(w_rot), ptr(out), B, H, W, Cy, Cx, stream())
+    return out
+
+
+def conv3x3_relu_dgrad_nhwc(dy, y, w_rot, out=None):
+    """Data gradient of y = relu(conv3x3(x, w) + b) (stride 1, pad 1): dx [B, H, W, Cx] = conv3x3(dy * [y > 0], w_rot) with dy, y [B, H, W, Cy] and
+    w_rot [Cx, 3, 3, Cy] (models.lpips.rotate_weight of the forward weight).  The ReLU mask is taken from y inside the operand gather."""
+    return _conv3x3_relu_dgrad("conv3x3_relu_dgrad_nhwc", "ldmae_conv3x3_relu_dgrad_nhwc_f32", dy, y, w_rot, out, torch.float32, torch.float32, 4, 0)
+
+
+def _maxpool2x2_bwd(op, entry, dy, x, out, x_dtype, align):
+    _arg(x, op + " x", x_dtype, "NHWC", copy=False, align=align)
+    B, H, W, C = x.shape
+    _arg(dy, op + " dy", torch.float32, (B, H // 2, W // 2, C), copy=False, like=x)
+    if C % 4 or x.numel() == 0:
+        raise RuntimeError(f"{op}: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 4 channels")
+    if out is None:
+        out = torch.empty(B, H, W, C, dtype=torch.float32, device=x.device)
+    _arg(out, op + " out", torch.float32, x.shape, out=True, like=x)
+    call(entry, ptr(dy) if dy.numel() else None, ptr(x), ptr(out), B, H, W, C, stream())
     return out
 
 
 def maxpool2x2_bwd_nhwc(dy, x, out=None):
     """Backward of pool2d_nhwc(x, "max", k=2, stride=2): dx [B, H, W, C] from dy [B, H // 2, W // 2, C] and the pooled input x.  dy goes to the
     window's maximum (the first in row-major order on a tie, as torch); odd last rows / columns get 0; every element of dx is written."""
-    _nhwc(x, "maxpool2x2_bwd_nhwc x")
-    _nhwc(dy, "maxpool2x2_bwd_nhwc dy")
-    B, H, W, C = x.shape
-    if tuple(dy.shape) != (B, H // 2, W // 2, C) or dy.device != x.device:
-        raise RuntimeError(f"maxpool2x2_bwd_nhwc: dy {tuple(dy.shape)} on {dy.device} is not [{B}, {H // 2}, {W // 2}, {C}] on {x.device}")
-    if C % 4 or x.numel() == 0:
-        raise RuntimeError(f"maxpool2x2_bwd_nhwc: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 4 channels")
-    if out is None:
-        out = torch.empty_like(x)
-    _nhwc(out, "maxpool2x2_bwd_nhwc out")
-    if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
-        raise RuntimeError(f"maxpool2x2_bwd_nhwc: out {tuple(out.shape)} on {out.device} does not match x {tuple(x.shape)} on {x.device}")
-    call("ldmae_maxpool2x2_bwd_nhwc_f32", ptr(dy) if dy.numel() else None, ptr(x), ptr(out), B, H, W, C, stream())
-    return out
+    return _maxpool2x2_bwd("maxpool2x2_bwd_nhwc", "ldmae_maxpool2x2_bwd_nhwc_f32", dy, x, out, torch.float32, 0)
+
+
+def _lpips_layer_bwd(op, f, lin_w, g, d_input, d_target, accumulate, f_dtype, align):
+    lin_w, B, h, w, C = _lpips_tap(op, f, lin_w, f_dtype, align)
+    _arg(g, op + " g", torch.float32, (B,), copy=False, like=f)
+    if d_input is None and d_target is None:
+        raise RuntimeError(f"{op}: neither d_input nor d_target given: nothing to compute")
+    _arg(d_input, op + " d_input", torch.float32, (B, h, w, C), out=True, like=f)
+    _arg(d_target, op + " d_target", torch.float32, (B, h, w, C), out=True, like=f)
+    call("ldmae_" + op, ptr(f), ptr(lin_w), ptr(g), ptr(d_input), ptr(d_target), B, h, w, C, 1 if accumulate else 0, stream())
+    return d_input, d_target
 
 
 def lpips_layer_bwd(f, lin_w, g, d_input=None, d_target=None, accumulate=False):
@@ -1477,90 +1509,52 @@ def lpips_layer_bwd(f, lin_w, g, d_input=None, d_target=None, accumulate=False):
     second (target) half is written into d_input / d_target [B, h, w, C]; None = that half is not wanted (at least one is).  accumulate=True adds
     into the buffers (which then hold the following pool's backward), else they are overwritten.  A pixel whose channels are all zero in a half
     gets exactly 0 there (torch gives NaN).  -> (d_input, d_target)."""
-    _nhwc(f, "lpips_layer_bwd")
-    n, h, w, C = f.shape
-    if n % 2 or C not in (64, 128, 256, 512):
-        raise RuntimeError(f"lpips_layer_bwd: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
-    B = n // 2
-    lin_w = _arg(lin_w, "lpips_layer_bwd lin_w", torch.float32, numel=C)
-    if g.dtype != torch.float32 or tuple(g.shape) != (B,) or not g.is_contiguous() or g.device != f.device or lin_w.device != f.device:
-        raise RuntimeError(f"lpips_layer_bwd: g must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(g.shape)} {g.dtype} on {g.device}")
-    if d_input is None and d_target is None:
-        raise RuntimeError("lpips_layer_bwd: neither d_input nor d_target given: nothing to compute")
-    for d, what in ((d_input, "d_input"), (d_target, "d_target")):
-        if d is not None and (d.dtype != torch.float32 or tuple(d.shape) != (B, h, w, C) or not d.is_contiguous() or d.device != f.device):
-            raise RuntimeError(f"lpips_layer_bwd: {what} must be a contiguous f32 [{B}, {h}, {w}, {C}] tensor on {f.device}, got {tuple(d.shape)} {d.dtype}")
-    call("ldmae_lpips_layer_bwd", ptr(f), ptr(lin_w), ptr(g), ptr(d_input), ptr(d_target), B, h, w, C, 1 if accumulate else 0, stream())
-    return d_input, d_target
+    return _lpips_layer_bwd("lpips_layer_bwd", f, lin_w, g, d_input, d_target, accumulate, torch.float32, 0)
+
+
+def _lpips_prep_bwd(op, g, C):
+    _arg(g, op + " g", torch.float32, ("B", "H", "W", C), copy=False)
+    B, H, W, _ = g.shape
+    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=g.device)
+    call("ldmae_" + op, ptr(g), ptr(out), B, H, W, stream())
+    return out
 
 
 def lpips_prep_bwd(g):
     """Backward of lpips_prep for one half: g NHWC f32 [B, H, W, 4] (the data gradient of conv1_1) -> NCHW f32 [B, 3, H, W] = g[..., c] / scale[c]."""
-    _nhwc(g, "lpips_prep_bwd")
-    B, H, W, C = g.shape
-    if C != 4:
-        raise RuntimeError(f"lpips_prep_bwd: gradient {tuple(g.shape)}: need [B, H, W, 4]")
-    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=g.device)
-    call("ldmae_lpips_prep_bwd", ptr(g), ptr(out), B, H, W, stream())
-    return out
-
-
-# ----------------------------------------------------------------------------- LPIPS in 16 bits (csrc/lpips_f16.hip): fp16 forward, bf16 data gradient
-def _nhwc_t(t, what, dtype):
-    if t.dtype != dtype or t.dim() != 4 or not t.is_contiguous():
-        raise RuntimeError(f"{what}: need a contiguous {str(dtype)[6:]} NHWC tensor, got {tuple(t.shape)} {t.dtype}")
-    return t
-
-
-def _aligned16(t, what):
-    if t.data_ptr() % 16:
-        raise RuntimeError(f"{what}: the tensor's storage must be 16-byte aligned")
+    return _lpips_prep_bwd("lpips_prep_bwd", g, 4)
 
 
 def lpips_prep_f16(input, target):
     """lpips_prep's f32 arithmetic, then one rounding: NCHW f32 [B, 3, H, W] x 2 -> NHWC fp16 [2B, H, W, 8], input first, channels 3 .. 7 zero
     (the Cin % 8 == 0 operand of conv3x3_relu_nhwc_f16)."""
-    _nchw(input, "lpips_prep_f16 input", 3)
-    _nchw(target, "lpips_prep_f16 target", 3)
-    _same(input, target, "lpips_prep_f16")
-    B, _, H, W = input.shape
-    out = torch.empty(2 * B, H, W, 8, dtype=torch.float16, device=input.device)
-    call("ldmae_lpips_prep_f16", ptr(input), ptr(target), ptr(out), B, H, W, stream())
-    return out
+    return _lpips_prep("lpips_prep_f16", input, target, torch.float16, 8)
 
 
 def conv3x3_relu_nhwc_f16(x, w, bias=None, out=None):
     """relu(conv3x3(x, w) + bias), stride 1, pad 1, on the fp16 MFMA with f32 accumulation: x fp16 [B, H, W, Cin] (Cin % 8 == 0), w fp16
     [Cout, 3, 3, Cin], bias f32 [Cout]; the f32 result is rounded once to fp16 (saturating at +-65504) into out [B, H, W, Cout] (a contiguous
     view of a larger tensor is taken as it is; allocated when None)."""
-    _nhwc_t(x, "conv3x3_relu_nhwc_f16 x", torch.float16)
+    _arg(x, "conv3x3_relu_nhwc_f16 x", torch.float16, "NHWC", copy=False, align=16)
     B, H, W, Cin = x.shape
-    if w.dtype != torch.float16 or w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, Cin) or not w.is_contiguous() or w.device != x.device:
-        raise RuntimeError(f"conv3x3_relu_nhwc_f16: weight {tuple(w.shape)} {w.dtype} on {w.device} is not a contiguous fp16 [Cout, 3, 3, {Cin}] "
-                           f"tensor on {x.device}")
+    _arg(w, "conv3x3_relu_nhwc_f16 weight", torch.float16, ("Cout", 3, 3, Cin), copy=False, like=x, align=16)
     if Cin % 8 or x.numel() == 0:
         raise RuntimeError(f"conv3x3_relu_nhwc_f16: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 8 channels")
     Cout = w.shape[0]
-    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,) or not bias.is_contiguous() or bias.device != x.device):
-        raise RuntimeError(f"conv3x3_relu_nhwc_f16: bias must be a contiguous f32 [{Cout}] tensor on {x.device}, got {tuple(bias.shape)} {bias.dtype}")
+    _arg(bias, "conv3x3_relu_nhwc_f16 bias", torch.float32, (Cout,), copy=False, like=x)
     if out is None:
         out = torch.empty(B, H, W, Cout, dtype=torch.float16, device=x.device)
-    _nhwc_t(out, "conv3x3_relu_nhwc_f16 out", torch.float16)
-    if tuple(out.shape) != (B, H, W, Cout) or out.device != x.device:
-        raise RuntimeError(f"conv3x3_relu_nhwc_f16: out {tuple(out.shape)} on {out.device} is not [{B}, {H}, {W}, {Cout}] on {x.device}")
-    _aligned16(x, "conv3x3_relu_nhwc_f16 x")
-    _aligned16(w, "conv3x3_relu_nhwc_f16 w")
+    _arg(out, "conv3x3_relu_nhwc_f16 out", torch.float16, (B, H, W, Cout), out=True, like=x)
     call("ldmae_conv3x3_relu_nhwc_f16", ptr(x), ptr(w), ptr(bias), ptr(out), B, H, W, Cin, Cout, stream())
     return out
 
 
 def maxpool2x2_nhwc_f16(x):
     """2x2 / 2 max pool of fp16 NHWC [B, H, W, C] (C % 8 == 0, H, W >= 2) -> [B, H // 2, W // 2, C]; the odd last row / column is dropped."""
-    _nhwc_t(x, "maxpool2x2_nhwc_f16", torch.float16)
+    _arg(x, "maxpool2x2_nhwc_f16 x", torch.float16, "NHWC", copy=False, align=16)
     B, H, W, C = x.shape
     if C % 8 or B == 0 or H < 2 or W < 2:
         raise RuntimeError(f"maxpool2x2_nhwc_f16: x {tuple(x.shape)}: need at least 2 x 2 pixels and a multiple of 8 channels")
-    _aligned16(x, "maxpool2x2_nhwc_f16 x")
     out = torch.empty(B, H // 2, W // 2, C, dtype=torch.float16, device=x.device)
     call("ldmae_maxpool2x2_nhwc_f16", ptr(x), ptr(out), B, H, W, C, stream())
     return out
@@ -1568,101 +1562,37 @@ def maxpool2x2_nhwc_f16(x):
 
 def lpips_layer_f16(f, lin_w, out):
     """lpips_layer on fp16 taps f [2B, h, w, C]: the same f32 arithmetic on the (exactly converted) values; out f32 [B] accumulated in place."""
-    _nhwc_t(f, "lpips_layer_f16", torch.float16)
-    n, h, w, C = f.shape
-    if n % 2 or C not in (64, 128, 256, 512):
-        raise RuntimeError(f"lpips_layer_f16: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
-    B = n // 2
-    lin_w = _arg(lin_w, "lpips_layer_f16 lin_w", torch.float32, numel=C)
-    if out.dtype != torch.float32 or tuple(out.shape) != (B,) or not out.is_contiguous() or lin_w.device != f.device or out.device != f.device:
-        raise RuntimeError(f"lpips_layer_f16: out must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(out.shape)} {out.dtype}")
-    _aligned16(f, "lpips_layer_f16 f")
-    ws = workspace(L.load().ldmae_lpips_workspace_bytes(B, h, w), f.device, "lpips")
-    call("ldmae_lpips_layer_f16", ptr(f), ptr(lin_w), ptr(out), B, h, w, C, ptr(ws), stream())
-    return out
+    return _lpips_layer("lpips_layer_f16", f, lin_w, out, torch.float16, 16)
 
 
 def conv3x3_relu_dgrad_nhwc_bf16(dy, y, w_rot, out=None):
     """conv3x3_relu_dgrad_nhwc with 16-bit operands: dy f32 [B, H, W, Cy] (Cy % 8 == 0), y the stored fp16 activation of the same shape, w_rot bf16
     [Cx, 3, 3, Cy]; dx f32 [B, H, W, Cx] = conv3x3(bf16(dy * [y > 0]), w_rot), f32 accumulation on the bf16 MFMA."""
-    _nhwc(dy, "conv3x3_relu_dgrad_nhwc_bf16 dy")
-    _nhwc_t(y, "conv3x3_relu_dgrad_nhwc_bf16 y", torch.float16)
-    _same(dy, y, "conv3x3_relu_dgrad_nhwc_bf16")
-    B, H, W, Cy = dy.shape
-    if w_rot.dtype != torch.bfloat16 or w_rot.dim() != 4 or tuple(w_rot.shape[1:]) != (3, 3, Cy) or not w_rot.is_contiguous() or w_rot.device != dy.device:
-        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc_bf16: rotated weight {tuple(w_rot.shape)} {w_rot.dtype} on {w_rot.device} is not a contiguous "
-                           f"bf16 [Cx, 3, 3, {Cy}] tensor on {dy.device}")
-    if Cy % 8 or dy.numel() == 0:
-        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc_bf16: {Cy} gradient channels (a multiple of 8) of a non-empty tensor")
-    Cx = w_rot.shape[0]
-    if out is None:
-        out = torch.empty(B, H, W, Cx, dtype=torch.float32, device=dy.device)
-    _nhwc(out, "conv3x3_relu_dgrad_nhwc_bf16 out")
-    if tuple(out.shape) != (B, H, W, Cx) or out.device != dy.device:
-        raise RuntimeError(f"conv3x3_relu_dgrad_nhwc_bf16: out {tuple(out.shape)} on {out.device} is not [{B}, {H}, {W}, {Cx}] on {dy.device}")
-    for t, what in ((dy, "dy"), (y, "y"), (w_rot, "w_rot")):
-        _aligned16(t, f"conv3x3_relu_dgrad_nhwc_bf16 {what}")
-    call("ldmae_conv3x3_relu_dgrad_nhwc_bf16", ptr(dy), ptr(y), ptr(w_rot), ptr(out), B, H, W, Cy, Cx, stream())
-    return out
+    return _conv3x3_relu_dgrad("conv3x3_relu_dgrad_nhwc_bf16", "ldmae_conv3x3_relu_dgrad_nhwc_bf16", dy, y, w_rot, out, torch.float16,
+                               torch.bfloat16, 8, 16)
 
 
 def maxpool2x2_bwd_nhwc_xf16(dy, x, out=None):
     """maxpool2x2_bwd_nhwc with the pooled input x stored as fp16; dy and dx f32."""
-    _nhwc_t(x, "maxpool2x2_bwd_nhwc_xf16 x", torch.float16)
-    _nhwc(dy, "maxpool2x2_bwd_nhwc_xf16 dy")
-    B, H, W, C = x.shape
-    if tuple(dy.shape) != (B, H // 2, W // 2, C) or dy.device != x.device:
-        raise RuntimeError(f"maxpool2x2_bwd_nhwc_xf16: dy {tuple(dy.shape)} on {dy.device} is not [{B}, {H // 2}, {W // 2}, {C}] on {x.device}")
-    if C % 4 or x.numel() == 0:
-        raise RuntimeError(f"maxpool2x2_bwd_nhwc_xf16: x {tuple(x.shape)}: need a non-empty tensor with a multiple of 4 channels")
-    if out is None:
-        out = torch.empty(B, H, W, C, dtype=torch.float32, device=x.device)
-    _nhwc(out, "maxpool2x2_bwd_nhwc_xf16 out")
-    if tuple(out.shape) != tuple(x.shape) or out.device != x.device:
-        raise RuntimeError(f"maxpool2x2_bwd_nhwc_xf16: out {tuple(out.shape)} on {out.device} does not match x {tuple(x.shape)} on {x.device}")
-    _aligned16(x, "maxpool2x2_bwd_nhwc_xf16 x")
-    call("ldmae_maxpool2x2_bwd_nhwc_xf16", ptr(dy) if dy.numel() else None, ptr(x), ptr(out), B, H, W, C, stream())
-    return out
+    return _maxpool2x2_bwd("maxpool2x2_bwd_nhwc_xf16", "ldmae_maxpool2x2_bwd_nhwc_xf16", dy, x, out, torch.float16, 16)
 
 
 def lpips_layer_bwd_f16(f, lin_w, g, d_input=None, d_target=None, accumulate=False):
     """lpips_layer_bwd on fp16 taps f [2B, h, w, C]; g, d_input, d_target f32, the same arithmetic.  -> (d_input, d_target)."""
-    _nhwc_t(f, "lpips_layer_bwd_f16", torch.float16)
-    n, h, w, C = f.shape
-    if n % 2 or C not in (64, 128, 256, 512):
-        raise RuntimeError(f"lpips_layer_bwd_f16: features {tuple(f.shape)}: need [2B, h, w, C] with C in 64, 128, 256, 512")
-    B = n // 2
-    lin_w = _arg(lin_w, "lpips_layer_bwd_f16 lin_w", torch.float32, numel=C)
-    if g.dtype != torch.float32 or tuple(g.shape) != (B,) or not g.is_contiguous() or g.device != f.device or lin_w.device != f.device:
-        raise RuntimeError(f"lpips_layer_bwd_f16: g must be a contiguous f32 [{B}] tensor on {f.device}, got {tuple(g.shape)} {g.dtype} on {g.device}")
-    if d_input is None and d_target is None:
-        raise RuntimeError("lpips_layer_bwd_f16: neither d_input nor d_target given: nothing to compute")
-    for d, what in ((d_input, "d_input"), (d_target, "d_target")):
-        if d is not None and (d.dtype != torch.float32 or tuple(d.shape) != (B, h, w, C) or not d.is_contiguous() or d.device != f.device):
-            raise RuntimeError(f"lpips_layer_bwd_f16: {what} must be a contiguous f32 [{B}, {h}, {w}, {C}] tensor on {f.device}, got {tuple(d.shape)} {d.dtype}")
-    _aligned16(f, "lpips_layer_bwd_f16 f")
-    call("ldmae_lpips_layer_bwd_f16", ptr(f), ptr(lin_w), ptr(g), ptr(d_input), ptr(d_target), B, h, w, C, 1 if accumulate else 0, stream())
-    return d_input, d_target
+    return _lpips_layer_bwd("lpips_layer_bwd_f16", f, lin_w, g, d_input, d_target, accumulate, torch.float16, 16)
 
 
 def lpips_prep_bwd_c8(g):
     """lpips_prep_bwd from the 8-channel data gradient of the fp16 path's conv1_1: g NHWC f32 [B, H, W, 8] -> NCHW f32 [B, 3, H, W] = g[..., c] /
     scale[c]; channels 3 .. 7 (exactly zero: their weight rows are) are ignored."""
-    _nhwc(g, "lpips_prep_bwd_c8")
-    B, H, W, C = g.shape
-    if C != 8:
-        raise RuntimeError(f"lpips_prep_bwd_c8: gradient {tuple(g.shape)}: need [B, H, W, 8]")
-    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=g.device)
-    call("ldmae_lpips_prep_bwd_c8", ptr(g), ptr(out), B, H, W, stream())
-    return out
+    return _lpips_prep_bwd("lpips_prep_bwd_c8", g, 8)
 
 
 def ssim(preds, target, lo=-1.0, hi=1.0, data_range=2.0):
     """Per-image SSIM f32 [B] of NCHW f32 [B, C, H, W] (H, W >= 11): torchmetrics' default Gaussian SSIM of the inputs clamped to [lo, hi]
     (+-inf: no clamp) with c1 = (0.01 data_range)^2, c2 = (0.03 data_range)^2."""
-    _nchw(preds, "ssim preds")
-    _nchw(target, "ssim target")
-    _same(preds, target, "ssim")
+    _arg(preds, "ssim preds", torch.float32, "BCHW", copy=False)
+    _arg(target, "ssim target", torch.float32, preds.shape, copy=False, like=preds)
     B, C, H, W = preds.shape
     if H < 11 or W < 11:
         raise RuntimeError(f"ssim: {H} x {W} images are smaller than the 11 x 11 Gaussian window")
@@ -1675,9 +1605,8 @@ def ssim(preds, target, lo=-1.0, hi=1.0, data_range=2.0):
 def recon_quantize_sse(decoded, ref):
     """What the reference writes as PNG, for both images, and their exact squared error: NCHW f32 [B, 3, H, W] x 2 ->
     (dec8, ref8) uint8 NHWC [B, H, W, 3] = (uint8) clamp(127.5 x + 128, 0, 255), sse int64 [B] = sum of (dec8 - ref8)^2."""
-    _nchw(decoded, "recon_quantize decoded", 3)
-    _nchw(ref, "recon_quantize ref", 3)
-    _same(decoded, ref, "recon_quantize")
+    _arg(decoded, "recon_quantize decoded", torch.float32, ("B", 3, "H", "W"), copy=False)
+    _arg(ref, "recon_quantize ref", torch.float32, decoded.shape, copy=False, like=decoded)
     B, _, H, W = decoded.shape
     dec8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=decoded.device)
     ref8 = torch.empty_like(dec8)
@@ -1689,9 +1618,10 @@ def recon_quantize_sse(decoded, ref):
 
 def sse_u8(a, b):
     """int64 [B]: exact sum of (a - b)^2 over each image of two uint8 tensors [B, ...] of one shape."""
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() < 2 or not a.is_contiguous() or not b.is_contiguous():
-        raise RuntimeError(f"sse_u8: need contiguous uint8 [B, ...] tensors, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
-    _same(a, b, "sse_u8")
+    _arg(a, "sse_u8 a", torch.uint8, copy=False)
+    if a.dim() < 2:
+        raise RuntimeError(f"sse_u8: need [B, ...] tensors of at least two dimensions, got {tuple(a.shape)}")
+    _arg(b, "sse_u8 b", torch.uint8, a.shape, copy=False, like=a)
     B, n = a.shape[0], a[0].numel()
     sse = torch.empty(B, dtype=torch.int64, device=a.device)
     ws = workspace(L.load().ldmae_sse_workspace_bytes(B, n), a.device, "sse")
@@ -1704,17 +1634,9 @@ VAE_PLAIN, VAE_NORM_ACT, VAE_DOWN, VAE_UP = 0, 1, 2, 3
 VAE_GROUPS, VAE_EPS = 32, 1e-6          # the reference's Normalize: GroupNorm(32, C, eps=1e-6)
 
 
-def _vec(t, what, n):
-    if t is None:
-        return None
-    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous():
-        raise RuntimeError(f"{what}: need a contiguous f32 [{n}] tensor, got {tuple(t.shape)} {t.dtype}")
-    return t
-
-
 def groupnorm_stats_nhwc(x, groups=VAE_GROUPS, eps=VAE_EPS):
     """(mean, rstd) f32 [B, groups] of x [B, H, W, C]: biased variance over the H * W * (C / groups) elements of every (image, group)."""
-    _nhwc(x, "groupnorm_stats_nhwc")
+    _arg(x, "groupnorm_stats_nhwc x", torch.float32, "NHWC", copy=False)
     B, H, W, C = x.shape
     mean = torch.empty(B, groups, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
@@ -1722,31 +1644,24 @@ def groupnorm_stats_nhwc(x, groups=VAE_GROUPS, eps=VAE_EPS):
     return mean, rstd
 
 
-def _stats(stats, B, groups, what):
-    mean, rstd = stats
-    for t in (mean, rstd):
-        if t.dtype != torch.float32 or tuple(t.shape) != (B, groups) or not t.is_contiguous():
-            raise RuntimeError(f"{what}: mean / rstd must be contiguous f32 [{B}, {groups}], got {tuple(t.shape)} {t.dtype}")
-    return mean, rstd
-
-
 def groupnorm_apply_nhwc(x, stats, gamma, beta, silu=False, out=None, out_dtype=torch.float32):
     """gamma (x - mean) rstd + beta of x [B, H, W, C] from groupnorm_stats_nhwc's (mean, rstd); silu=True: y * sigmoid(y) of that.
     out_dtype=torch.float16: the same f32 value stored as fp16 (round to nearest even, saturating at +-65504): the operand of the two-pass
     TF32-class convolution."""
-    _nhwc(x, "groupnorm_apply_nhwc")
+    _arg(x, "groupnorm_apply_nhwc x", torch.float32, "NHWC", copy=False)
     B, H, W, C = x.shape
-    mean, rstd = _stats(stats, B, stats[0].shape[1], "groupnorm_apply_nhwc")
+    mean, rstd = stats
+    _arg(mean, "groupnorm_apply_nhwc mean", torch.float32, (B, "groups"), copy=False, like=x)
+    _arg(rstd, "groupnorm_apply_nhwc rstd", torch.float32, mean.shape, copy=False, like=x)
+    _arg(gamma, "groupnorm_apply_nhwc gamma", torch.float32, (C,), copy=False, like=x)
+    _arg(beta, "groupnorm_apply_nhwc beta", torch.float32, (C,), copy=False, like=x)
     if out_dtype not in (torch.float32, torch.float16):
         raise RuntimeError(f"groupnorm_apply_nhwc: out_dtype {out_dtype} (float32 or float16)")
     if out is None:
         out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    if out.dtype != out_dtype or out.dim() != 4 or not out.is_contiguous():
-        raise RuntimeError(f"groupnorm_apply_nhwc out: need a contiguous {out_dtype} NHWC tensor, got {tuple(out.shape)} {out.dtype}")
-    _same(out, x, "groupnorm_apply_nhwc")
+    _arg(out, "groupnorm_apply_nhwc out", out_dtype, x.shape, out=True, like=x)
     call("ldmae_groupnorm_apply_nhwc_f32" if out_dtype == torch.float32 else "ldmae_groupnorm_apply_nhwc_f16out", ptr(x), ptr(mean), ptr(rstd),
-         ptr(_vec(gamma, "groupnorm_apply_nhwc gamma", C)), ptr(_vec(beta, "groupnorm_apply_nhwc beta", C)), ptr(out), B, H * W, C, mean.shape[1],
-         1 if silu else 0, stream())
+         ptr(gamma), ptr(beta), ptr(out), B, H * W, C, mean.shape[1], 1 if silu else 0, stream())
     return out
 
 
@@ -1766,15 +1681,9 @@ def conv3x3_vae_nhwc(x, w, bias=None, mode=VAE_PLAIN, res=None, stats=None, gamm
     precision "tf32": w is the fp16 pack (ops.cast of the f32 one), Cin % 8 == 0; both operands of every product are rounded once to fp16
     (saturating), accumulation, bias, residual and output are f32.  x may then be fp16 in VAE_PLAIN (groupnorm_apply_nhwc(out_dtype=float16))."""
     tf32 = _precision(precision, "conv3x3_vae_nhwc")
-    if tf32 and x.dtype == torch.float16:
-        if x.dim() != 4 or not x.is_contiguous():
-            raise RuntimeError(f"conv3x3_vae_nhwc: need a contiguous NHWC tensor, got {tuple(x.shape)}")
-    else:
-        _nhwc(x, "conv3x3_vae_nhwc")
+    _arg(x, "conv3x3_vae_nhwc x", (torch.float32, torch.float16) if tf32 else torch.float32, "NHWC", copy=False)
     B, H, W, Cin = x.shape
-    wdt = torch.float16 if tf32 else torch.float32
-    if w.dim() != 4 or tuple(w.shape[1:]) != (3, 3, Cin) or w.dtype != wdt or not w.is_contiguous():
-        raise RuntimeError(f"conv3x3_vae_nhwc: weight {tuple(w.shape)} {w.dtype} is not a contiguous {wdt} [Cout, 3, 3, {Cin}]")
+    _arg(w, "conv3x3_vae_nhwc weight", torch.float16 if tf32 else torch.float32, ("Cout", 3, 3, Cin), copy=False, like=x)
     Cout = w.shape[0]
     if mode == VAE_DOWN:
         Ho, Wo = (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
@@ -1791,17 +1700,17 @@ def conv3x3_vae_nhwc(x, w, bias=None, mode=VAE_PLAIN, res=None, stats=None, gamm
     if mode == VAE_NORM_ACT:
         if stats is None or gamma is None or beta is None:
             raise RuntimeError("conv3x3_vae_nhwc: norm-act needs stats, gamma and beta")
-        groups = stats[0].shape[1]
-        mean, rstd = _stats(stats, B, groups, "conv3x3_vae_nhwc")
-        _vec(gamma, "conv3x3_vae_nhwc gamma", Cin)
-        _vec(beta, "conv3x3_vae_nhwc beta", Cin)
+        mean, rstd = stats
+        _arg(mean, "conv3x3_vae_nhwc mean", torch.float32, (B, "groups"), copy=False, like=x)
+        _arg(rstd, "conv3x3_vae_nhwc rstd", torch.float32, mean.shape, copy=False, like=x)
+        groups = mean.shape[1]
+        _arg(gamma, "conv3x3_vae_nhwc gamma", torch.float32, (Cin,), copy=False, like=x)
+        _arg(beta, "conv3x3_vae_nhwc beta", torch.float32, (Cin,), copy=False, like=x)
+    _arg(bias, "conv3x3_vae_nhwc bias", torch.float32, (Cout,), copy=False, like=x)
+    _arg(res, "conv3x3_vae_nhwc res", torch.float32, (B, Ho, Wo, Cout), copy=False, like=x)
     out = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
-    if res is not None:
-        _nhwc(res, "conv3x3_vae_nhwc res")
-        _same(res, out, "conv3x3_vae_nhwc res")
-    tail = (ptr(x), ptr(w), ptr(_vec(bias, "conv3x3_vae_nhwc bias", Cout)), ptr(res), ptr(mean), ptr(rstd),
-            ptr(gamma if mode == VAE_NORM_ACT else None), ptr(beta if mode == VAE_NORM_ACT else None), groups, 1 if silu else 0, ptr(out), B, H, W,
-            Cin, Cout, stream())
+    tail = (ptr(x), ptr(w), ptr(bias), ptr(res), ptr(mean), ptr(rstd), ptr(gamma if mode == VAE_NORM_ACT else None),
+            ptr(beta if mode == VAE_NORM_ACT else None), groups, 1 if silu else 0, ptr(out), B, H, W, Cin, Cout, stream())
     if tf32:
         call("ldmae_conv3x3_vae_nhwc_f16", mode, dt(x.dtype), *tail)
     else:
@@ -1813,25 +1722,22 @@ def conv1x1_res_nhwc(x, w, bias=None, res=None, precision="f32"):
     """x [..., Cin] (contiguous f32) times w [Cout, Cin]^T + bias + res [..., Cout]: the 1x1 convolution with a residual epilogue.
     precision "tf32": w is the fp16 pack, Cin % 8 == 0; the arithmetic contract of conv3x3_vae_nhwc."""
     tf32 = _precision(precision, "conv1x1_res_nhwc")
-    wdt = torch.float16 if tf32 else torch.float32
-    if x.dtype != torch.float32 or not x.is_contiguous() or w.dtype != wdt or not w.is_contiguous() or w.dim() != 2 or w.shape[1] != x.shape[-1]:
-        raise RuntimeError(f"conv1x1_res_nhwc: x {tuple(x.shape)} {x.dtype} and w {tuple(w.shape)} {w.dtype} must be contiguous f32 [..., Cin] and "
-                           f"{wdt} [Cout, Cin]")
+    _arg(x, "conv1x1_res_nhwc x", torch.float32, copy=False)
+    _arg(w, "conv1x1_res_nhwc weight", torch.float16 if tf32 else torch.float32, ("Cout", x.shape[-1]), copy=False, like=x)
     Cout, Cin = w.shape
+    _arg(bias, "conv1x1_res_nhwc bias", torch.float32, (Cout,), copy=False, like=x)
+    _arg(res, "conv1x1_res_nhwc res", torch.float32, (*x.shape[:-1], Cout), copy=False, like=x)
     out = torch.empty(*x.shape[:-1], Cout, dtype=torch.float32, device=x.device)
-    if res is not None:
-        if res.dtype != torch.float32 or not res.is_contiguous():
-            raise RuntimeError("conv1x1_res_nhwc: res must be a contiguous f32 tensor")
-        _same(res, out, "conv1x1_res_nhwc res")
-    call("ldmae_conv1x1_res_nhwc_f16" if tf32 else "ldmae_conv1x1_res_nhwc_f32", ptr(x), ptr(w), ptr(_vec(bias, "conv1x1_res_nhwc bias", Cout)),
-         ptr(res), ptr(out), x.numel() // Cin, Cin, Cout, stream())
+    call("ldmae_conv1x1_res_nhwc_f16" if tf32 else "ldmae_conv1x1_res_nhwc_f32", ptr(x), ptr(w), ptr(bias), ptr(res), ptr(out), x.numel() // Cin, Cin,
+         Cout, stream())
     return out
 
 
 def softmax_rows_(s, cols, scale=1.0):
     """In place on s [rows, ld] f32 (contiguous): s[:, :cols] = softmax(scale * s[:, :cols], dim=1); s[:, cols:] = 0."""
-    if s.dtype != torch.float32 or s.dim() != 2 or not s.is_contiguous() or not 0 < cols <= s.shape[1]:
-        raise RuntimeError(f"softmax_rows_: need a contiguous f32 [rows, ld >= cols] tensor, got {tuple(s.shape)} {s.dtype}, cols {cols}")
+    _arg(s, "softmax_rows_ s", torch.float32, ("rows", "ld"), out=True)
+    if not 0 < cols <= s.shape[1]:
+        raise RuntimeError(f"softmax_rows_: cols {cols} of rows of {s.shape[1]} (ld >= cols > 0)")
     call("ldmae_softmax_rows_f32", ptr(s), s.shape[1], s.shape[0], cols, float(scale), stream())
     return s
 
@@ -1857,22 +1763,14 @@ def attention_wide(q, k, vt, scale, bias=None):
 
 
 # ----------------------------------------------------------------------------- adaptive dopri5 ODE sampler (csrc/ode.hip), f32
-def _ode_vec(t, what, n):
-    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
-        raise RuntimeError(f"{what}: need a contiguous f32 tensor of {n} elements, got {tuple(t.shape)} {t.dtype}")
-    return t
+# State vectors are addressed flat: _arg(numel=n).  Device scalars (h, t, the error ratio) and scratch are f32 memory of at_least= so many
+# elements.  Everything shares the device of the state.
 
-
-def _ode_slab(k, n):
-    if k.dtype != torch.float32 or k.dim() != 2 or k.shape[0] != 7 or not k.is_contiguous() or k.shape[1] < n or k.shape[1] % 4:
-        raise RuntimeError(f"ode: the stage slab must be a contiguous f32 [7, ld] tensor with ld % 4 == 0 and ld >= {n}, got {tuple(k.shape)} {k.dtype}")
+def _ode_slab(k, n, y):
+    _arg(k, "ode: the stage slab", torch.float32, (7, "ld"), copy=False, like=y)
+    if k.shape[1] < n or k.shape[1] % 4:
+        raise RuntimeError(f"ode: the stage slab must be a contiguous f32 [7, ld] tensor with ld % 4 == 0 and ld >= {n}, got {tuple(k.shape)}")
     return k
-
-
-def _ode_scalar(t, what, n=1):
-    if t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous():
-        raise RuntimeError(f"{what}: need f32 device memory of {n} element(s), got {tuple(t.shape)} {t.dtype}")
-    return t
 
 
 def ode_slab_ld(n):
@@ -1890,9 +1788,13 @@ def rk_stage(y, k_slab, coef, h_dev, out, t_dev=None, ct=0.0, t_out=None):
     every element of t_out = t + ct * h as well, the time vector of the next model evaluation.  Returns out."""
     n = y.numel()
     m = len(coef)
-    _ode_vec(y, "rk_stage y", n), _ode_vec(out, "rk_stage out", n), _ode_slab(k_slab, n), _ode_scalar(h_dev, "rk_stage h_dev")
+    _arg(y, "rk_stage y", torch.float32, copy=False)
+    _arg(out, "rk_stage out", torch.float32, numel=n, out=True, like=y)
+    _ode_slab(k_slab, n, y)
+    _arg(h_dev, "rk_stage h_dev", torch.float32, copy=False, like=y, at_least=1)
     if t_out is not None:
-        _ode_scalar(t_dev, "rk_stage t_dev"), _ode_vec(t_out, "rk_stage t_out", t_out.numel())
+        _arg(t_dev, "rk_stage t_dev", torch.float32, copy=False, like=y, at_least=1)
+        _arg(t_out, "rk_stage t_out", torch.float32, out=True, like=y)
     cf = (ctypes.c_float * 7)(*[float(c) for c in coef])
     call("ldmae_rk_stage_f32", ptr(y), ptr(k_slab), k_slab.shape[1], cf, m, ptr(h_dev), ptr(out), n, ptr(t_dev), float(ct), ptr(t_out),
          0 if t_out is None else t_out.numel(), stream())
@@ -1903,8 +1805,12 @@ def dopri5_finish(y, k_slab, h_dev, atol, rtol, y1, partial, ratio_dev):
     """y1 = y + h * sum b_j k_j and ratio_dev = rms over ALL elements of (h * sum e_j k_j) / (atol + rtol * max(|y|, |y1|)), in one pass plus a
     one-block fold; fixed summation order (bitwise reproducible), no atomics.  partial: >= ode_partials(n) f32."""
     n = y.numel()
-    _ode_vec(y, "dopri5_finish y", n), _ode_vec(y1, "dopri5_finish y1", n), _ode_slab(k_slab, n), _ode_scalar(h_dev, "dopri5_finish h_dev")
-    _ode_scalar(partial, "dopri5_finish partial", ode_partials(n)), _ode_scalar(ratio_dev, "dopri5_finish ratio_dev")
+    _arg(y, "dopri5_finish y", torch.float32, copy=False)
+    _arg(y1, "dopri5_finish y1", torch.float32, numel=n, out=True, like=y)
+    _ode_slab(k_slab, n, y)
+    _arg(h_dev, "dopri5_finish h_dev", torch.float32, copy=False, like=y, at_least=1)
+    _arg(partial, "dopri5_finish partial", torch.float32, out=True, like=y, at_least=ode_partials(n))
+    _arg(ratio_dev, "dopri5_finish ratio_dev", torch.float32, out=True, like=y, at_least=1)
     call("ldmae_dopri5_finish_f32", ptr(y), ptr(k_slab), k_slab.shape[1], ptr(h_dev), float(atol), float(rtol), ptr(y1), ptr(partial), ptr(ratio_dev),
          n, stream())
     return y1
@@ -1913,9 +1819,10 @@ def dopri5_finish(y, k_slab, h_dev, atol, rtol, y1, partial, ratio_dev):
 def rms_norm_scaled(x, y, atol, rtol, partial, out_dev):
     """out_dev = sqrt(mean((x / (atol + rtol * |y|))^2)) (y None: y = x), the norm of the starting-step rule; same two-stage fold as dopri5_finish."""
     n = x.numel()
-    _ode_vec(x, "rms_norm_scaled x", n), _ode_scalar(partial, "rms_norm_scaled partial", ode_partials(n)), _ode_scalar(out_dev, "rms_norm_scaled out_dev")
-    if y is not None:
-        _ode_vec(y, "rms_norm_scaled y", n)
+    _arg(x, "rms_norm_scaled x", torch.float32, copy=False)
+    _arg(y, "rms_norm_scaled y", torch.float32, numel=n, copy=False, like=x)
+    _arg(partial, "rms_norm_scaled partial", torch.float32, out=True, like=x, at_least=ode_partials(n))
+    _arg(out_dev, "rms_norm_scaled out_dev", torch.float32, out=True, like=x, at_least=1)
     call("ldmae_rms_norm_scaled_f32", ptr(x), ptr(y), float(atol), float(rtol), ptr(partial), ptr(out_dev), n, stream())
     return out_dev
 
@@ -1924,22 +1831,25 @@ def dopri5_interp(y0, y1, y_mid, k_slab, h_dev, t0_dev, t_eval, out):
     """out = the quartic through y0, y1, y_mid with end slopes k_slab[0], k_slab[6], at x = (t_eval - t0) / h; coefficients never stored."""
     n = y0.numel()
     for t, w in ((y0, "y0"), (y1, "y1"), (y_mid, "y_mid"), (out, "out")):
-        _ode_vec(t, "dopri5_interp " + w, n)
-    _ode_slab(k_slab, n), _ode_scalar(h_dev, "dopri5_interp h_dev"), _ode_scalar(t0_dev, "dopri5_interp t0_dev")
+        _arg(t, "dopri5_interp " + w, torch.float32, numel=n, copy=False, like=y0)
+    _ode_slab(k_slab, n, y0)
+    _arg(h_dev, "dopri5_interp h_dev", torch.float32, copy=False, like=y0, at_least=1)
+    _arg(t0_dev, "dopri5_interp t0_dev", torch.float32, copy=False, like=y0, at_least=1)
     call("ldmae_dopri5_interp_f32", ptr(y0), ptr(y1), ptr(y_mid), ptr(k_slab), k_slab.shape[1], ptr(h_dev), ptr(t0_dev), float(t_eval), ptr(out), n, stream())
     return out
 
 
 def dopri5_advance(ratio_dev, h_dev, t_dev, status_dev):
     """The step-size controller on the device (one thread): status_dev[0..5] = (accepted, ratio, t, h, t', h'); t_dev, h_dev updated in place."""
-    _ode_scalar(ratio_dev, "dopri5_advance ratio_dev"), _ode_scalar(h_dev, "dopri5_advance h_dev"), _ode_scalar(t_dev, "dopri5_advance t_dev")
-    _ode_scalar(status_dev, "dopri5_advance status_dev", 6)
+    for t, w, n in ((ratio_dev, "ratio_dev", 1), (h_dev, "h_dev", 1), (t_dev, "t_dev", 1), (status_dev, "status_dev", 6)):
+        _arg(t, "dopri5_advance " + w, torch.float32, copy=False, like=ratio_dev, at_least=n)
     call("ldmae_dopri5_advance", ptr(ratio_dev), ptr(h_dev), ptr(t_dev), ptr(status_dev), stream())
 
 
 def dopri5_initial_step(d_dev, phase, h_dev):
     """The Hairer-Norsett-Wanner starting step from the norms d_dev = (d0, d1, d2 * h0, h0): phase 0 writes h0, phase 1 the step, to h_dev."""
-    _ode_scalar(d_dev, "dopri5_initial_step d_dev", 4), _ode_scalar(h_dev, "dopri5_initial_step h_dev")
+    _arg(d_dev, "dopri5_initial_step d_dev", torch.float32, out=True, at_least=4)
+    _arg(h_dev, "dopri5_initial_step h_dev", torch.float32, out=True, like=d_dev, at_least=1)
     call("ldmae_dopri5_initial_step", ptr(d_dev), int(phase), ptr(h_dev), stream())
 
 
@@ -1957,14 +1867,15 @@ def rademacher(shape, seed, counter, device):
 def rowdot(a, b=None, out=None):
     """out[r] = sum over everything but dim 0 of a[r] * b[r] (b None: b = a, the row sums of squares); f32, contiguous, two-stage fixed-order sum."""
     b = a if b is None else b
-    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous() or a.dim() < 1 \
-            or a.numel() == 0:
-        raise RuntimeError(f"rowdot: two contiguous non-empty f32 tensors of one shape expected, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    _arg(a, "rowdot a", torch.float32, copy=False)
+    _arg(b, "rowdot b", torch.float32, a.shape, copy=False, like=a)
+    if a.dim() < 1 or a.numel() == 0:
+        raise RuntimeError(f"rowdot: two non-empty tensors of at least one dimension expected, got {tuple(a.shape)}")
     B, m = a.shape[0], a.numel() // a.shape[0]
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=a.device)
     else:
-        _ode_vec(out, "rowdot out", B)
+        _arg(out, "rowdot out", torch.float32, numel=B, out=True, like=a)
     partial = torch.empty(int(L.load().ldmae_rowdot_partials(B, m)), dtype=torch.float32, device=a.device)
     call("ldmae_rowdot_f32", ptr(a), ptr(b), ptr(out), B, m, ptr(partial), stream())
     return out
@@ -1975,7 +1886,8 @@ def likelihood_finish(sumsq, delta, m):
     integrated divergence."""
     import math
     B = sumsq.numel()
-    _ode_vec(sumsq, "likelihood_finish sumsq", B), _ode_vec(delta, "likelihood_finish delta", B)
+    _arg(sumsq, "likelihood_finish sumsq", torch.float32, copy=False)
+    _arg(delta, "likelihood_finish delta", torch.float32, numel=B, copy=False, like=sumsq)
     out = torch.empty(B, dtype=torch.float32, device=sumsq.device)
     call("ldmae_likelihood_finish_f32", ptr(sumsq), ptr(delta), -m / 2.0 * math.log(2 * math.pi), ptr(out), B, stream())
     return out
@@ -1989,7 +1901,7 @@ def normal(shape, seed, counter, device, out=None):
         out = torch.empty(shape, dtype=torch.float32, device=device)
     if out.numel() == 0:
         raise RuntimeError("normal: empty shape")
-    _ode_vec(out, "normal out", out.numel())
+    _arg(out, "normal out", torch.float32, out=True)
     call("ldmae_normal_f32", ptr(out), out.numel(), int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1), stream())
     return out
 
@@ -2002,15 +1914,12 @@ def sde_combine(ins, coef, out, noise_coef=0.0, z=None, seed=None, counter=0, me
     n, m = out.numel(), len(ins)
     if not 1 <= m <= 4 or len(coef) != m:
         raise RuntimeError(f"sde_combine: 1 to 4 inputs with one coefficient each, got {m} inputs and {len(coef)} coefficients")
+    _arg(out, "sde_combine out", torch.float32, out=True)
     for j, t in enumerate(ins):
-        _ode_vec(t, f"sde_combine input {j}", n)
-    _ode_vec(out, "sde_combine out", n)
-    if z is not None:
-        _ode_vec(z, "sde_combine z", n)
-    if mean_out is not None:
-        _ode_vec(mean_out, "sde_combine mean_out", n)
-    if t_out is not None:
-        _ode_vec(t_out, "sde_combine t_out", t_out.numel())
+        _arg(t, f"sde_combine input {j}", torch.float32, numel=n, copy=False, like=out)
+    _arg(z, "sde_combine z", torch.float32, numel=n, copy=False, like=out)
+    _arg(mean_out, "sde_combine mean_out", torch.float32, numel=n, out=True, like=out)
+    _arg(t_out, "sde_combine t_out", torch.float32, out=True, like=out)
     mode = 1 if z is not None else (2 if seed is not None else 0)
     p = [ptr(t) for t in ins] + [None] * (4 - m)
     cf = (ctypes.c_float * 4)(*([float(c) for c in coef] + [0.0] * (4 - m)))

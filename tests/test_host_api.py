@@ -150,3 +150,59 @@ def test_reference_method_names_exist():
     le = LabelEmbedder(10, 8, 0.1)
     out = le.token_drop(torch.tensor([1, 2, 3]), force_drop_ids=torch.tensor([1, 0, 1]))
     assert out.tolist() == [10, 2, 10]
+
+
+def test_header_parser_maps_every_c_type_it_knows_and_refuses_the_rest():
+    """_lib.SIGNATURES is derived from the header: the parser's type map, on a synthetic header with every form the real one uses."""
+    from ldmae_amd._lib import parse_header
+    C = ctypes
+    sigs = parse_header('''
+        /* a comment with a semicolon; and a parenthesis ( that closes nothing,
+         * int not_a_prototype(int a); */
+        #ifndef X_H
+        #define X_H 1   /* trailing; comment ( */
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        const char* x_name(void);
+        long x_bytes(int M,
+                     long n,      /* between ( parameters; */
+                     float beta);
+        int x_copy(int count, void* const* dst, const void* const* src, const long* n, void* stream);
+        int x_draw(float* out, long n, unsigned long long seed, long long k, double lr, const unsigned char* drop);
+        void x_stamps(void* buf);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    ''')
+    assert sigs == {"x_name": (C.c_char_p, []),
+                    "x_bytes": (C.c_long, [C.c_int, C.c_long, C.c_float]),
+                    "x_copy": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                    "x_draw": (C.c_int, [C.c_void_p, C.c_long, C.c_ulonglong, C.c_longlong, C.c_double, C.c_void_p]),
+                    "x_stamps": (None, [C.c_void_p])}
+    assert list(sigs) == ["x_name", "x_bytes", "x_copy", "x_draw", "x_stamps"] and all(type(a) is list for _, a in sigs.values())
+    for bad, word in (("int f(short a);", "short a"), ("unsigned f(int a);", "unsigned"), ("int f(size_t n);", "size_t n"),
+                      ("float* f(int a);", "float*"), ("int f(int a); stray text\nint g(int b);", "stray text"), ("int counter;", "counter"),
+                      ("int f(int);", "'int'")):
+        with pytest.raises(ValueError, match=re.escape(word)):
+            parse_header(bad)
+
+
+def test_signatures_carry_the_headers_types():
+    from ldmae_amd import _lib
+    C = ctypes
+    header = open(os.path.join(ROOT, "include", "ldmae_hip.h")).read()
+    assert len(_lib.SIGNATURES) == len(set(re.findall(r"\b(ldmae_[a-z0-9_]+)\s*\(", header)))
+    S = _lib.SIGNATURES
+    assert S["ldmae_last_error"] == (C.c_char_p, []) and S["ldmae_gemm_tn_workspace_bytes"][0] is C.c_long
+    assert S["ldmae_cast"][1][-2] is C.c_long and S["ldmae_cast"][1] == [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+    assert S["ldmae_adamw_ema"][1].count(C.c_double) == 7 and S["ldmae_rademacher_f32"][1].count(C.c_ulonglong) == 2
+    assert S["ldmae_label_embed_fwd"][1][1] is C.c_void_p and S["ldmae_sse_workspace_bytes"] == (C.c_long, [C.c_int, C.c_long])
+    # host arrays are plain pointers too: ctypes arrays and byref() both convert to c_void_p
+    for name in ("ldmae_prof_collect", "ldmae_launch_counts", "ldmae_mx8_launch_counts"):
+        assert S[name][1][0] is C.c_void_p, name
+    assert S["ldmae_rk_stage_f32"][1][3] is C.c_void_p and S["ldmae_sde_combine_f32"][1][4] is C.c_void_p
+    assert C.c_void_p.from_param((C.c_float * 4)()) is not None and C.c_void_p.from_param(C.byref(C.c_double())) is not None
+    assert _lib.DIAG_SIGNATURES == {"ldmae_tune": (C.c_int, [C.c_int, C.c_int]), "ldmae_tune_query": (C.c_int, [C.c_int]),
+                                    "ldmae_debug_nt_stamps": (None, [C.c_void_p])}
