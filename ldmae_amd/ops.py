@@ -718,8 +718,8 @@ def rope(t, cos, sin, transposed=False):
     return out
 
 
-_ATTN_HDS = (16, 32, 64, 72, 128)            # head dims the attention kernels are instantiated for (csrc/attention.hip: ATTN_HD_DISPATCH)
-_ATTN_HDS_F32 = (16, 32, 64, 72, 80, 96, 128)      # ... and the f32 kernels (ATTN_HD_DISPATCH_F32): their backward's LDS tiles end at head_dim 96
+_ATTN_HDS = (16, 32, 64, 72, 128)            # head dims the attention kernels are instantiated for (csrc/attention.hip: attn_hd_dispatch)
+_ATTN_HDS_F32 = (16, 32, 64, 72, 80, 96, 128)      # ... and the f32 kernels (attn_hd_dispatch_f32): their backward's LDS tiles end at head_dim 96
 
 
 def _attn_hds(dtype):

@@ -12,8 +12,8 @@ A seeded table of cases drives the C ABI directly, so each case controls pointer
 The backward is fed o and lse made by the f64 reference (rounded to their storage types), never the forward kernel's output.
 
 Dispatch predicates (csrc/attention.hip), each taken and not taken by some case (test_case_table_covers_every_predicate):
-  attention_fwd_core / attention_bwd_core: dtype (fp16 -> <16, R, true>; bf16 -> ATTN_HD_DISPATCH; f32 -> hd == 16 ? hd16 kernel : ATTN_HD_DISPATCH_F32);
-  RAGGED = N % 64 != 0 (its own instantiation; the backward then runs prefetch depth 0, whole-tile head dim 64 depth 1);
+  attention_fwd_core / attention_bwd_core: dtype (fp16 -> <16, R, true>; bf16 -> attn_hd_dispatch; f32 -> hd == 16 ? hd16 kernel : attn_hd_dispatch_f32);
+  RAGGED = N % 64 != 0 (its own instantiation; the backward then runs prefetch depth 0, whole tiles attn_pf(hd): 1 at head dim 64);
   layouts: head-major (sb, sh, ld) = (H N hd, N hd, hd), packed (N 3 H hd, hd, 3 H hd), mixed (q / k head-major, v packed);
   static shift: SB != NULL && bq <= 50 for every lane of the wave; sb_heads ? (SB[2 bh] > 0 ? sqrt(SB0 SB1) c 1.02 : own norm) : *SB;
   active = q0 < N per wave; xcd_remap: r = grid & 7 (x < r branch) and q = grid >> 3 (0 below 8 workgroups).
