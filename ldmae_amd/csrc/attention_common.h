@@ -218,7 +218,6 @@ template <int PPW, int STAGES> __device__ __forceinline__ void ring_wait(int ahe
 }
 #define EXP2(x) __builtin_amdgcn_exp2f(x)
 constexpr int ATT_STAGES = 3;
-template <int I> struct IC { static constexpr int value = I; };
 // f(IC<0>{}), f(IC<1>{}), ... f(IC<N-1>{}): a loop whose index is a compile-time constant in the body
 template <int N, int I = 0, typename F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) { f(IC<I>{}); static_for<N, I + 1>(f); }

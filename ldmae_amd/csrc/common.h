@@ -202,6 +202,8 @@ void ldmae_prof_end(long idx, hipStream_t st);
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+// an int as a type: f(IC<hd>{}) hands a generic lambda a compile-time constant (the attention and GEMM launch dispatchers)
+template <int I> struct IC { static constexpr int value = I; };
 
 // sigmoid on the fast-math units: v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the 12-instruction IEEE division; every SwiGLU
 // site (fused GEMM epilogues and the standalone kernels) uses this one definition, so fused and unfused paths stay bit-identical.

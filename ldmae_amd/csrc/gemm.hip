@@ -198,13 +198,6 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(const bf16* __rest
   }
 }
 
-#ifdef LDMAE_DIAG
-// launch-gap probes (tools/, diagnostic build): the persistent NT kernel's launch configuration and arguments around an empty body
-__global__ __launch_bounds__(512) void gemm_nt_dummy_kernel(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb, EpiArgs e, int ntiles,
-                                                            int delay, unsigned long long* stamps) {
-  if (M < 0) stamps[0] = (unsigned long long)(size_t)A + (size_t)B + N + K + lda + ldb + ntiles + delay + (size_t)e.C;
-}
-#endif
 // ------------------------------------------------------------------------------------------------
 // f32 NT GEMM: 64x64 tile, 256 threads (2x2 waves, 32x32 per wave), BK = 16, register staged.
 // ------------------------------------------------------------------------------------------------
@@ -712,125 +705,123 @@ extern "C" void ldmae_debug_nt_stamps(void* buf) { g_nt_stamps = buf; }
 #else
 static constexpr void* g_nt_stamps = nullptr;
 #endif
+
+// gemm_nt_persist_kernel: 3-deep ring, the eight epilogue strips behind it, 2 KiB for the per-K-step stamps of the diagnostic TL build
+constexpr int PERS_LDS = 3 * 512 * 64 + 8 * 16 * 68 * 4 + 2048;
+// its epilogues per output type: the SwiGLU pair writes bf16 only (ldmae_gemm_nt refuses it for any other output)
+template <typename OutT, typename F> static bool persist_epi_dispatch(int epi, F&& f) {
+  if constexpr (sizeof(OutT) == 2)
+    return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_BIAS_POS, LDMAE_EPI_BIAS_GELU, LDMAE_EPI_SWIGLU, LDMAE_EPI_SWIGLU_BWD,
+                           LDMAE_EPI_GELU_BWD>(epi, f);
+  else return nt_epi_dispatch_any_out(epi, f);
+}
+
+#ifdef LDMAE_DIAG
+// launch-gap probes (tools/, diagnostic build): the persistent NT kernel's launch configuration and arguments around an empty body
+__global__ __launch_bounds__(512) void gemm_nt_dummy_kernel(const bf16* A, const bf16* B, int M, int N, int K, int lda, int ldb, EpiArgs e, int ntiles,
+                                                            int delay, unsigned long long* stamps) {
+  if (M < 0) stamps[0] = (unsigned long long)(size_t)A + (size_t)B + N + K + lda + ldb + ntiles + delay + (size_t)e.C;
+}
+
+// Every A/B route of the diagnostic build (bf16 operands), tried in this order ahead of the product path; true = it launched (`what` then names
+// the launch for the error text).  A route that refuses the shape or the epilogue falls through to the next.
+template <typename OutT>
+static bool nt_diag_route(int dtype, int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, const NtGrid& g,
+                          hipStream_t st, const char*& what) {
+  if (dtype != LDMAE_BF16) return false;
+  constexpr bool out16 = sizeof(OutT) == 2;
+  // tune key 0: 1 / 2 = the experimental kernels of probe/gemm_w4.hip
+  if (ldmae_tune_get(0) != 0 && (ldmae_tune_get(0) == 1 ? ldmae_launch_nt_w4(epi, out16, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)
+                                                         : ldmae_launch_nt_p8(epi, out16, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st))) {
+    what = "gemm_nt_w4";
+    return true;
+  }
+  // tune key 12 = 1: the fused epilogue's elementwise part runs inside the next tile's main loop (probe/gemm_nt_defer.hip).  Built, bitwise
+  // equal, and 5-9 % SLOWER than the fused epilogues (profiles/r04_defer_ab.txt).
+  if (out16 && g.pers && g.grid != g.ntiles && (epi == LDMAE_EPI_GATE_RES || epi == LDMAE_EPI_SWIGLU) && ldmae_tune_get(12) == 1 &&
+      ldmae_launch_nt_defer(epi, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
+    what = "gemm_nt_defer";
+    return true;
+  }
+  // tune key 15 = 1: whole-line ring DMA (probe/gemm_nt_wl.hip: 128-B LDS rows, pieces of 8 rows x 128 B).  Built, bitwise equal on every
+  // epilogue, 6.5 % SLOWER over the block's eight GEMMs (profiles/r04_wl_ab.txt): the CU's DMA path is limited in BYTES per cycle, not in
+  // line requests.
+  if (ldmae_tune_get(15) == 1 && out16 && M % 8 == 0 && N % 8 == 0 && M >= 8 && N >= 8 && K % 64 == 0 && lda % 64 == 0 && ldb % 64 == 0 &&
+      ((uintptr_t)A & 127) == 0 && ((uintptr_t)B & 127) == 0 && (epi != LDMAE_EPI_SWIGLU || N % 256 == 0) &&
+      ldmae_launch_nt_wl(epi, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
+    what = "gemm_nt_wl";
+    return true;
+  }
+  // The rest are forms of gemm_nt_persist_kernel (keys 14, 7 and 11 also switch the whole-line kernel off: launch_nt).
+  // tune key 14 = 1: 4-deep ring, 128 KiB, strips aliased onto it, the SwiGLU-bwd scratch behind it (160 KiB in all).  Measured neutral
+  // (profiles/r04_ring4_ab.txt: block total 8.158 -> 8.118 ms): the L2 read latency seen by the CU is ~360 cycles (TCP_TCC_READ_REQ_LATENCY /
+  // READ_REQ, profiles/r04_pmc_ta.md), far inside what two stages in flight cover.
+  if (ldmae_tune_get(14) == 1)
+    return persist_epi_dispatch<OutT>(epi, [&](auto E) {
+      constexpr int lds4 = 4 * 512 * 64 + (decltype(E)::value == LDMAE_EPI_SWIGLU_BWD ? 8 * 1024 * 4 : 0);
+      nt_launch(gemm_nt_persist_kernel<4, decltype(E)::value, OutT>, g.grid, 512, lds4, st, A, B, M, N, K, lda, ldb, e, g.ntiles, ldmae_tune_get(5),
+                g_nt_stamps);
+    });
+  // tune key 7 = 1: the per-K-step stamp build (TL) of the bias and SwiGLU epilogues
+  if (ldmae_tune_get(7) == 1) {
+    auto tl = [&](auto E) {
+      nt_launch(gemm_nt_persist_kernel<3, decltype(E)::value, OutT, true>, g.grid, 512, PERS_LDS, st, A, B, M, N, K, lda, ldb, e, g.ntiles,
+                ldmae_tune_get(5) | (ldmae_tune_get(16) << 16), g_nt_stamps);
+    };
+    bool hit;
+    if constexpr (out16) hit = nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_SWIGLU>(epi, tl);
+    else hit = nt_epi_dispatch<LDMAE_EPI_BIAS>(epi, tl);
+    if (hit) return true;
+  }
+  // tune key 11 (launch-gap probes, wrong results by design): 1 = an empty kernel with the same launch configuration, 2 = the real kernel
+  // with ntiles = 0 (every workgroup returns at once)
+  if (ldmae_tune_get(11) == 1) {
+    nt_launch(gemm_nt_dummy_kernel, g.grid, 512, PERS_LDS, st, A, B, M, N, K, lda, ldb, e, g.ntiles, 0, nullptr);
+    return true;
+  }
+  if (ldmae_tune_get(11) == 2)
+    return persist_epi_dispatch<OutT>(epi, [&](auto E) {
+      nt_launch(gemm_nt_persist_kernel<3, decltype(E)::value, OutT>, g.grid, 512, PERS_LDS, st, A, B, M, N, K, lda, ldb, e, 0, 0, nullptr);
+    });
+  return false;
+}
+#endif
+
+// The product dispatch: the whole-line kernel, else the half-line persistent kernel, else (f32 operands) the f32 kernel.
 template <typename OutT>
 static int launch_nt(int dtype, int epi, bool tile_launch, bool half_lines, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e,
                      hipStream_t st) {
   const long pi = (ldmae_prof_is_on() && dtype == LDMAE_BF16) ? ldmae_prof_begin(st, 2.0 * M * N * K) : -1;
-  // per call and per device (a process may drive several GPUs; the query is a cached driver attribute, ~100 ns)
-  int ncu = 0;
-  {
-    int dev = 0, n = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    ncu = n >= 8 ? n / 8 * 8 : 8;
-  }
-  const int ntiles = cdiv(M, 256) * cdiv(N, 256);
+  // (tune key 8 = 2, diagnostic build: one tile per workgroup for every call)
+  const NtGrid g = nt_grid(M, N, tile_launch || ldmae_tune_get(8) == 2);
+  const char* what = "gemm_nt";
 #ifdef LDMAE_DIAG
-  // tune key 11 (launch-gap probes): 1 = an empty kernel with the same launch configuration, 2 = the real kernel with ntiles = 0 (every
-  // workgroup returns at once)
-#define NT_DUMMY_BRANCHES(E)                                                                                                       \
-    else if (ldmae_tune_get(11) == 1) { hipFuncSetAttribute((const void*)gemm_nt_dummy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 2048); hipLaunchKernelGGL(gemm_nt_dummy_kernel, dim3(pgrid), dim3(512), lds + 2048, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, ntiles, 0, (unsigned long long*)nullptr); } \
-    else if (ldmae_tune_get(11) == 2) { PERS_ATTR(3, E, OutT); hipLaunchKernelGGL((gemm_nt_persist_kernel<3, E, OutT>), dim3(pgrid), dim3(512), lds + 2048, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, 0, 0, (unsigned long long*)nullptr); }
+  bool ok = nt_diag_route<OutT>(dtype, epi, A, B, M, N, K, lda, ldb, e, g, st, what);
 #else
-#define NT_DUMMY_BRANCHES(E)
+  bool ok = false;
 #endif
-  // launch mode, a per-call argument (LDMAE_EPI_TILE_LAUNCH or'ed into `epi` by the caller): one 256x256 tile per workgroup instead of
-  // one persistent workgroup per CU -- what a data-parallel caller asks for while RCCL's collective kernels hold some CUs
-  // the persistent mapping gives every XCD a contiguous range of A row-blocks: with fewer than 8 row-blocks (the batched adaLN GEMM: M = batch
-  // = 256, N = depth * 6D) whole XCDs would idle, so such shapes take the tile launch, which deals tiles to all XCDs
-  const bool pers = !tile_launch && ldmae_tune_get(8) != 2 && cdiv(M, 256) >= 8;
-  const int pgrid = (pers && ntiles != ncu) ? ncu : ntiles;
-#ifdef LDMAE_DIAG
-  // tune key 0: 1 / 2 = the experimental kernels of probe/gemm_w4.hip (diagnostic build only)
-  if (dtype == LDMAE_BF16 && ldmae_tune_get(0) != 0 &&
-      (ldmae_tune_get(0) == 1 ? ldmae_launch_nt_w4(epi, sizeof(OutT) == 2, A, B, M, N, K, lda, ldb, e, pgrid, ntiles, st)
-                                : ldmae_launch_nt_p8(epi, sizeof(OutT) == 2, A, B, M, N, K, lda, ldb, e, pgrid, ntiles, st))) {
-    if (pi >= 0) ldmae_prof_end(pi, st);
-    LDMAE_CHECK_LAUNCH("gemm_nt_w4");
-    return LDMAE_OK;
+  if (ok) {
+  } else if (dtype == LDMAE_BF16 && !half_lines && ldmae_tune_get(19) == 0 && ldmae_tune_get(7) == 0 && ldmae_tune_get(11) == 0 &&
+             ldmae_tune_get(14) == 0 && ldmae_launch_nt_lines(epi, sizeof(OutT) == 2, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
+    // bf16, whole-line form (gemm_nt_lines.hip): every shape whose rows start on 128-B lines.  LDMAE_EPI_HALF_LINES and the diagnostic tune
+    // keys 19, 7, 11 and 14 keep the half-line kernel below.
+    ok = true;
+    what = "gemm_nt_lines";
+  } else if (dtype == LDMAE_BF16) {
+    // bf16: the persistent ring kernel (one workgroup per CU).  tune key 5 = start delay of every other workgroup, key 16 = column-group
+    // walk (A/B knobs, 0 in the product build)
+    ok = persist_epi_dispatch<OutT>(epi, [&](auto E) {
+      nt_launch(gemm_nt_persist_kernel<3, decltype(E)::value, OutT>, g.grid, 512, PERS_LDS, st, A, B, M, N, K, lda, ldb, e, g.ntiles,
+                ldmae_tune_get(5) | (ldmae_tune_get(16) << 16), g_nt_stamps);
+    });
+  } else {
+    ok = nt_epi_dispatch_any_out(epi, [&](auto E) {
+      nt_launch(gemm_nt_f32_kernel<decltype(E)::value, OutT>, cdiv(M, F_BM) * cdiv(N, F_BN), 256, 0, st, A, B, M, N, K, lda, ldb, e);
+    });
   }
-#endif
-#ifdef LDMAE_DIAG
-  // tune key 12 = 1 (diagnostic build only): the fused epilogue's elementwise part runs inside the next tile's main loop
-  // (probe/gemm_nt_defer.hip).  Built, bitwise equal, and 5-9 % SLOWER than the fused epilogues (profiles/r04_defer_ab.txt).
-  if (dtype == LDMAE_BF16 && sizeof(OutT) == 2 && pers && pgrid != ntiles && (epi == LDMAE_EPI_GATE_RES || epi == LDMAE_EPI_SWIGLU) &&
-      ldmae_tune_get(12) == 1 && ldmae_launch_nt_defer(epi, A, B, M, N, K, lda, ldb, e, pgrid, ntiles, st)) {
-    if (pi >= 0) ldmae_prof_end(pi, st);
-    LDMAE_CHECK_LAUNCH("gemm_nt_defer");
-    return LDMAE_OK;
-  }
-#endif
-#ifdef LDMAE_DIAG
-  // tune key 15 = 1 (diagnostic build only): whole-line ring DMA (probe/gemm_nt_wl.hip: 128-B LDS rows, pieces of 8 rows x 128 B).  Built,
-  // bitwise equal on every epilogue, 6.5 % SLOWER over the block's eight GEMMs (profiles/r04_wl_ab.txt): the CU's DMA path is limited in
-  // BYTES per cycle, not in line requests.
-  if (ldmae_tune_get(15) == 1 && dtype == LDMAE_BF16 && sizeof(OutT) == 2 && M % 8 == 0 && N % 8 == 0 && M >= 8 && N >= 8 && K % 64 == 0 && lda % 64 == 0 &&
-      ldb % 64 == 0 && ((uintptr_t)A & 127) == 0 && ((uintptr_t)B & 127) == 0 && (epi != LDMAE_EPI_SWIGLU || N % 256 == 0) &&
-      ldmae_launch_nt_wl(epi, A, B, M, N, K, lda, ldb, e, pgrid, ntiles, st)) {
-    if (pi >= 0) ldmae_prof_end(pi, st);
-    LDMAE_CHECK_LAUNCH("gemm_nt_wl");
-    return LDMAE_OK;
-  }
-#endif
-  // bf16, whole-line form (gemm_nt_lines.hip; round 5): every shape whose rows start on 128-B lines.  Diagnostic tune key 19 = 1 keeps the
-  // half-line kernel below for A/B runs.
-  if (dtype == LDMAE_BF16 && !half_lines && ldmae_tune_get(19) == 0 && ldmae_tune_get(7) == 0 && ldmae_tune_get(11) == 0 && ldmae_tune_get(14) == 0 &&
-      ldmae_launch_nt_lines(epi, sizeof(OutT) == 2, A, B, M, N, K, lda, ldb, e, pgrid, ntiles, st)) {
-    if (pi >= 0) ldmae_prof_end(pi, st);
-    LDMAE_CHECK_LAUNCH("gemm_nt_lines");
-    return LDMAE_OK;
-  }
-  // bf16: the persistent ring kernel (one workgroup per CU).  tune key 5 = start delay of every other workgroup (A/B knob),
-  // key 7 = diagnostic per-K-step stamp build.
-#define PERS_ATTR(...) hipFuncSetAttribute((const void*)gemm_nt_persist_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, lds + 2048)
-#define PERS_GO(...)                                                                                                             \
-  hipLaunchKernelGGL((gemm_nt_persist_kernel<__VA_ARGS__>), dim3(pgrid), dim3(512), lds + 2048, st, (const bf16*)A, (const bf16*)B, \
-                     M, N, K, lda, ldb, e, ntiles, ldmae_tune_get(5) | (ldmae_tune_get(16) << 16), (unsigned long long*)g_nt_stamps)
-  // tune key 14 = 1 (diagnostic build only): 4-deep ring, 128 KiB, strips aliased onto it, the SwiGLU-bwd scratch behind it (160 KiB in all).
-  // Measured neutral (profiles/r04_ring4_ab.txt: block total 8.158 -> 8.118 ms): the L2 read latency seen by the CU is ~360 cycles
-  // (TCP_TCC_READ_REQ_LATENCY / READ_REQ, profiles/r04_pmc_ta.md), far inside what two stages in flight cover.
-#ifdef LDMAE_DIAG
-#define PERS_RING4(E)                                                                                                             \
-  if (ldmae_tune_get(14) == 1) {                                                                                                  \
-    constexpr int lds4 = 4 * 512 * 64 + (E == LDMAE_EPI_SWIGLU_BWD ? 8 * 1024 * 4 : 0);                                            \
-    hipFuncSetAttribute((const void*)gemm_nt_persist_kernel<4, E, OutT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4);       \
-    hipLaunchKernelGGL((gemm_nt_persist_kernel<4, E, OutT>), dim3(pgrid), dim3(512), lds4, st, (const bf16*)A, (const bf16*)B,      \
-                       M, N, K, lda, ldb, e, ntiles, ldmae_tune_get(5), (unsigned long long*)g_nt_stamps);                       \
-  } else
-#else
-#define PERS_RING4(E)
-#endif
-#define PERS(E)                                                                                                                  \
-  PERS_RING4(E)                                                                                                                   \
-  {                                                                                                                               \
-    constexpr int lds = 3 * 512 * 64 + 8 * 16 * 68 * 4;                                                                           \
-    /* the LDS opt-in is per device and cheap: set it at every launch (no process-wide "done" flag) */                            \
-    if (E == LDMAE_EPI_BIAS && ldmae_tune_get(7) == 1) { PERS_ATTR(3, LDMAE_EPI_BIAS, OutT, true); PERS_GO(3, LDMAE_EPI_BIAS, OutT, true); }     \
-    else if (E == LDMAE_EPI_SWIGLU && ldmae_tune_get(7) == 1) { PERS_ATTR(3, LDMAE_EPI_SWIGLU, OutT, true); PERS_GO(3, LDMAE_EPI_SWIGLU, OutT, true); } \
-    NT_DUMMY_BRANCHES(E)                                                                                                          \
-    else { PERS_ATTR(3, E, OutT); PERS_GO(3, E, OutT); }                                                                          \
-  }
-#define NT_LAUNCH(E)                                                                                                             \
-  if (dtype == LDMAE_BF16) PERS(E)                                                                                                \
-  else                                                                                                                           \
-    hipLaunchKernelGGL((gemm_nt_f32_kernel<E, OutT>), dim3(cdiv(M, F_BM) * cdiv(N, F_BN)), dim3(256), 0, st, (const float*)A,    \
-                       (const float*)B, M, N, K, lda, ldb, e)
-  switch (epi) {
-    case LDMAE_EPI_BIAS: NT_LAUNCH(LDMAE_EPI_BIAS); break;
-    case LDMAE_EPI_GATE_RES: NT_LAUNCH(LDMAE_EPI_GATE_RES); break;
-    case LDMAE_EPI_BIAS_POS: NT_LAUNCH(LDMAE_EPI_BIAS_POS); break;
-    case LDMAE_EPI_SWIGLU: PERS(LDMAE_EPI_SWIGLU); break;
-    case LDMAE_EPI_SWIGLU_BWD: PERS(LDMAE_EPI_SWIGLU_BWD); break;
-    case LDMAE_EPI_GELU_BWD: NT_LAUNCH(LDMAE_EPI_GELU_BWD); break;
-    default: NT_LAUNCH(LDMAE_EPI_BIAS_GELU); break;
-  }
-#undef NT_LAUNCH
-#undef PERS
-#undef PERS_GO
-#undef PERS_RING4
-#undef PERS_ATTR
+  if (!ok) LDMAE_FAIL(LDMAE_ERR_INVALID, "gemm_nt: unknown epilogue %d", epi);   // (ldmae_gemm_nt has refused it already)
   if (pi >= 0) ldmae_prof_end(pi, st);
-  LDMAE_CHECK_LAUNCH("gemm_nt");
+  LDMAE_CHECK_LAUNCH(what);
   return LDMAE_OK;
 }
 
@@ -885,14 +876,8 @@ extern "C" int ldmae_gemm_nt(int dtype, int out_dtype, int epi, const void* A, i
                   "gemm_nt(fp16): bias, gated residual, pos, gelu, gelu-bwd epilogues (the VMAE blocks), got %d", epi);
     LDMAE_REQUIRE(beta == 0.f, "gemm_nt(fp16): beta must be 0");
     ldmae_count(LDMAE_COUNT_NT_F16);
-    int ncu = 0, dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    ncu = ncu >= 8 ? ncu / 8 * 8 : 8;
-    const int ntiles = cdiv(M, 256) * cdiv(N, 256);
-    const bool pers = !tile_launch && cdiv(M, 256) >= 8;
-    const int pgrid = (pers && ntiles != ncu) ? ncu : ntiles;
-    LDMAE_REQUIRE(ldmae_launch_nt_lines_f16(epi, out_dtype == LDMAE_F16, A, B, M, N, K, lda, ldb, e, pgrid, ntiles, as_stream(stream)),
+    const NtGrid g = nt_grid(M, N, tile_launch);
+    LDMAE_REQUIRE(ldmae_launch_nt_lines_f16(epi, out_dtype == LDMAE_F16, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, as_stream(stream)),
                   "gemm_nt(fp16): shape outside the whole-line kernel (M=%d N=%d multiples of 8, K=%d lda=%d ldb=%d multiples of 64, 128-B aligned operands)",
                   M, N, K, lda, ldb);
     LDMAE_CHECK_LAUNCH("gemm_nt_lines_f16");
@@ -927,22 +912,19 @@ extern "C" int ldmae_gemm_nt_qkv_rope(const void* A, int lda, const void* W, int
   e.q2 = q2; e.k2 = k2; e.wq = wq; e.wk = wk; e.cosT = cos; e.sinT = sin; e.heads = H; e.store_raw_qk = store_raw_qk; e.eps = eps;
   hipStream_t st = as_stream(stream);
   const long pi = ldmae_prof_is_on() ? ldmae_prof_begin(st, 2.0 * M * Nc * K) : -1;
-  int ncu = 0, dev = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  ncu = ncu >= 8 ? ncu / 8 * 8 : 8;
-  const int ntiles = cdiv(M, 256) * cdiv(Nc, 256);
-  const bool pers = !tile_launch && cdiv(M, 256) >= 8;
-  const int pgrid = (pers && ntiles != ncu) ? ncu : ntiles;
+  const NtGrid g = nt_grid(M, Nc, tile_launch != 0);
   ldmae_count(LDMAE_COUNT_NT_BF16);
-  LDMAE_REQUIRE(ldmae_launch_nt_lines(LDMAE_EPI_QKV_ROPE, 1, A, W, M, Nc, K, lda, ldb, e, pgrid, ntiles, st), "gemm_nt_qkv_rope: the whole-line kernel refused the shape");
+  LDMAE_REQUIRE(ldmae_launch_nt_lines(LDMAE_EPI_QKV_ROPE, 1, A, W, M, Nc, K, lda, ldb, e, g.grid, g.ntiles, st), "gemm_nt_qkv_rope: the whole-line kernel refused the shape");
   if (pi >= 0) ldmae_prof_end(pi, st);
   LDMAE_CHECK_LAUNCH("gemm_nt_qkv_rope");
   return LDMAE_OK;
 }
 
+// the 256 x 256 ring kernel takes every 16-bit product whose row count is a multiple of 32 (tune key 1 = 1: the 128 x 128 kernel, A/B)
+static bool tn_ring(int dtype, int M) { return dtype == LDMAE_BF16 && ldmae_tune_get(1) == 0 && M % 32 == 0; }
+
 static int tn_plan(int dtype, int M, int N, int K, int* rows_out) {
-  const bool ring = dtype == LDMAE_BF16 && ldmae_tune_get(1) == 0 && M % 32 == 0;
+  const bool ring = tn_ring(dtype, M);
   const int bn = ring ? 256 : (dtype == LDMAE_BF16 ? TN_BN : FT_BN), bk = ring ? 256 : (dtype == LDMAE_BF16 ? TN_BK : FT_BK);
   const long tiles = (long)cdiv(N, bn) * cdiv(K, bk);
   // ring kernel: ONE round of at most 256 workgroups (one per CU; measured 5-10 % faster than two rounds of 512: no second-round
@@ -957,6 +939,13 @@ static int tn_plan(int dtype, int M, int N, int K, int* rows_out) {
   rows = (rows + 63) / 64 * 64;
   if (rows_out) *rows_out = rows;
   return (M + rows - 1) / rows;
+}
+
+// one launch of the ring kernel: WNn x 4 waves; the ring (4 x 32 KiB) and the 139 KiB epilogue region share 160 KiB of LDS
+template <int WNn, bool STAG, bool F16>
+static void tn_ring_launch(unsigned grid, hipStream_t st, const void* A, const void* B, float* P, float* Pb, int M, int N, int K, int lda, int ldb,
+                           int rows) {
+  nt_launch(gemm_tn_ring_kernel<4, WNn, STAG, F16>, grid, WNn * 4 * 64, 5 * 32768, st, A, B, P, Pb, M, N, K, lda, ldb, rows);
 }
 
 extern "C" int ldmae_gemm_tn_splits(int dtype, int M, int N, int K) { return tn_plan(dtype == LDMAE_F16 ? LDMAE_BF16 : dtype, M, N, K, nullptr); }
@@ -977,7 +966,7 @@ extern "C" int ldmae_gemm_tn(int dtype, const void* A, int lda, const void* B, i
   LDMAE_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && ((uintptr_t)C & 15) == 0, "gemm_tn: pointers must be 16-B aligned");
   int rows = 0;
   const int splits = tn_plan(dtype, M, N, K, &rows);
-  const bool ring = dtype == LDMAE_BF16 && ldmae_tune_get(1) == 0 && M % 32 == 0;
+  const bool ring = tn_ring(dtype, M);
   hipStream_t st = as_stream(stream);
   ldmae_count(half ? LDMAE_COUNT_TN_F16 : (dtype == LDMAE_BF16 ? LDMAE_COUNT_TN_BF16 : LDMAE_COUNT_TN_F32));
   LDMAE_REQUIRE(workspace && workspace_bytes >= (long)splits * ((long)N * K + N) * 4, "gemm_tn: workspace too small (%ld < %ld)",
@@ -987,24 +976,19 @@ extern "C" int ldmae_gemm_tn(int dtype, const void* A, int lda, const void* B, i
   float* P = direct ? C : workspace;
   float* Pb = direct ? dbias : workspace + (size_t)splits * N * K;
   if (ring) {
-    constexpr int lds = 5 * 32768;   // ring (4 x 32 KiB) and the 139 KiB epilogue region share it
-    if (ldmae_tune_get(4) == 3) hipFuncSetAttribute((const void*)gemm_tn_ring_kernel<4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else if (ldmae_tune_get(4) == 4) hipFuncSetAttribute((const void*)gemm_tn_ring_kernel<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    else hipFuncSetAttribute((const void*)gemm_tn_ring_kernel<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     const unsigned grid = cdiv(N, 256) * cdiv(K, 256) * splits;
+    float* pb = dbias ? Pb : nullptr;
     // default: 8 waves (128x64 each), 4-deep ring, the two wave groups half a step apart (1115-1135 TF/s with the fused bias
-    // gradient vs 965-1030 for 16 lock-step waves); tune key 4: 3 = 16 lock-step waves, 4 = 16 staggered waves.
+    // gradient vs 965-1030 for 16 lock-step waves); tune key 4 (diagnostic build): 3 = 16 lock-step waves, 4 = 16 staggered waves.
     // The bias-gradient MFMAs stay on the wk == 0 waves: spreading them over all waves (a wave-uniform switch on wk, or one
     // slot per K-tile workgroup) measured 8-15 % SLOWER -- every wave's MFMA phase is on the staggered loop's critical path.
-    if (ldmae_tune_get(4) == 3)
-      hipLaunchKernelGGL((gemm_tn_ring_kernel<4, 4, false>), dim3(grid), dim3(1024), lds, st, (const bf16*)A, (const bf16*)B, P, dbias ? Pb : nullptr, M, N, K, lda, ldb, rows);
-    else if (ldmae_tune_get(4) == 4)
-      hipLaunchKernelGGL((gemm_tn_ring_kernel<4, 4, true>), dim3(grid), dim3(1024), lds, st, (const bf16*)A, (const bf16*)B, P, dbias ? Pb : nullptr, M, N, K, lda, ldb, rows);
-    else if (half) {
-      hipFuncSetAttribute((const void*)gemm_tn_ring_kernel<4, 2, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipLaunchKernelGGL((gemm_tn_ring_kernel<4, 2, true, true>), dim3(grid), dim3(512), lds, st, (const bf16*)A, (const bf16*)B, P, dbias ? Pb : nullptr, M, N, K, lda, ldb, rows);
-    } else
-      hipLaunchKernelGGL((gemm_tn_ring_kernel<4, 2, true>), dim3(grid), dim3(512), lds, st, (const bf16*)A, (const bf16*)B, P, dbias ? Pb : nullptr, M, N, K, lda, ldb, rows);
+#ifdef LDMAE_DIAG
+    if (ldmae_tune_get(4) == 3) tn_ring_launch<4, false, false>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
+    else if (ldmae_tune_get(4) == 4) tn_ring_launch<4, true, false>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
+    else
+#endif
+    if (half) tn_ring_launch<2, true, true>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
+    else tn_ring_launch<2, true, false>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
   } else if (dtype == LDMAE_BF16) {
     const unsigned grid = cdiv(N, TN_BN) * cdiv(K, TN_BK) * splits;
     if (half) hipLaunchKernelGGL(gemm_tn_bf16_kernel<true>, dim3(grid), dim3(256), 4 * TN_TILE_BYTES, st, (const bf16*)A, (const bf16*)B, P, M, N, K, lda, ldb, rows);

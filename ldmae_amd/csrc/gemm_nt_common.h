@@ -32,6 +32,40 @@ struct EpiArgs {
   float eps;
 };
 
+// ------------------------------------------------------------------------------------------------
+// Host side shared by every NT launcher (gemm.hip, gemm_nt_lines.hip, mx8.hip, probe/gemm_*.hip)
+// ------------------------------------------------------------------------------------------------
+// Grid plan of the 256 x 256-tile kernels: one persistent workgroup per CU (`grid` = the CU count rounded down to whole XCDs), or one tile per
+// workgroup (`grid` = ntiles) -- when the caller asks for it (LDMAE_EPI_TILE_LAUNCH: a data-parallel caller while RCCL's collective kernels
+// hold some CUs), and for fewer than 8 row-blocks: the persistent mapping gives every XCD a contiguous range of A row-blocks, so with fewer
+// (the batched adaLN GEMM: M = batch = 256, N = depth * 6D) whole XCDs would idle, while the tile launch deals tiles to all XCDs.
+// Per call and per device (a process may drive several GPUs; the query is a cached driver attribute, ~100 ns).
+struct NtGrid { int ntiles, grid; bool pers; };
+static inline NtGrid nt_grid(int M, int N, bool tile_launch) {
+  int dev = 0, n = 0;
+  hipGetDevice(&dev);
+  hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+  const int ncu = n >= 8 ? n / 8 * 8 : 8, ntiles = cdiv(M, 256) * cdiv(N, 256);
+  const bool pers = !tile_launch && cdiv(M, 256) >= 8;
+  return {ntiles, (pers && ntiles != ncu) ? ncu : ntiles, pers};
+}
+// One launch: the kernel's dynamic-LDS limit is raised to `lds` on every call (per device and cheap: no process-wide "done" flag), then the
+// launch.  Every argument is converted to the kernel's own parameter type (the C ABI hands over const void*).
+template <typename... P, typename... A>
+static inline void nt_launch(void (*kernel)(P...), unsigned grid, unsigned threads, int lds, hipStream_t st, A... args) {
+  if (lds > 0) hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, st, (P)args...);
+}
+// f(IC<E>{}) for the epilogue of EPIS... that `epi` names; false when it names none of them.  A launcher instantiates its kernel for exactly
+// the epilogues it lists.
+template <int... EPIS, typename F> static inline bool nt_epi_dispatch(int epi, F&& f) {
+  return ((epi == EPIS ? (f(IC<EPIS>{}), true) : false) || ...);
+}
+// the five epilogues that exist for every operand and output type (the SwiGLU pair and the qkv front end write bf16 only)
+template <typename F> static inline bool nt_epi_dispatch_any_out(int epi, F&& f) {
+  return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_BIAS_POS, LDMAE_EPI_BIAS_GELU, LDMAE_EPI_GELU_BWD>(epi, f);
+}
+
 // gemm_nt_lines.hip: the whole-line form of the persistent bf16 NT kernel (128-B LDS rows, seamless ring of five half-block slots).  Returns 0
 // when the shape / alignment is outside what it covers; the caller then launches gemm_nt_persist_kernel.
 int ldmae_launch_nt_lines(int epi, int out_bf16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const struct EpiArgs& e,

@@ -162,30 +162,21 @@ __global__ __launch_bounds__(512) void gemm_nt_lines_kernel(const bf16* __restri
   }
 }
 
-// returns 0 when the shape / arguments are outside what the whole-line kernel covers (the caller then launches gemm_nt_persist_kernel)
-template <typename OutT>
+// returns 0 when the epilogue is outside what the whole-line kernel is instantiated for (the caller then launches gemm_nt_persist_kernel, or
+// refuses fp16 operands).  bf16 operands: every epilogue with bf16 outputs; fp16 operands (InT = f16): the VMAE blocks' five.  f32 outputs:
+// no SwiGLU / qkv epilogue (they write bf16), and no fp16 GELU backward (out_dtype == dtype there).
+template <typename OutT, typename InT>
 static int launch_lines(int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles,
                         hipStream_t st) {
-  constexpr int lds = 5 * 256 * 128;
-#define LINES_GO(E)                                                                                                                    \
-  {                                                                                                                                     \
-    hipFuncSetAttribute((const void*)gemm_nt_lines_kernel<E, OutT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                   \
-    hipLaunchKernelGGL((gemm_nt_lines_kernel<E, OutT>), dim3(grid), dim3(512), lds, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, \
-                       ntiles);                                                                                                        \
-    return 1;                                                                                                                           \
-  }
-  switch (epi) {
-    case LDMAE_EPI_BIAS: LINES_GO(LDMAE_EPI_BIAS);
-    case LDMAE_EPI_GATE_RES: LINES_GO(LDMAE_EPI_GATE_RES);
-    case LDMAE_EPI_BIAS_POS: LINES_GO(LDMAE_EPI_BIAS_POS);
-    case LDMAE_EPI_BIAS_GELU: LINES_GO(LDMAE_EPI_BIAS_GELU);
-    case LDMAE_EPI_GELU_BWD: LINES_GO(LDMAE_EPI_GELU_BWD);
-    case LDMAE_EPI_SWIGLU: if constexpr (sizeof(OutT) == 2) LINES_GO(LDMAE_EPI_SWIGLU) else return 0;
-    case LDMAE_EPI_SWIGLU_BWD: if constexpr (sizeof(OutT) == 2) LINES_GO(LDMAE_EPI_SWIGLU_BWD) else return 0;
-    case LDMAE_EPI_QKV_ROPE: if constexpr (sizeof(OutT) == 2) LINES_GO(LDMAE_EPI_QKV_ROPE) else return 0;
-    default: return 0;
-  }
-#undef LINES_GO
+  auto go = [&](auto E) {
+    nt_launch(gemm_nt_lines_kernel<decltype(E)::value, OutT, InT>, grid, 512, 5 * 256 * 128, st, A, B, M, N, K, lda, ldb, e, ntiles);
+  };
+  constexpr bool half_in = __is_same(InT, f16), out16 = sizeof(OutT) == 2;
+  if constexpr (!half_in && out16)
+    return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_BIAS_POS, LDMAE_EPI_BIAS_GELU, LDMAE_EPI_GELU_BWD, LDMAE_EPI_SWIGLU,
+                           LDMAE_EPI_SWIGLU_BWD, LDMAE_EPI_QKV_ROPE>(epi, go);
+  else if constexpr (half_in && !out16) return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_BIAS_POS, LDMAE_EPI_BIAS_GELU>(epi, go);
+  else return nt_epi_dispatch_any_out(epi, go);
 }
 
 static bool lines_shape_ok(int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb) {
@@ -194,39 +185,17 @@ static bool lines_shape_ok(int epi, const void* A, const void* B, int M, int N, 
   return !(epi == LDMAE_EPI_SWIGLU && N % 256 != 0);
 }
 
-template <typename OutT>
-static int launch_lines_f16(int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles,
-                            hipStream_t st) {
-  constexpr int lds = 5 * 256 * 128;
-#define LINES_GO(E)                                                                                                                    \
-  {                                                                                                                                     \
-    hipFuncSetAttribute((const void*)gemm_nt_lines_kernel<E, OutT, f16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);              \
-    hipLaunchKernelGGL((gemm_nt_lines_kernel<E, OutT, f16>), dim3(grid), dim3(512), lds, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, \
-                       e, ntiles);                                                                                                     \
-    return 1;                                                                                                                           \
-  }
-  switch (epi) {
-    case LDMAE_EPI_BIAS: LINES_GO(LDMAE_EPI_BIAS);
-    case LDMAE_EPI_GATE_RES: LINES_GO(LDMAE_EPI_GATE_RES);
-    case LDMAE_EPI_BIAS_POS: LINES_GO(LDMAE_EPI_BIAS_POS);
-    case LDMAE_EPI_BIAS_GELU: LINES_GO(LDMAE_EPI_BIAS_GELU);
-    case LDMAE_EPI_GELU_BWD: if constexpr (sizeof(OutT) == 2) LINES_GO(LDMAE_EPI_GELU_BWD) else return 0;
-    default: return 0;
-  }
-#undef LINES_GO
-}
-
 int ldmae_launch_nt_lines_f16(int epi, int out_f16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid,
                               int ntiles, hipStream_t st) {
   if (!lines_shape_ok(epi, A, B, M, N, K, lda, ldb)) return 0;
-  return out_f16 ? launch_lines_f16<f16>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st)
-                 : launch_lines_f16<float>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st);
+  return out_f16 ? launch_lines<f16, f16>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st)
+                 : launch_lines<float, f16>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st);
 }
 
 int ldmae_launch_nt_lines(int epi, int out_bf16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid,
                           int ntiles, hipStream_t st) {
   if (!lines_shape_ok(epi, A, B, M, N, K, lda, ldb)) return 0;
   // the lane offsets are 32-bit: 8 rows of the operand must stay below 4 GiB (they do by many orders of magnitude)
-  return out_bf16 ? launch_lines<bf16>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st)
-                  : launch_lines<float>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st);
+  return out_bf16 ? launch_lines<bf16, bf16>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st)
+                  : launch_lines<float, bf16>(epi, A, B, M, N, K, lda, ldb, e, grid, ntiles, st);
 }

@@ -426,29 +426,12 @@ static bool mx8_shape_ok(int epi, long M, int N, int K, int lda, int ldb) {
 template <typename OutT>
 static int launch_mx8(int epi, const void* A, const void* As, const void* B, const void* Bs, int M, int N, int K, int lda, int ldb, const EpiArgs& e,
                       int tile_launch, hipStream_t st) {
-  constexpr int lds = 5 * 256 * 128;
-  int ncu = 0, dev = 0;
-  hipGetDevice(&dev);
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  ncu = ncu >= 8 ? ncu / 8 * 8 : 8;
-  const int ntiles = cdiv(M, 256) * cdiv(N, 256);
-  const bool pers = !tile_launch && cdiv(M, 256) >= 8;
-  const int grid = (pers && ntiles != ncu) ? ncu : ntiles;
-#define MX8_GO(E)                                                                                                                            \
-  {                                                                                                                                           \
-    hipFuncSetAttribute((const void*)gemm_nt_mx8_kernel<E, OutT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                           \
-    hipLaunchKernelGGL((gemm_nt_mx8_kernel<E, OutT>), dim3(grid), dim3(512), lds, st, (const uint8_t*)A, (const uint8_t*)As, (const uint8_t*)B, \
-                       (const uint8_t*)Bs, M, N, K, lda, ldb, e, ntiles);                                                                          \
-    return 1;                                                                                                                                 \
-  }
-  switch (epi) {
-    case LDMAE_EPI_BIAS: MX8_GO(LDMAE_EPI_BIAS);
-    case LDMAE_EPI_GATE_RES: MX8_GO(LDMAE_EPI_GATE_RES);
-    case LDMAE_EPI_SWIGLU: if constexpr (sizeof(OutT) == 2) MX8_GO(LDMAE_EPI_SWIGLU) else return 0;
-    case LDMAE_EPI_QKV_ROPE: if constexpr (sizeof(OutT) == 2) MX8_GO(LDMAE_EPI_QKV_ROPE) else return 0;
-    default: return 0;
-  }
-#undef MX8_GO
+  const NtGrid g = nt_grid(M, N, tile_launch != 0);
+  auto go = [&](auto E) {
+    nt_launch(gemm_nt_mx8_kernel<decltype(E)::value, OutT>, g.grid, 512, 5 * 256 * 128, st, A, As, B, Bs, M, N, K, lda, ldb, e, g.ntiles);
+  };
+  if constexpr (sizeof(OutT) == 2) return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_SWIGLU, LDMAE_EPI_QKV_ROPE>(epi, go);
+  else return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES>(epi, go);
 }
 
 extern "C" int ldmae_gemm_nt_mx8_ok(int M, int N, int K, int lda, int ldb) { return mx8_shape_ok(LDMAE_EPI_BIAS, M, N, K, lda, ldb) ? 1 : 0; }

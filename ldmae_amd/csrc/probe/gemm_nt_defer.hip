@@ -417,29 +417,18 @@ int ldmae_launch_nt_defer(int epi, const void* A, const void* B, int M, int N, i
   if (epi == LDMAE_EPI_GATE_RES) {
     if (!e.C || e.ldc % 8 || nk < 24) return 0;
     if (e.gate && (e.rows_per_batch % 256 || ((uintptr_t)e.gate & 15) || e.gate_ld % 4)) return 0;
-#define DEFER_GO(E, D)                                                                                                          \
-  {                                                                                                                            \
-    hipFuncSetAttribute((const void*)gemm_nt_defer_kernel<E, D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);              \
-    hipLaunchKernelGGL((gemm_nt_defer_kernel<E, D>), dim3(grid), dim3(512), lds, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, ntiles); \
-  }
-#ifdef LDMAE_DIAG
-#define DEFER_LAUNCH(E)                                                                     \
-  switch (ldmae_tune_get(13)) {                                                             \
-    case 1: DEFER_GO(E, 1); break;                                                          \
-    case 2: DEFER_GO(E, 2); break;                                                          \
-    case 3: DEFER_GO(E, 3); break;                                                          \
-    default: DEFER_GO(E, 0); break;                                                         \
-  }
-#else
-#define DEFER_LAUNCH(E) DEFER_GO(E, 0)
-#endif
-    DEFER_LAUNCH(LDMAE_EPI_GATE_RES);
-    return 1;
-  }
-  if (epi == LDMAE_EPI_SWIGLU) {
+  } else if (epi == LDMAE_EPI_SWIGLU) {
     if (!e.C || e.ldc != N || nk < 16) return 0;
-    DEFER_LAUNCH(LDMAE_EPI_SWIGLU);
-    return 1;
   }
-  return 0;
+  return nt_epi_dispatch<LDMAE_EPI_GATE_RES, LDMAE_EPI_SWIGLU>(epi, [&](auto E) {
+    auto go = [&](auto D) {
+      nt_launch(gemm_nt_defer_kernel<decltype(E)::value, decltype(D)::value>, grid, 512, lds, st, A, B, M, N, K, lda, ldb, e, ntiles);
+    };
+    switch (ldmae_tune_get(13)) {   // tune key 13 = 1..3: the kernel's DBG ablations (timing only)
+      case 1: go(IC<1>{}); break;
+      case 2: go(IC<2>{}); break;
+      case 3: go(IC<3>{}); break;
+      default: go(IC<0>{}); break;
+    }
+  });
 }

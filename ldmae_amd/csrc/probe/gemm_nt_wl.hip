@@ -131,19 +131,8 @@ __global__ __launch_bounds__(512) void gemm_nt_wl_kernel(const bf16* __restrict_
 
 int ldmae_launch_nt_wl(int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles,
                        hipStream_t st) {
-#define WL_GO(E)                                                                                                                        \
-  {                                                                                                                                      \
-    constexpr int ldsw = 4 * 256 * 128 + (E == LDMAE_EPI_SWIGLU_BWD ? 8 * 1024 * 4 : 0);                                                  \
-    hipFuncSetAttribute((const void*)gemm_nt_wl_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, ldsw);                             \
-    hipLaunchKernelGGL((gemm_nt_wl_kernel<E>), dim3(grid), dim3(512), ldsw, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, ntiles); \
-    return 1;                                                                                                                            \
-  }
-  switch (epi) {
-    case LDMAE_EPI_BIAS: WL_GO(LDMAE_EPI_BIAS);
-    case LDMAE_EPI_GATE_RES: WL_GO(LDMAE_EPI_GATE_RES);
-    case LDMAE_EPI_SWIGLU: WL_GO(LDMAE_EPI_SWIGLU);
-    case LDMAE_EPI_SWIGLU_BWD: WL_GO(LDMAE_EPI_SWIGLU_BWD);
-    default: return 0;
-  }
-#undef WL_GO
+  return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_SWIGLU, LDMAE_EPI_SWIGLU_BWD>(epi, [&](auto E) {
+    constexpr int ldsw = 4 * 256 * 128 + (decltype(E)::value == LDMAE_EPI_SWIGLU_BWD ? 8 * 1024 * 4 : 0);
+    nt_launch(gemm_nt_wl_kernel<decltype(E)::value>, grid, 512, ldsw, st, A, B, M, N, K, lda, ldb, e, ntiles);
+  });
 }

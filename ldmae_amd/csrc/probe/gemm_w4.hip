@@ -299,49 +299,25 @@ __global__ __launch_bounds__(512) void gemm_nt_p8_kernel(const bf16* __restrict_
   }
 }
 
-// host side: called from gemm.hip's launch_nt when tune key 0 selects this kernel
-template <int EPI, typename OutT>
-static void go_w4(const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles, hipStream_t st) {
-  constexpr int ST = 4;
-  constexpr int lds = ST * 512 * 64 + 4 * 16 * 68 * 4 + 4 * 2048;
-  hipFuncSetAttribute((const void*)gemm_nt_w4_kernel<ST, EPI, OutT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((gemm_nt_w4_kernel<ST, EPI, OutT>), dim3(grid), dim3(256), lds, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, ntiles);
-}
-
-template <int EPI, typename OutT>
-static void go_p8(const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles, hipStream_t st) {
-  constexpr int lds = 3 * 512 * 64 + 8 * 16 * 68 * 4 + 8 * 2048;
-  hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<EPI, OutT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL((gemm_nt_p8_kernel<EPI, OutT>), dim3(grid), dim3(512), lds, st, (const bf16*)A, (const bf16*)B, M, N, K, lda, ldb, e, ntiles);
+// host side: called from gemm.hip's nt_diag_route when tune key 0 selects one of these kernels; 0 = no instantiation for `epi`.
+// (SwiGLU-bwd: the shared epilogue needs 1024 floats of per-wave scratch, which these experimental kernels do not reserve: shipped kernel)
+template <typename F> static int w4_epi_dispatch(int epi, int out_bf16, F&& f) {
+  if (out_bf16) return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES, LDMAE_EPI_SWIGLU>(epi, [&](auto E) { f(E, bf16{}); });
+  return nt_epi_dispatch<LDMAE_EPI_BIAS, LDMAE_EPI_GATE_RES>(epi, [&](auto E) { f(E, float{}); });
 }
 
 int ldmae_launch_nt_p8(int epi, int out_bf16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid,
                        int ntiles, hipStream_t st) {
-#define P8(E)                                                                                        \
-  if (out_bf16) go_p8<E, bf16>(A, B, M, N, K, lda, ldb, e, grid, ntiles, st);                        \
-  else go_p8<E, float>(A, B, M, N, K, lda, ldb, e, grid, ntiles, st)
-  switch (epi) {
-    case LDMAE_EPI_BIAS: P8(LDMAE_EPI_BIAS); break;
-    case LDMAE_EPI_GATE_RES: P8(LDMAE_EPI_GATE_RES); break;
-    case LDMAE_EPI_SWIGLU: go_p8<LDMAE_EPI_SWIGLU, bf16>(A, B, M, N, K, lda, ldb, e, grid, ntiles, st); break;
-    // (SwiGLU-bwd: the shared epilogue now needs 1024 floats of per-wave scratch, which these experimental kernels do not reserve: shipped kernel)
-    default: return 0;
-  }
-#undef P8
-  return 1;
+  constexpr int lds = 3 * 512 * 64 + 8 * 16 * 68 * 4 + 8 * 2048;
+  return w4_epi_dispatch(epi, out_bf16, [&](auto E, auto out) {
+    nt_launch(gemm_nt_p8_kernel<decltype(E)::value, decltype(out)>, grid, 512, lds, st, A, B, M, N, K, lda, ldb, e, ntiles);
+  });
 }
 
 int ldmae_launch_nt_w4(int epi, int out_bf16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid,
                        int ntiles, hipStream_t st) {
-#define W4(E)                                                                                        \
-  if (out_bf16) go_w4<E, bf16>(A, B, M, N, K, lda, ldb, e, grid, ntiles, st);                        \
-  else go_w4<E, float>(A, B, M, N, K, lda, ldb, e, grid, ntiles, st)
-  switch (epi) {
-    case LDMAE_EPI_BIAS: W4(LDMAE_EPI_BIAS); break;
-    case LDMAE_EPI_GATE_RES: W4(LDMAE_EPI_GATE_RES); break;
-    case LDMAE_EPI_SWIGLU: go_w4<LDMAE_EPI_SWIGLU, bf16>(A, B, M, N, K, lda, ldb, e, grid, ntiles, st); break;
-    default: return 0;
-  }
-#undef W4
-  return 1;
+  constexpr int ST = 4, lds = ST * 512 * 64 + 4 * 16 * 68 * 4 + 4 * 2048;
+  return w4_epi_dispatch(epi, out_bf16, [&](auto E, auto out) {
+    nt_launch(gemm_nt_w4_kernel<ST, decltype(E)::value, decltype(out)>, grid, 256, lds, st, A, B, M, N, K, lda, ldb, e, ntiles);
+  });
 }

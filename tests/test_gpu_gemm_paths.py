@@ -210,7 +210,8 @@ def _nt_path(c, a, b):
     return "nt_bf16_lines" if ok else "nt_bf16_ring"
 
 
-def run_nt(lib, c):
+def run_nt(lib, c, keep=None):
+    """keep: a dict that receives the outputs of the first run (tests/test_gpu_gemm_diag.py compares them across tune keys)"""
     dtype, out_dt, M, N, K, epi = c["dtype"], c["out"], c["M"], c["N"], c["K"], c["epi"]
     lda, ldb = c.get("lda", K), c.get("ldb", K)
     ldc = c.get("ldc", N)
@@ -320,11 +321,14 @@ def run_nt(lib, c):
         ref, S = gc.colsum_ref(first["dh12"])
         # per-128-row partials of dh12 AS STORED, summed here in f64 (the wrapper sums them with colsum)
         _record(key + ":dbias", gc.check_sum(c["name"] + " dbias", first["part"].double().sum(0), ref, S, M, F32))
+    if keep is not None:
+        keep.update(first)
     return path
 
 
 # ----------------------------------------------------------------------------- TN, colsum, thin
-def run_tn(lib, c):
+def run_tn(lib, c, keep=None):
+    """keep: as in run_nt"""
     dtype, M, N, K = c["dtype"], c["M"], c["N"], c["K"]
     lda, ldb, beta, with_bias = c.get("lda", N), c.get("ldb", K), c.get("beta", 0.0), c.get("bias", False)
     s = 2000 + sum(map(ord, c["name"]))
@@ -365,6 +369,8 @@ def run_tn(lib, c):
     if with_bias:
         ref, S = gc.colsum_ref(a, olds["dbias"][0] if beta else None)
         _record(path + ":dbias", gc.check_sum(c["name"] + " dbias", first["dbias"][0], ref, S, M, F32))
+    if keep is not None:
+        keep.update(first)
     return path, splits
 
 
@@ -484,6 +490,22 @@ def test_f16_refused_shape_names_the_kernel(lib):
     with pytest.raises(RuntimeError, match=r"gemm_nt\(fp16\): shape outside the whole-line kernel \(M=203 N=64"):
         lib.call("ldmae_gemm_nt", 2, 2, EPI_BIAS, A.data_ptr(), 64, B.data_ptr(), 64, C.data_ptr(), 64, 203, 64, 64, None, 0.0, None, None,
                  None, 0, 0, _stream())
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("epi", [EPI_SWIGLU, EPI_SWIGLU_BWD], ids=["swiglu", "swiglu_bwd"])
+def test_swiglu_with_f32_output_is_refused(lib, dtype, epi):
+    """The SwiGLU epilogues write bf16 only: the library returns LDMAE_ERR_INVALID (-1) before any launch, whatever the operand type."""
+    M, N, K = 256, 256, 64
+    A, B = operand(M, K, dtype, K, 1).t, operand(N, K, dtype, K, 2).t
+    C, x = Canvas(M, 2 * N, 2 * N, F32), Canvas(M, 2 * N, 2 * N, F32)
+    lib.launch_counts(reset=True)
+    rc = lib.load().ldmae_gemm_nt(_dt(dtype), _dt(F32), epi, A.data_ptr(), K, B.data_ptr(), K, C.t.data_ptr(), 2 * N if epi == EPI_SWIGLU_BWD else N,
+                                  M, N, K, None, 0.0, x.t.data_ptr(), x.t.data_ptr(), None, 0, 0, _stream())
+    assert rc == -1 and "epilogue is bf16 only" in lib.last_error()
+    torch.cuda.synchronize()
+    assert not any(lib.launch_counts().values()) and C.intact() and x.intact()
+    assert bool((C.t.view(torch.int32) == _BITS[F32][1]).all()), "a refused call wrote its output"
 
 
 # ----------------------------------------------------------------------------- wrapper layout rules (ldmae_amd.ops)
