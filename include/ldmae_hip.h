@@ -43,6 +43,9 @@ extern "C" {
  * under fp16 autocast (engine_pretrain.py:51-57) also the backward: ldmae_gemm_nt(EPI_BIAS / EPI_GELU_BWD | LDMAE_EPI_F16_INF), ldmae_gemm_tn,
  * ldmae_attention_bwd_qkv (head_dim 16), ldmae_layernorm_bwd, ldmae_colsum, ldmae_gelu_fwd/bwd. */
 #define LDMAE_F16 2
+/* An entry point accepts exactly the dtype codes it has kernels for (stated with each prototype; f32 and bf16 where nothing is said).  Any
+ * other code -- another of the three, or no code at all -- is refused with LDMAE_ERR_INVALID before anything is launched: no entry falls
+ * back to the f32 kernel, which would run past the end of 16-bit buffers. */
 
 /* GEMM epilogues */
 #define LDMAE_EPI_BIAS 0       /* C = acc + bias (+ beta*C)                                   */

@@ -1153,7 +1153,7 @@ extern "C" int ldmae_attention_fwd_pv_bounded(int dtype, const void* q, const vo
   const QkvLayout hm = layout_hm(H, N, hd), pk = layout_pk(H, N, hd);
   return attention_fwd_core(dtype, q, k, (const bf16*)qkv + 2 * hw, o, lse, B, H, N, hd, scale, hm, pk, as_stream(stream), score_bound);
 }
-// The bound for heads that went through QK-RMSNorm + RoPE (lightningdit.py:66-80; elementwise.hip: q = x * rsqrt(mean(x^2) + eps) * w, then a
+// The bound for heads that went through QK-RMSNorm + RoPE (lightningdit.py:66-80; qk_rope.hip: q = x * rsqrt(mean(x^2) + eps) * w, then a
 // rotation): |q|^2 = sum w_i^2 xhat_i^2 <= max|w|^2 * hd, the same for k, RoPE preserves norms, so
 // |q . k| * scale * log2(e) <= hd * max|wq| * max|wk| * scale * log2(e); 2 % on top for the bf16 roundings of q, k and of the scaled q.
 __global__ void qk_score_bound_kernel(const float* __restrict__ wq, const float* __restrict__ wk, int hd, float c, float* __restrict__ out) {

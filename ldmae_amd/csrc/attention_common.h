@@ -256,7 +256,7 @@ __device__ __forceinline__ void store_rows_t(const f32x16 (&acc)[hd_pad(HD) / 32
 }
 
 // ---- QK-RMSNorm + RoPE backward folded into the dQ / dK epilogues (LightningDiT block, head dims with 8 or 16 chunks per row).
-// The unfused chain wrote dq / dk head-major, then elementwise.hip's qknorm_rope_bwd read them back with the pre-norm q / k to produce
+// The unfused chain wrote dq / dk head-major, then qk_rope.hip's qknorm_rope_bwd read them back with the pre-norm q / k to produce
 // the packed dqkv (1.6 GB per layer at bs 256).  Here the dq (dk) tile goes through the same bf16 row image as store_rows_t and every
 // (row, 16-B chunk) lane finishes the job: rope^T, RMSNorm backward against the pre-norm row it loads from the packed qkv, the result
 // stored into the q (k) slot of dqkv as a whole 128-B line per row.  Same per-element formulas as qknorm_rope_bwd_kernel.
@@ -340,7 +340,7 @@ __device__ __forceinline__ void qknorm_rows_math(GRAD&& grad, int lane, const Qk
     const float rs = norm ? rsqrtf(row_sum<CPR>(ss) / (float)HD + a.eps) : 1.f;
     float nq[8], dn[8], dot = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; j += 2) {              // rope^T on the pair (j, j+1): elementwise.hip rope_apply_bwd
+    for (int j = 0; j < 8; j += 2) {              // rope^T on the pair (j, j+1): qk_rope.hip rope_apply_bwd
       const float t0 = g[j] * c8[j] + g[j + 1] * s8[j + 1], t1 = g[j + 1] * c8[j + 1] - g[j] * s8[j];
       nq[j] = x[j] * rs; nq[j + 1] = x[j + 1] * rs;
       aw[j] += t0 * nq[j]; aw[j + 1] += t1 * nq[j + 1];

@@ -168,7 +168,7 @@ template <int W> __device__ __forceinline__ float group_sum(float v) {
 }
 
 // RoPE on two interleaved pairs (VisionRotaryEmbeddingFast.forward, pos_embed.py:135: t * cos + rotate_half(t) * sin, rotate_half: (x0, x1) -> (-x1, x0)).
-// One definition for the QK-norm / RoPE kernels of elementwise.hip and the fused qkv epilogue of gemm_nt_common.h: they agree bit for bit.
+// One definition for the QK-norm / RoPE kernels of qk_rope.hip and the fused qkv epilogue of gemm_nt_common.h: they agree bit for bit.
 __device__ __forceinline__ float4 rope_apply(float4 t, float4 c, float4 s) {
   return make_float4(t.x * c.x - t.y * s.x, t.y * c.y + t.x * s.y, t.z * c.z - t.w * s.z, t.w * c.w + t.z * s.w);
 }
@@ -204,6 +204,28 @@ static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 // an int as a type: f(IC<hd>{}) hands a generic lambda a compile-time constant (the attention and GEMM launch dispatchers)
 template <int I> struct IC { static constexpr int value = I; };
+// a type as a value, and the LDMAE_* code of an element type
+template <typename T> struct TypeTag { using type = T; };
+template <typename Tag> using tag_t = typename Tag::type;
+template <typename T> struct DtypeCode;
+template <> struct DtypeCode<float> : IC<LDMAE_F32> {};
+template <> struct DtypeCode<bf16> : IC<LDMAE_BF16> {};
+template <> struct DtypeCode<f16> : IC<LDMAE_F16> {};
+// f(TypeTag<T>{}) for the one T of Ts... whose code is `code`; false, and f not called, when `code` names none of them.  Every entry point
+// that takes a dtype code chooses its kernel through this, over exactly the types it is instantiated for, and refuses the rest
+// (LDMAE_ERR_INVALID before any HIP call): a kernel of another element size than the caller's buffers would run past their end.
+template <typename... Ts, typename F> static inline bool dtype_dispatch(int code, F&& f) {
+  return ((code == DtypeCode<Ts>::value ? (f(TypeTag<Ts>{}), true) : false) || ...);
+}
+// f(IC<NCH>{}) for the row kernels that keep a row in NCH = ceil(D / 256) float4 chunks per lane (one wave per row), NCH in 1 .. 8
+template <typename F> static inline int row_nch_dispatch(int D, F&& f) {
+  switch ((D / 4 + 63) / 64) {
+    case 1: f(IC<1>{}); break; case 2: f(IC<2>{}); break; case 3: f(IC<3>{}); break; case 4: f(IC<4>{}); break;
+    case 5: f(IC<5>{}); break; case 6: f(IC<6>{}); break; case 7: f(IC<7>{}); break; case 8: f(IC<8>{}); break;
+    default: LDMAE_FAIL(LDMAE_ERR_INVALID, "row width D=%d > 2048 unsupported", D);
+  }
+  return LDMAE_OK;
+}
 
 // sigmoid on the fast-math units: v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the 12-instruction IEEE division; every SwiGLU
 // site (fused GEMM epilogues and the standalone kernels) uses this one definition, so fused and unfused paths stay bit-identical.

@@ -1003,7 +1003,7 @@ extern "C" int ldmae_gemm_tn(int dtype, const void* A, int lda, const void* B, i
     else splitk_reduce(P, C, (long)N * K, splits, beta, st);
     LDMAE_CHECK_LAUNCH("splitk_reduce");
   }
-  if (dbias && !ring) {   // non-ring paths: separate column-sum pass (elementwise.hip), re-using the workspace
+  if (dbias && !ring) {   // non-ring paths: separate column-sum pass (pointwise.hip), re-using the workspace
     LDMAE_REQUIRE(workspace_bytes >= ldmae_colsum_workspace_bytes(M, N), "gemm_tn: workspace too small for the bias-gradient pass");
     return ldmae_colsum(half ? LDMAE_F16 : dtype, A, lda, M, N, dbias, beta, workspace, stream);
   }

@@ -235,7 +235,7 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[MI][NI], float* ew, flo
   };
   if constexpr (EPI == LDMAE_EPI_QKV_ROPE) {
     // The qkv Linear of the DiT block with q_norm / k_norm / RoPE in the epilogue.  TNn == 64: a wave's column slice is ONE head of q, k or v, and the
-    // strip lane map (8 lanes x 8 columns per row) is the lane group of qknorm_rope_fwd8_kernel (elementwise.hip) -- the same arithmetic in the same
+    // strip lane map (8 lanes x 8 columns per row) is the lane group of qknorm_rope_fwd8_kernel (qk_rope.hip) -- the same arithmetic in the same
     // order on the same bf16-rounded values, so q2 / k2 are bitwise what GEMM + that kernel produce, without its 806-MB re-read at bs 256.
     // Host contract (ldmae_gemm_nt_qkv_rope_ok): M % 256 == 0, rows_per_batch % 128 == 0 (a wave's 128 rows lie in one sample), N == 3 * heads * 64.
     static_assert(TNn == 64 && sizeof(OutT) == 2, "EPI_QKV_ROPE: 64-column wave slices, bf16 outputs");

@@ -15,7 +15,7 @@
 // (tests/mx8_check.py bounds it).
 // The scale bytes are not staged: every lane reads the scale byte of its row and 32-block straight from global memory, half a K-step ahead
 // (12 byte loads per lane and K-step; the compiler counts their waits, the ring DMA is invisible to it and can only be over-waited).
-#include "common.h"
+#include "rowwise_common.h"
 
 #include "gemm_nt_common.h"
 
@@ -89,10 +89,10 @@ extern "C" int ldmae_mx8_quantize(int src_dtype, const void* src, int ld, void* 
   LDMAE_REQUIRE(((uintptr_t)src & 15) == 0 && ((uintptr_t)q & 7) == 0, "mx8_quantize: source must be 16-B aligned, q 8-B aligned");
   const long n8 = (long)M * K / 8;
   hipStream_t st = as_stream(stream);
-  if (src_dtype == LDMAE_F32)
-    hipLaunchKernelGGL(mx8_quantize_kernel<float>, dim3(cdiv(n8, 256)), dim3(256), 0, st, (const float*)src, ld, (uint8_t*)q, (uint8_t*)scales, n8, K);
-  else
-    hipLaunchKernelGGL(mx8_quantize_kernel<bf16>, dim3(cdiv(n8, 256)), dim3(256), 0, st, (const bf16*)src, ld, (uint8_t*)q, (uint8_t*)scales, n8, K);
+  dtype_dispatch<float, bf16>(src_dtype, [&](auto t) {        // (codes outside the two were refused above)
+    using T = tag_t<decltype(t)>;
+    hipLaunchKernelGGL(mx8_quantize_kernel<T>, dim3(cdiv(n8, 256)), dim3(256), 0, st, (const T*)src, ld, (uint8_t*)q, (uint8_t*)scales, n8, K);
+  });
   mx8_count(0);
   LDMAE_CHECK_LAUNCH("mx8_quantize");
   return LDMAE_OK;
@@ -101,12 +101,6 @@ extern "C" int ldmae_mx8_quantize(int src_dtype, const void* src, int ld, void* 
 // ---------------------------------------------------------------- RMSNorm + modulate + quantise
 // The arithmetic of rmsnorm_mod_fwd_kernel<NCH, bf16> (elementwise.hip) up to and including its bf16 rounding, then the quantiser on the
 // rounded values while they are in registers.  A lane holds 4 consecutive columns per 256-column chunk, so a 32-block is 8 lanes.
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-__device__ __forceinline__ float4 operator+(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 operator-(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 operator*(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 operator*(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float hsum(float4 a) { return (a.x + a.y) + (a.z + a.w); }
 
 // quantise one 256-column chunk of a row from the modulated values: bf16 rounding, 8-lane amax, e4m3 bytes and the scale byte
 __device__ __forceinline__ void mx8_norm_emit(float4 y, bool inr, int lane, uint8_t* __restrict__ qrow, uint8_t* __restrict__ srow, int c) {
@@ -214,14 +208,10 @@ extern "C" int ldmae_rmsnorm_modulate_fwd_mx8(const float* x, const float* w, co
   const unsigned grid = cdiv(M, 16);
   // the same choice of form as ldmae_rmsnorm_modulate_fwd makes for a bf16 output
   const bool full = D % 256 == 0 && M % 16 == 0 && rows_per_batch % 16 == 0;
-#define MX8_NORM(N_) case N_: \
-    if (full) hipLaunchKernelGGL((rmsnorm_mod_fwd_mx8_kernel<N_, true>), dim3(grid), dim3(256), 0, st, x, w, shift, scale, mod_ld, (uint8_t*)q, (uint8_t*)scales, rstd, M, D, rows_per_batch, eps, 0); \
-    else hipLaunchKernelGGL((rmsnorm_mod_fwd_mx8_kernel<N_, false>), dim3(grid), dim3(256), 0, st, x, w, shift, scale, mod_ld, (uint8_t*)q, (uint8_t*)scales, rstd, M, D, rows_per_batch, eps, 0); \
-    break
-  switch ((D / 4 + 63) / 64) {
-    MX8_NORM(1); MX8_NORM(2); MX8_NORM(3); MX8_NORM(4); MX8_NORM(5); MX8_NORM(6); MX8_NORM(7); MX8_NORM(8);
-  }
-#undef MX8_NORM
+  if (int e = row_nch_dispatch(D, [&](auto nch) {
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, x, w, shift, scale, mod_ld, (uint8_t*)q, (uint8_t*)scales, rstd, M, D, rows_per_batch, eps, 0); };
+        if (full) launch(rmsnorm_mod_fwd_mx8_kernel<decltype(nch)::value, true>); else launch(rmsnorm_mod_fwd_mx8_kernel<decltype(nch)::value, false>);
+      })) return e;
   mx8_count(1);
   LDMAE_CHECK_LAUNCH("rmsnorm_modulate_fwd_mx8");
   return LDMAE_OK;

@@ -12,6 +12,13 @@ __device__ __forceinline__ unsigned f32_ordered(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// f(IC<NV>{}) for the smallest NV of NVS... (ascending) that holds the ceil(D / 64) 16-B chunks a lane owns in a row; the last one takes
+// whatever is left (its entry point bounds D).  The row kernels below are instantiated for a few chunk counts only.
+template <int... NVS, typename F> static inline void nv_dispatch(int D, F&& f) {
+  constexpr int last = (NVS, ...);
+  (void)((((D + 63) / 64 <= NVS || NVS == last) ? (f(IC<NVS>{}), true) : false) || ...);
+}
+
 // One workgroup per sample.  Sorts 64-bit keys (ordered(noise) << 32 | index) ascending: equal noise
 // values are ordered by index == a stable argsort (models_mae.py:484).  L padded to a power of two LP.
 __global__ __launch_bounds__(256) void random_masking_kernel(const float* __restrict__ noise, long long* __restrict__ ids_restore,
@@ -88,8 +95,8 @@ extern "C" int ldmae_patch_gather(int tok_dtype, const float* img, const long lo
                                   int C, int S, int p, int D, void* stream) {
   LDMAE_REQUIRE(img && ids && pos && tok && posg && N > 0 && keep > 0, "patch_gather: null pointer or empty input");
   LDMAE_REQUIRE(p > 0 && S % p == 0 && D % 4 == 0, "patch_gather: image size %d must be a multiple of the patch size %d, D=%d of 4", S, p, D);
-  if (tok_dtype == LDMAE_BF16) hipLaunchKernelGGL(patch_gather_kernel<bf16>, dim3(keep, N), dim3(64), 0, as_stream(stream), img, ids, pos, (bf16*)tok, posg, keep, C, S, p, D);
-  else hipLaunchKernelGGL(patch_gather_kernel<float>, dim3(keep, N), dim3(64), 0, as_stream(stream), img, ids, pos, (float*)tok, posg, keep, C, S, p, D);
+  auto go = [&](auto t) { using T = tag_t<decltype(t)>; hipLaunchKernelGGL(patch_gather_kernel<T>, dim3(keep, N), dim3(64), 0, as_stream(stream), img, ids, pos, (T*)tok, posg, keep, C, S, p, D); };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16>(tok_dtype, go)), "patch_gather: dtype %d (f32 or bf16)", tok_dtype);
   LDMAE_CHECK_LAUNCH("patch_gather");
   return LDMAE_OK;
 }
@@ -220,10 +227,7 @@ extern "C" int ldmae_restore_tokens_bwd(const float* dout, const long long* ids_
   const long rows = (long)B * L;
   const unsigned grid = restore_grid(rows);
   float* P = dmask_token ? workspace : nullptr;
-#define RT(NV) hipLaunchKernelGGL(restore_tokens_bwd_kernel<NV>, dim3(grid), dim3(256), 0, as_stream(stream), dout, ids_restore, dx, P, rows, L, keep, D)
-  const int nv = (D + 63) / 64;
-  if (nv <= 3) RT(3); else if (nv <= 6) RT(6); else RT(8);
-#undef RT
+  nv_dispatch<3, 6, 8>(D, [&](auto nv) { hipLaunchKernelGGL(restore_tokens_bwd_kernel<decltype(nv)::value>, dim3(grid), dim3(256), 0, as_stream(stream), dout, ids_restore, dx, P, rows, L, keep, D); });
   LDMAE_CHECK_LAUNCH("restore_tokens_bwd");
   if (dmask_token) return ldmae_colsum(LDMAE_F32, P, D, (int)grid, D, dmask_token, 0.f, P + (size_t)grid * D, stream);
   return LDMAE_OK;
@@ -371,19 +375,16 @@ __global__ __launch_bounds__(256) void ln_reduce_kernel(const float* __restrict_
   }
 }
 
-constexpr int LN_ROWS = 128;
-#define LN_NV_DISPATCH(D, MACRO) \
-  { const int nv_ = (D + 63) / 64; \
-    if (nv_ <= 3) MACRO(3) else if (nv_ <= 6) MACRO(6) else if (nv_ <= 12) MACRO(12) else if (nv_ <= 16) MACRO(16) else MACRO(20) }      /* 20: D = 1280, mae_vit_huge_patch14 */
+constexpr int LN_ROWS = 128;      // (the NV classes of the two kernels: 3, 6, 12, 16, 20 -- 20: D = 1280, mae_vit_huge_patch14)
 extern "C" int ldmae_layernorm_fwd(int out_dtype, const float* x, const float* w, const float* b, void* out, float* mean, float* rstd,
                                    int M, int D, float eps, void* stream) {
   LDMAE_REQUIRE(x && w && b && out && M > 0 && D > 0 && D % 4 == 0 && D <= 1280, "layernorm_fwd: bad arguments (D=%d: multiple of 4, <= 1280)", D);
   const unsigned grid = cdiv(M, 16) < 4096 ? cdiv(M, 16) : 4096;
-#define LN_F(NV) { if (out_dtype == LDMAE_F16) hipLaunchKernelGGL((layernorm_fwd_kernel<f16, NV>), dim3(grid), dim3(256), 0, as_stream(stream), x, w, b, (f16*)out, mean, rstd, M, D, eps); \
-                   else if (out_dtype == LDMAE_BF16) hipLaunchKernelGGL((layernorm_fwd_kernel<bf16, NV>), dim3(grid), dim3(256), 0, as_stream(stream), x, w, b, (bf16*)out, mean, rstd, M, D, eps); \
-                   else hipLaunchKernelGGL((layernorm_fwd_kernel<float, NV>), dim3(grid), dim3(256), 0, as_stream(stream), x, w, b, (float*)out, mean, rstd, M, D, eps); }
-  LN_NV_DISPATCH(D, LN_F);
-#undef LN_F
+  auto go = [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    nv_dispatch<3, 6, 12, 16, 20>(D, [&](auto nv) { hipLaunchKernelGGL((layernorm_fwd_kernel<T, decltype(nv)::value>), dim3(grid), dim3(256), 0, as_stream(stream), x, w, b, (T*)out, mean, rstd, M, D, eps); });
+  };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16, f16>(out_dtype, go)), "layernorm_fwd: dtype %d (f32, bf16 or f16)", out_dtype);
   LDMAE_CHECK_LAUNCH("layernorm_fwd");
   return LDMAE_OK;
 }
@@ -396,14 +397,15 @@ extern "C" int ldmae_layernorm_bwd_cast(int dtype, const void* dout, const float
   hipStream_t st = as_stream(stream);
   const int G = cdiv(M, LN_ROWS);
   const size_t lds = (size_t)32 * D * 4;
-#define LN_B(NV) { if (dtype == LDMAE_F16) { hipFuncSetAttribute((const void*)layernorm_bwd_kernel<f16, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                     hipLaunchKernelGGL((layernorm_bwd_kernel<f16, NV>), dim3(G), dim3(256), lds, st, (const f16*)dout, x, w, mean, rstd, dx_accum, (f16*)dx_cast, workspace, M, D, LN_ROWS); } \
-                   else if (dtype == LDMAE_BF16) { hipFuncSetAttribute((const void*)layernorm_bwd_kernel<bf16, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                     hipLaunchKernelGGL((layernorm_bwd_kernel<bf16, NV>), dim3(G), dim3(256), lds, st, (const bf16*)dout, x, w, mean, rstd, dx_accum, (bf16*)dx_cast, workspace, M, D, LN_ROWS); } \
-                   else { hipFuncSetAttribute((const void*)layernorm_bwd_kernel<float, NV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                     hipLaunchKernelGGL((layernorm_bwd_kernel<float, NV>), dim3(G), dim3(256), lds, st, (const float*)dout, x, w, mean, rstd, dx_accum, (float*)nullptr, workspace, M, D, LN_ROWS); } }
-  LN_NV_DISPATCH(D, LN_B);
-#undef LN_B
+  auto go = [&](auto t) {
+    using T = tag_t<decltype(t)>;
+    nv_dispatch<3, 6, 12, 16, 20>(D, [&](auto nv) {
+      const auto kernel = layernorm_bwd_kernel<T, decltype(nv)::value>;
+      hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kernel, dim3(G), dim3(256), lds, st, (const T*)dout, x, w, mean, rstd, dx_accum, (T*)dx_cast, workspace, M, D, LN_ROWS);      // (f32: dx_cast is NULL, above)
+    });
+  };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16, f16>(dtype, go)), "layernorm_bwd: dtype %d (f32, bf16 or f16)", dtype);
   hipLaunchKernelGGL(ln_reduce_kernel, dim3(cdiv(2 * D / 4, 4)), dim3(256), 0, st, workspace, G, D, dw, db, beta_w);
   LDMAE_CHECK_LAUNCH("layernorm_bwd");
   return LDMAE_OK;
@@ -432,17 +434,15 @@ __global__ void gelu_bwd_kernel(const T* __restrict__ dout, const T* __restrict_
 static unsigned gelu_grid(long n) { long g = (n + 255) / 256; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
 extern "C" int ldmae_gelu_fwd(int dtype, const void* x, void* out, long n, void* stream) {
   LDMAE_REQUIRE(x && out && n > 0, "gelu_fwd: bad arguments");
-  if (dtype == LDMAE_F16) hipLaunchKernelGGL(gelu_fwd_kernel<f16>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const f16*)x, (f16*)out, n);
-  else if (dtype == LDMAE_BF16) hipLaunchKernelGGL(gelu_fwd_kernel<bf16>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const bf16*)x, (bf16*)out, n);
-  else hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const float*)x, (float*)out, n);
+  auto go = [&](auto t) { using T = tag_t<decltype(t)>; hipLaunchKernelGGL(gelu_fwd_kernel<T>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const T*)x, (T*)out, n); };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16, f16>(dtype, go)), "gelu_fwd: dtype %d (f32, bf16 or f16)", dtype);
   LDMAE_CHECK_LAUNCH("gelu_fwd");
   return LDMAE_OK;
 }
 extern "C" int ldmae_gelu_bwd(int dtype, const void* dout, const void* x, void* dx, long n, void* stream) {
   LDMAE_REQUIRE(dout && x && dx && n > 0, "gelu_bwd: bad arguments");
-  if (dtype == LDMAE_F16) hipLaunchKernelGGL(gelu_bwd_kernel<f16>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const f16*)dout, (const f16*)x, (f16*)dx, n);
-  else if (dtype == LDMAE_BF16) hipLaunchKernelGGL(gelu_bwd_kernel<bf16>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const bf16*)dout, (const bf16*)x, (bf16*)dx, n);
-  else hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const float*)dout, (const float*)x, (float*)dx, n);
+  auto go = [&](auto t) { using T = tag_t<decltype(t)>; hipLaunchKernelGGL(gelu_bwd_kernel<T>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const T*)dout, (const T*)x, (T*)dx, n); };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16, f16>(dtype, go)), "gelu_bwd: dtype %d (f32, bf16 or f16)", dtype);
   LDMAE_CHECK_LAUNCH("gelu_bwd");
   return LDMAE_OK;
 }
@@ -469,17 +469,15 @@ __global__ void gelu_tanh_bwd_kernel(const T* __restrict__ dout, const T* __rest
 }
 extern "C" int ldmae_gelu_tanh_fwd(int dtype, const void* x, void* out, long n, void* stream) {
   LDMAE_REQUIRE(x && out && n > 0, "gelu_tanh_fwd: bad arguments");
-  LDMAE_REQUIRE(dtype == LDMAE_F32 || dtype == LDMAE_BF16, "gelu_tanh_fwd: f32 or bf16");
-  if (dtype == LDMAE_BF16) hipLaunchKernelGGL(gelu_tanh_fwd_kernel<bf16>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const bf16*)x, (bf16*)out, n);
-  else hipLaunchKernelGGL(gelu_tanh_fwd_kernel<float>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const float*)x, (float*)out, n);
+  auto go = [&](auto t) { using T = tag_t<decltype(t)>; hipLaunchKernelGGL(gelu_tanh_fwd_kernel<T>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const T*)x, (T*)out, n); };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16>(dtype, go)), "gelu_tanh_fwd: dtype %d (f32 or bf16)", dtype);
   LDMAE_CHECK_LAUNCH("gelu_tanh_fwd");
   return LDMAE_OK;
 }
 extern "C" int ldmae_gelu_tanh_bwd(int dtype, const void* dout, const void* x, void* dx, long n, void* stream) {
   LDMAE_REQUIRE(dout && x && dx && n > 0, "gelu_tanh_bwd: bad arguments");
-  LDMAE_REQUIRE(dtype == LDMAE_F32 || dtype == LDMAE_BF16, "gelu_tanh_bwd: f32 or bf16");
-  if (dtype == LDMAE_BF16) hipLaunchKernelGGL(gelu_tanh_bwd_kernel<bf16>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const bf16*)dout, (const bf16*)x, (bf16*)dx, n);
-  else hipLaunchKernelGGL(gelu_tanh_bwd_kernel<float>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const float*)dout, (const float*)x, (float*)dx, n);
+  auto go = [&](auto t) { using T = tag_t<decltype(t)>; hipLaunchKernelGGL(gelu_tanh_bwd_kernel<T>, dim3(gelu_grid(n)), dim3(256), 0, as_stream(stream), (const T*)dout, (const T*)x, (T*)dx, n); };
+  LDMAE_REQUIRE((dtype_dispatch<float, bf16>(dtype, go)), "gelu_tanh_bwd: dtype %d (f32 or bf16)", dtype);
   LDMAE_CHECK_LAUNCH("gelu_tanh_bwd");
   return LDMAE_OK;
 }

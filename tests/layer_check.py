@@ -1,4 +1,4 @@
-"""Per-element references and error bounds for csrc/vmae.hip and the second half of csrc/elementwise.hip (colsum, casts, thin GEMMs,
+"""Per-element references and error bounds for csrc/vmae.hip and csrc/pointwise.hip (colsum, casts, thin GEMMs,
 multi_add, embedders, AdamW / EMA), in the manner of row_check.py.
 
 Every check is |got - ref| <= bound for EVERY element (gemm_check.check).  `ref` is f64, computed from the operands AS STORED (16-bit inputs
@@ -198,7 +198,7 @@ def ln_bwd_ref(dout, x, w, mean, rstd, dx_old, dw_old, db_old, beta_w, d_row=Non
 
 # ----------------------------------------------------------------------------- column sums
 def colsum_rows(M: int, N: int) -> int:
-    """colsum_rows of csrc/elementwise.hip: rows summed by one workgroup."""
+    """colsum_rows of csrc/pointwise.hip: rows summed by one workgroup."""
     groups = max(512 // ((N + 1023) // 1024), 1)
     rows, r = (M + groups - 1) // groups, 8
     while r < rows and r < 256:

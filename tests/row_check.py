@@ -1,4 +1,4 @@
-"""Per-element references and error bounds for the row kernels of csrc/elementwise.hip, in the manner of gemm_check.py / attn_check.py.
+"""Per-element references and error bounds for the row kernels of csrc/elementwise.hip and csrc/qk_rope.hip, in the manner of gemm_check.py / attn_check.py.
 
 Every check is |got - ref| <= bound for EVERY element (gemm_check.check).  `ref` is f64, computed from the operands AS STORED (bf16 widened
 exactly) and from the mathematical definition of the operation (oracle/dit.py: rmsnorm, modulate, apply_rope; LayerNorm without affine

@@ -1,4 +1,4 @@
-"""Every dispatch path of the VMAE layer kernels (csrc/vmae.hip) and of the second half of csrc/elementwise.hip (colsum, casts, thin GEMMs,
+"""Every dispatch path of the VMAE layer kernels (csrc/vmae.hip) and of csrc/pointwise.hip (colsum, casts, thin GEMMs,
 activations, multi_add, embedders, AdamW / EMA), element by element, with the bounds of tests/layer_check.py.
 
 Seeded case tables drive the C ABI directly, so each case controls pointers, leading dimensions, NULLs, alignment and workspace sizes.  Each case
@@ -34,6 +34,8 @@ test_case_table_covers_every_predicate, computed from the tables alone):
     with 0, +-0, +-1e-30 and |x| up to 12 (GELU) or 90 (SwiGLU, SiLU), where the exponentials overflow and the formulas must return the limit.
   timestep_embedding: dim 2, 3, 256, 257; t in {0, 0.25, 1, 1000}; two values of max_period; B * half not a multiple of 256.
   latent_prologue with sample = 1: logvar below -30, above 20 and at both clamp points.
+  refused arguments: besides the shape / alignment / workspace refusals, one dtype code per dtype-taking entry point that it has no kernel
+    for (dtype_dispatch, csrc/common.h), on buffers of the f32 size: refused with -1, nothing launched, nothing written.
 The error constants of the device math functions are measured with csrc/probe/intrinsic_probe and listed in layer_check.py.
 
 Fixed with this suite: random_masking_kernel ordered -0.0 before +0.0 where the stable argsort it restates treats them as equal (found by
@@ -1168,6 +1170,34 @@ def _refusals(L):
     for nm, p in (("p % 4", 6), ("p not dividing H", 8)):
         add(f"mae_loss_fwd {nm}", lambda p=p: L.ldmae_mae_loss_fwd(lp.ptr(), li.ptr(), lmk.ptr(), lP.ptr(), 1, 1, 12, 12, p, st), lP)
         add(f"mae_loss_bwd {nm}", lambda p=p: L.ldmae_mae_loss_bwd(lp.ptr(), li.ptr(), lmk.ptr(), lc_.ptr(), ldx.ptr(), 1, 1, 12, 12, p, st), ldx)
+    # A dtype code the entry point has no kernel for: 2 (f16) where only f32 / bf16 exist, 7 where all three do.  Every buffer has the f32
+    # size whatever the code claims, so a fall-through to the float kernel would stay in bounds and show up below as a write.
+    h12, hid, dh12, dhid = f(16, 256), o(16, 128), o(16, 256), f(16, 128)
+    add("swiglu_fwd dtype 2", lambda: L.ldmae_swiglu_fwd(2, h12.ptr(), hid.ptr(), 16, 128, st), hid)
+    add("swiglu_bwd dtype 2", lambda: L.ldmae_swiglu_bwd(2, dhid.ptr(), h12.ptr(), dh12.ptr(), 16, 128, st), dh12)
+    ex, eg, ey = f(64), f(64), o(64)
+    add("silu_fwd dtype 2", lambda: L.ldmae_silu_fwd(2, ex.ptr(), ey.ptr(), 64, st), ey)
+    add("gelu_tanh_fwd dtype 2", lambda: L.ldmae_gelu_tanh_fwd(2, ex.ptr(), ey.ptr(), 64, st), ey)
+    add("gelu_tanh_bwd dtype 2", lambda: L.ldmae_gelu_tanh_bwd(2, eg.ptr(), ex.ptr(), ey.ptr(), 64, st), ey)
+    add("gelu_fwd dtype 7", lambda: L.ldmae_gelu_fwd(7, ex.ptr(), ey.ptr(), 64, st), ey)
+    add("gelu_bwd dtype 7", lambda: L.ldmae_gelu_bwd(7, eg.ptr(), ex.ptr(), ey.ptr(), 64, st), ey)
+    nT, nW, nb, nout = f(16, 16), f(256, 16), f(256), o(16, 256)
+    add("thin_nt dtype 2", lambda: L.ldmae_thin_nt(2, nT.ptr(), nW.ptr(), nb.ptr(), None, nout.ptr(), 16, 256, 16, 16, st), nout)
+    img, ppos, ptok, pposg = f(1, 3, 16, 16), f(16, 256), o(4, 48), o(4, 256)
+    add("patch_gather dtype 2", lambda: L.ldmae_patch_gather(2, img.ptr(), ids.data_ptr(), ppos.ptr(), ptok.ptr(), pposg.ptr(), 1, 4, 3, 16, 4, 256, st), ptok, pposg)
+    sX, sout, sws = f(16, 256), o(256), o(4096)
+    add("colsum dtype 7", lambda: L.ldmae_colsum(7, sX.ptr(), 256, 16, 256, sout.ptr(), 0.0, sws.ptr(), st), sout, sws)
+    wd, wdT = o(16, 256), o(256, 16)
+    add("cast_weight dtype 7", lambda: L.ldmae_cast_weight(7, sX.ptr(), wd.ptr(), wdT.ptr(), 16, 256, st), wd, wdT)
+    srcs = (ctypes.c_void_p * 1)(cs.ptr())
+    add("cast_stack dtype 2", lambda: L.ldmae_cast_stack(2, srcs, 1, 8, ey.ptr(), st), ey)
+    add("layernorm_fwd dtype 7", lambda: L.ldmae_layernorm_fwd(7, x.ptr(), w.ptr(), b.ptr(), y.ptr(), mu.ptr(), rs.ptr(), 4, 64, EPS, st), y, mu, rs)
+    add("layernorm_bwd dtype 7", lambda: L.ldmae_layernorm_bwd(7, x.ptr(), x.ptr(), w.ptr(), m_.ptr(), r_.ptr(), dx.ptr(), dw.ptr(), db.ptr(), 0.0, 4, 64,
+                                                              ws.ptr(), st), dx, dw, db, ws)
+    add("layernorm_bwd_cast dtype 7", lambda: L.ldmae_layernorm_bwd_cast(7, x.ptr(), x.ptr(), w.ptr(), m_.ptr(), r_.ptr(), dx.ptr(), dxc.ptr(), dw.ptr(),
+                                                                        db.ptr(), 0.0, 4, 64, ws.ptr(), st), dx, dxc, dw, db, ws)
+    mq, msc = o(16, 64), o(32)
+    add("mx8_quantize dtype 2", lambda: L.ldmae_mx8_quantize(2, sX.ptr(), 256, mq.ptr(), msc.ptr(), 16, 256, st), mq, msc)
     return R
 
 
@@ -1175,7 +1205,10 @@ REFUSED = ["layernorm_fwd D % 4", "layernorm_fwd D > 1280", "layernorm_bwd D % 4
            "restore_tokens_bwd D > 512", "restore_tokens_bwd dmask without workspace", "latent_prologue mean only", "latent_prologue std only",
            "latent_prologue sample without noise", "thin_tn beta 0.5", "thin_tn short workspace", "cast misaligned src", "cast misaligned dst",
            "cast bf16 -> f16", "cast bf16 -> bf16", "adamw_ema n % 4", "adamw_ema step 0", "conv3x3_bwd C = 4", "conv3x3_bwd C = 1",
-           "mae_loss_fwd p % 4", "mae_loss_bwd p % 4", "mae_loss_fwd p not dividing H", "mae_loss_bwd p not dividing H"]
+           "mae_loss_fwd p % 4", "mae_loss_bwd p % 4", "mae_loss_fwd p not dividing H", "mae_loss_bwd p not dividing H",
+           "swiglu_fwd dtype 2", "swiglu_bwd dtype 2", "silu_fwd dtype 2", "gelu_tanh_fwd dtype 2", "gelu_tanh_bwd dtype 2", "gelu_fwd dtype 7",
+           "gelu_bwd dtype 7", "thin_nt dtype 2", "patch_gather dtype 2", "colsum dtype 7", "cast_weight dtype 7", "cast_stack dtype 2",
+           "layernorm_fwd dtype 7", "layernorm_bwd dtype 7", "layernorm_bwd_cast dtype 7", "mx8_quantize dtype 2"]
 
 
 def test_refused_arguments(lib):

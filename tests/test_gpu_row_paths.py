@@ -1,4 +1,5 @@
-"""Every dispatch path of the row kernels (csrc/elementwise.hip), element by element, with the bounds of tests/row_check.py.
+"""Every dispatch path of the row kernels (csrc/elementwise.hip: norm + modulate, gate_bwd; csrc/qk_rope.hip: QK-norm / RoPE), element by
+element, with the bounds of tests/row_check.py.
 
 Seeded case tables drive the C ABI directly, so each case controls pointers, leading dimensions and NULLs.  Each case
   - places every input in a NaN-padded buffer and every output (rstd, dx with beta_x = 0, dy, the unused column blocks of a [B, 6 D]
@@ -11,7 +12,7 @@ Seeded case tables drive the C ABI directly, so each case controls pointers, lea
   - records the worst err / bound per path and output (printed at module teardown).
 The norm backward is fed rstd made by the f64 reference (rounded to f32), never the forward kernel's output.
 
-Dispatch predicates (host code of csrc/elementwise.hip), each taken and not taken by some case
+Dispatch predicates (host code of csrc/elementwise.hip and csrc/qk_rope.hip), each taken and not taken by some case
 (tests/test_row_check_cpu.py::test_case_table_covers_every_predicate, computed from the tables alone):
   norm forward: FULL = bf16 && D % 256 == 0 && M % 16 == 0 && rows_per_batch % 16 == 0 && !center; NCH = ceil(D / 256) in 1 .. 8; a partly
     filled last chunk; shift / scale / rstd NULL; center.
@@ -25,6 +26,8 @@ Dispatch predicates (host code of csrc/elementwise.hip), each taken and not take
   qknorm_rope_bwd: lanes per item; qk_bwd_grid: m = H / gcd(H, groups per workgroup) = 1, m > 1 with g >= m, g < m; the capped grid and
     its second pass; group_reduce<32> iff grid >= 256; dbias; dv NULL; beta_w; the three modes.
   rope: dtype, transposed, the 8192-workgroup cap.
+  every entry point: one dtype code it has no kernel for (dtype_dispatch, csrc/common.h) is refused with -1 and writes nothing
+    (test_refused_dtype_codes; buffers of the f32 size, so a fall-through to the float kernel would show as a write, not as a fault).
 
 First device run (MI355X): all 231 cases inside their bounds with zero excluded elements, every rerun bitwise equal, no canary touched; the
 module takes about 3 s.  The backward launches with more than 64 KiB of dynamic LDS (D = 1536, 1792, 2048: 72, 84, 96 KiB) were accepted
@@ -627,6 +630,55 @@ def test_rope(lib, c):
     ref, fn = rc.rope_ref(Gt.t.double().view(rows // N, N, hd), Gc.t, Gs.t, bool(c["transposed"]))
     path = f"rope[{_tn(T)},{hd},{'adjoint' if c['transposed'] else 'forward'}{',two-pass' if rope_passes(c) > 1 else ''}]"
     _chk(path, c["name"], "out", got["out"].view(rows // N, N, hd), ref, rc.stored(ref, fn, T))
+
+
+# ----------------------------------------------------------------------------- refused dtype codes
+def test_refused_dtype_codes(lib):
+    """One dtype code per entry point that it has no kernel for -- 2 (f16), or 0 (f32) for the residual + norm pass, which takes the 16-bit
+    types only: the call returns -1 with a message that names the entry, launches nothing and leaves every output with its NaN payload.
+    Every buffer has the f32 size whatever the code claims, so a fall-through to the float kernel would stay in bounds and show up as a
+    write, never as a fault."""
+    L, st = lib.load(), _stream()
+    M, D, rpb, B, N, H, hd = 16, 256, 16, 1, 8, 1, 64
+    f = lambda *s: Guard(s, F32, torch.zeros(s).cuda())        # noqa: E731  finite input
+    o = lambda *s: Guard(s, F32)                               # noqa: E731  NaN-filled output
+    x, w, mod, g, rstd, y, gate = f(M, D), f(D), f(1, D), f(M, D), f(M), f(M, D), f(1, D)
+    out, rs, xout, dx, dsh, dsc, dw, dy, dgate, dbias = o(M, D), o(M), o(M, D), o(M, D), o(1, D), o(1, D), o(D), o(M, D), o(1, D), o(D)
+    need = max(L.ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes(M, D, rpb), L.ldmae_gate_bwd_workspace_bytes(M, D, rpb),
+               L.ldmae_qknorm_rope_bwd_workspace_bytes(B, N, H, hd))
+    ws = o(need // 4)
+    bwd = (g.ptr(), x.ptr(), w.ptr(), mod.ptr(), D, rstd.ptr(), dx.ptr(), 0.0, dsh.ptr(), dsc.ptr(), D, dw.ptr(), 0.0)
+    lbwd = (g.ptr(), x.ptr(), mod.ptr(), D, rstd.ptr(), dx.ptr(), 0.0, dsh.ptr(), dsc.ptr(), D)
+    gt = (y.ptr(), gate.ptr(), D, dy.ptr(), dgate.ptr(), D, dbias.ptr())
+    tail = (M, D, rpb, ws.ptr(), st)
+    qkv, wq, cs, gq = f(B, N, 3 * H * hd), f(hd), f(N, hd), f(B, H, N, hd)
+    q, k, v, dqkv, dwq, dwk, dbq = o(B, H, N, hd), o(B, H, N, hd), o(B, H, N, hd), o(B, N, 3 * H * hd), o(hd), o(hd), o(3 * H * hd)
+    R = {
+        "rmsnorm_modulate_fwd": (lambda: L.ldmae_rmsnorm_modulate_fwd(2, x.ptr(), w.ptr(), mod.ptr(), mod.ptr(), D, out.ptr(), rs.ptr(), M, D, rpb, EPS, st), 2),
+        "layernorm_modulate_fwd": (lambda: L.ldmae_layernorm_modulate_fwd(2, x.ptr(), mod.ptr(), mod.ptr(), D, out.ptr(), rs.ptr(), M, D, rpb, EPS, st), 2),
+        "res_rmsnorm_modulate_fwd": (lambda: L.ldmae_res_rmsnorm_modulate_fwd(0, x.ptr(), y.ptr(), gate.ptr(), D, None, None, 0, xout.ptr(), w.ptr(), mod.ptr(),
+                                                                             mod.ptr(), D, out.ptr(), rs.ptr(), M, D, rpb, EPS, st), 0),
+        "rmsnorm_modulate_bwd": (lambda: L.ldmae_rmsnorm_modulate_bwd(2, *bwd, *tail), 2),
+        "rmsnorm_modulate_bwd_gate": (lambda: L.ldmae_rmsnorm_modulate_bwd_gate(2, *bwd, *gt, *tail), 2),
+        "rmsnorm_modulate_bwd_gate_recompute": (lambda: L.ldmae_rmsnorm_modulate_bwd_gate_recompute(2, *bwd, *gt, *tail), None),     # its message has no code
+        "layernorm_modulate_bwd": (lambda: L.ldmae_layernorm_modulate_bwd(2, *lbwd, *tail), 2),
+        "layernorm_modulate_bwd_gate": (lambda: L.ldmae_layernorm_modulate_bwd_gate(2, *lbwd, *gt, *tail), 2),
+        "gate_bwd": (lambda: L.ldmae_gate_bwd(2, g.ptr(), *gt, *tail), 2),
+        "qknorm_rope_fwd": (lambda: L.ldmae_qknorm_rope_fwd(2, qkv.ptr(), wq.ptr(), wq.ptr(), cs.ptr(), cs.ptr(), q.ptr(), k.ptr(), v.ptr(), B, N, H, hd, EPS, st), 2),
+        "qknorm_rope_bwd": (lambda: L.ldmae_qknorm_rope_bwd(2, gq.ptr(), gq.ptr(), gq.ptr(), qkv.ptr(), wq.ptr(), wq.ptr(), cs.ptr(), cs.ptr(), dqkv.ptr(), dwq.ptr(),
+                                                           dwk.ptr(), 0.0, dbq.ptr(), B, N, H, hd, EPS, ws.ptr(), st), 2),
+        "rope": (lambda: L.ldmae_rope(2, gq.ptr(), cs.ptr(), cs.ptr(), q.ptr(), B * H * N, N, hd, 0, st), 2),
+    }
+    for name, (fn, code) in R.items():
+        status = fn()
+        msg = lib.last_error()
+        assert status == -1 and msg.startswith(name + ":"), f"{name}: not refused as an invalid argument (status {status}: {msg!r})"
+        assert code is None or f"dtype {code}" in msg, msg
+    torch.cuda.synchronize()
+    for q_ in (out, rs, xout, dx, dsh, dsc, dw, dy, dgate, dbias, ws, q, k, v, dqkv, dwq, dwk, dbq):
+        assert q_.intact() and q_.untouched(q_.t), "a refused call wrote to a buffer"
+    for q_ in (x, w, mod, g, rstd, y, gate, qkv, wq, cs, gq):
+        assert q_.intact(), "a canary changed"
 
 
 def test_case_names_are_unique():

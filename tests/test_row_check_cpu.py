@@ -1,6 +1,6 @@
 """The bounds of tests/row_check.py pass and bite (CPU only).
 
-A plain torch f32 emulation of each row kernel of csrc/elementwise.hip rounds where the kernel rounds.  It runs with two associations of
+A plain torch f32 emulation of each row kernel of csrc/elementwise.hip and csrc/qk_rope.hip rounds where the kernel rounds.  It runs with two associations of
 every sum (sequential; pairwise halves, as the wave butterflies pair lanes) and with products contracted into the following add (that one
 product-add in f64, rounded once) or not.  The row mean of the LayerNorm form is the one sum whose bound depends on the association
 (row_check.py R4: NCH + 9 roundings deep), so it is always summed pairwise, whose depth log2(D) <= 8 + NCH is within that count.

@@ -2,7 +2,7 @@
 """In-kernel timeline of the fused VMAE encoder's MLP steps (shader-clock stamps of waves 0 and 4 of two workgroups: ring wait + barrier,
 fc1 + GELU, bias / convert, fc2).  Needs a TIMING build of csrc/vmae_fused.hip (-DVF_TL=1: the stamps overwrite the head of the output and
 the extra registers spill -- never the product library):
-    hipcc ... -DVF_TL=1 -c vmae_fused.hip -o build/vf_tl.o && hipcc -shared -o ../libldmae_hip_tl.so build/{core,gemm,elementwise,attention,vmae}.o build/vf_tl.o
+    hipcc ... -DVF_TL=1 -c vmae_fused.hip -o build/vf_tl.o && hipcc -shared -o ../libldmae_hip_tl.so build/{core,gemm,elementwise,qk_rope,pointwise,attention,vmae}.o build/vf_tl.o
     LDMAE_HIP_LIB=.../libldmae_hip_tl.so python tools/vmae_timeline.py"""
 import os, sys, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
