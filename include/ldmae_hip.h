@@ -404,7 +404,18 @@ int ldmae_fid_stats_accumulate(const float* feats, int n, int D, const float* sh
  * pr_flags: the same d between u [M, D] and v [N, D]; u_in [M, nk] = 1 where some j has d(i, j) <= rv[j, k], v_in [N, nk] = 1 where some
  * i has d(i, j) <= ru[i, k]; the caller zeroes u_in / v_in; only 1s are stored.
  * adm_softmax_is: p = softmax(logits [M, C]) in f32; h [M] = sum_c p log p (f64, 0 log 0 = 0); S [ceil(M / split), C] = sum of p over
- * each split of `split` consecutive rows (f64, fixed order).  workspace: adm_is_workspace_bytes(M, C, split) bytes. */
+ * each split of `split` consecutive rows (f64, fixed order).  workspace: adm_is_workspace_bytes(M, C, split) bytes.
+ * kid_sums: the sums of the unbiased MMD^2 with the cubic polynomial kernel k(x, y) = (gamma x.y + coef0)^3 over S subsets of m rows each,
+ * in one launch.  a [Na, D], b [Nb, D] f32; idx_a / idx_b [S, m] int32: row i of subset s is a[idx_a[s, i]] (b[idx_b[s, i]]), read through
+ * the index, never gathered.  The kernel TRUSTS the tables: the caller checks every entry against [0, Na) / [0, Nb) on their host copy.
+ * Per element g = the exact-f32 MFMA dot product, p = fmaf(gamma, g, coef0), p3 = (p * p) * p (each step rounded once to f32), added in
+ * f64.  out [S, 3] f64 = (sum over i != j of k(a_i, a_j), sum over i != j of k(b_i, b_j), sum over all i, j of k(a_i, b_j)), i and j
+ * positions in the subset.  Partials are one f64 per (s, sum, 128-row tile, 64-column tile), added in ascending (row tile, column tile)
+ * order: no atomics, and the same bits for every nsplit.  workspace: kid_workspace_bytes(S, m) bytes.  Refused: m < 2, m > min(Na, Nb),
+ * S < 1, S > 21845 (the grid's y extent holds 3 S).
+ * ball_counts: d as in knn_radii between u [M, D] (norms nu, ONE radius column ru [M], squared distances as knn_radii writes them) and
+ * v [N, D] (norms nv); counts [M] = #{ j : d(i, j) < ru[i] }, STRICTLY less (pr_flags keeps its <=).  partials (int,
+ * ball_counts_partials_bytes(M, nsplit) bytes) hold one count per (row, column range, half tile); integer sums: nsplit cannot change them. */
 int ldmae_adm_preprocess(const unsigned char* img, float* out, int B, int H, int W, int Ho, int Wo, void* stream);
 int ldmae_adm_spatial_tap(const float* x, int ldx, int xoff, float* out, int B, int HW, int C, void* stream);
 int ldmae_row_sqnorms_f32(const float* x, int M, int D, float* out, void* stream);
@@ -416,6 +427,12 @@ int ldmae_pr_flags(const float* u, const float* nu, const float* ru, int M, cons
                    int nsplit, int* u_in, int* v_in, void* stream);
 long ldmae_adm_is_workspace_bytes(int M, int C, int split);
 int ldmae_adm_softmax_is(const float* logits, int M, int C, int split, void* workspace, double* h, double* S, void* stream);
+long ldmae_kid_workspace_bytes(int S, int m);
+int ldmae_kid_sums(const float* a, int Na, const float* b, int Nb, int D, const int* idx_a, const int* idx_b, int S, int m, float gamma,
+                   float coef0, int nsplit, void* workspace, double* out, void* stream);
+long ldmae_ball_counts_partials_bytes(int M, int nsplit);
+int ldmae_ball_counts(const float* u, const float* nu, const float* ru, int M, const float* v, const float* nv, int N, int D, int nsplit,
+                      int* partials, int* counts, void* stream);
 
 /* ---- tokenizer evaluation: rFID, PSNR, SSIM and LPIPS (reference evaluate_tokenizer.py, models/lpips.py), f32 ----------------------
  * lpips_prep: input / target NCHW [B, 3, H, W] -> out NHWC [2B, H, W, 4] = (x - shift) / scale of LPIPS' ScalingLayer (shift -0.030, -0.088,

@@ -3,7 +3,8 @@
 //   - the sFID spatial tap: channels [0, 7) of Mixed_6d's output (TF mixed_6/conv), flattened in TF's NHWC order;
 //   - f64 row norms |u|^2 rounded to f32 once;
 //   - one NT pairwise GEMM core U[M, D] . V[N, D]^T on the exact-f32 MFMA with three epilogues: plain logits, per-row k smallest squared
-//     distances (k-NN radii) and the precision / recall membership flags;
+//     distances (k-NN radii) and the precision / recall membership flags; two more for KID (polynomial-kernel sums in f64 over index
+//     subsets) and for density / coverage (per-row ball counts);
 //   - the softmax + Inception Score sums in f64 with fixed-order partials.
 #include "common.h"
 
@@ -98,20 +99,36 @@ extern "C" int ldmae_row_sqnorms_f32(const float* x, int M, int D, float* out, v
 //              in registers and writes them as one partial list.
 //   PW_PR:     the same d; u_in[i, k] = 1 if some column j has d <= rv[j, k]; v_in[j, k] = 1 if some row i has d <= ru[i, k]: plain stores
 //              of 1 into flags the caller zeroed (an OR: idempotent, no ordering needed).
+//   PW_COUNT:  the same d; each (row, split, half of the tile's columns) counts its columns with d < ru[i] (strictly) and writes the count as
+//              one integer partial; count_merge_kernel adds a row's partials (integers: no order to fix).
+//   PW_KID:    rows are read THROUGH an index table (row i of the operand is x[idx[i]], never gathered); blockIdx.y = 3 s + which picks the
+//              subset s and the pair which = 0: (a, a), 1: (b, b), 2: (a, b).  Per element p = fmaf(gamma, u.v, coef0), p3 = (p * p) * p with
+//              one rounding per step; p3 is added in f64 over the valid elements (i < m, j < m, and i != j for which < 2: both sides are the
+//              same subset, so the position diagonal is the trace).  A thread adds its 32 elements in (j, i, r) order, the 64 lanes fold in
+//              a butterfly, the four wave sums as (w0 + w1) + (w2 + w3): one f64 partial per (s, which, row tile, column tile) -- per TILE, not
+//              per split, so kid_fold_kernel's sum over the tiles in ascending (row tile, column tile) order is the same bits for every nsplit.
 constexpr int PW_BM = 128, PW_BN = 64, PW_BK = 16, PW_LD = 20, PW_NT = 256, PW_DLD = PW_BN + 1;
 constexpr int KNN_KP = 8;           // list length: radii for neighbourhood sizes 0..7 (sorted index k, self-distance included)
 constexpr int PR_MAXK = 8;          // at most 8 neighbourhood sizes
-enum { PW_LOGITS = 0, PW_KNN = 1, PW_PR = 2 };
+enum { PW_LOGITS = 0, PW_KNN = 1, PW_PR = 2, PW_KID = 3, PW_COUNT = 4 };
 
 struct PairArgs {
   const float *u, *v, *nu, *nv, *ru, *rv;
   int M, N, D, nsplit, tps, nk;
   float* out;                        // PW_LOGITS: [M, N]; PW_KNN: partials [M, nsplit, 2, KNN_KP]
-  int *u_in, *v_in;                  // PW_PR: [M, nk], [N, nk]
+  int *u_in, *v_in;                  // PW_PR: [M, nk], [N, nk]; PW_COUNT: u_in = partials [M, nsplit, 2]
 };
+// PW_KID alone takes more (the other modes keep PairArgs as their kernel argument): u = a, v = b, M = N = m
+struct KidArgs : PairArgs {
+  const int *idx_u, *idx_v;          // [S, m]
+  double* part;                      // [S, 3, row tiles, column tiles]
+  float gamma, coef0;
+};
+template <int MODE> struct PairArgsOf { using type = PairArgs; };
+template <> struct PairArgsOf<PW_KID> { using type = KidArgs; };
 
 template <int MODE, bool VEC>
-__global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
+__global__ __launch_bounds__(PW_NT) void pairwise_kernel(typename PairArgsOf<MODE>::type a) {
   constexpr int STAGE = 2 * PW_BM * PW_LD + 2 * PW_BN * PW_LD, DIST = PW_BM * PW_DLD;
   __shared__ __attribute__((aligned(16))) float smem[STAGE > DIST ? STAGE : DIST];
   __shared__ float Ru[MODE == PW_PR ? PW_BM * PR_MAXK : 1], Rv[MODE == PW_PR ? PW_BN * PR_MAXK : 1];
@@ -122,12 +139,31 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
   const int wm = wave >> 1, wn = wave & 1;
   const int rt = (int)(blockIdx.x / a.nsplit), split = (int)(blockIdx.x % a.nsplit);
   const int m0 = rt * PW_BM;
+  const float *ub = a.u, *vb = a.v;
+  const int *iu = nullptr, *iv = nullptr;
+  int which = 0;
+  if constexpr (MODE == PW_KID) {
+    which = (int)(blockIdx.y % 3);
+    const size_t sub = (size_t)(blockIdx.y / 3) * a.M;
+    iu = (which == 1 ? a.idx_v : a.idx_u) + sub;
+    iv = (which == 0 ? a.idx_u : a.idx_v) + sub;
+    ub = which == 1 ? a.v : a.u;
+    vb = which == 0 ? a.u : a.v;
+  }
+  auto urow_of = [&](int pos) -> const float* {                // pos < M (clamped by the caller)
+    if constexpr (MODE == PW_KID) return ub + (size_t)iu[pos] * a.D;
+    return ub + (size_t)pos * a.D;
+  };
+  auto vrow_of = [&](int pos) -> const float* {
+    if constexpr (MODE == PW_KID) return vb + (size_t)iv[pos] * a.D;
+    return vb + (size_t)pos * a.D;
+  };
   const int col_tiles = (a.N + PW_BN - 1) / PW_BN;
   const int ct0 = split * a.tps, ct1 = min(ct0 + a.tps, col_tiles);
   const int lr = tid >> 2, lc = (tid & 3) * 4;
   const float* urow[2];
 #pragma unroll
-  for (int p = 0; p < 2; ++p) urow[p] = a.u + (size_t)min(m0 + lr + p * 64, a.M - 1) * a.D;   // rows past M: real data, never stored
+  for (int p = 0; p < 2; ++p) urow[p] = urow_of(min(m0 + lr + p * 64, a.M - 1));              // rows past M: real data, never stored
   const int q4 = (lane >> 4) * 4, r16 = lane & 15;
 
   // epilogue state: KNN lists of row er = tid >> 1, columns [eh * 32, eh * 32 + 32) of each tile; PR row bits of the same thread
@@ -136,6 +172,11 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
 #pragma unroll
   for (int q = 0; q < KNN_KP; ++q) best[q] = INFINITY;
   unsigned rowbits = 0;
+  int count = 0;                                              // PW_COUNT: columns inside row er's ball, this thread's half of each tile
+  float rrow = -1.f;                                          // d >= 0: a padded row counts nothing
+  if constexpr (MODE == PW_COUNT) {
+    if (m0 + er < a.M) rrow = a.ru[m0 + er];
+  }
   if (MODE == PW_PR) {
     for (int e = tid; e < PW_BM * a.nk; e += PW_NT) {
       const int m = m0 + e / a.nk;
@@ -157,7 +198,7 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
   const int nk_steps = (a.D + PW_BK - 1) / PW_BK;
   for (int ct = ct0; ct < ct1; ++ct) {
     const int n0 = ct * PW_BN;
-    const float* vrow = a.v + (size_t)min(n0 + lr, a.N - 1) * a.D;
+    const float* vrow = vrow_of(min(n0 + lr, a.N - 1));
     f32x4 acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -217,6 +258,30 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
           }
       }
       continue;
+    } else if constexpr (MODE == PW_KID) {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn * 32 + j * 16 + r16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int m = m0 + wm * 64 + i * 16 + q4 + r;
+            if (m < a.M && n < a.N && (which == 2 || m != n)) {
+              const float p = fmaf(a.gamma, acc[i][j][r], a.coef0);
+              t += (double)__fmul_rn(__fmul_rn(p, p), p);
+            }
+          }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+      double* red = (double*)smem;                                         // the staging buffers are free: the K loop ended on a barrier
+      if (lane == 0) red[wave] = t;
+      __syncthreads();
+      const size_t row_tiles = gridDim.x / a.nsplit;
+      if (tid == 0) a.part[((size_t)blockIdx.y * row_tiles + rt) * col_tiles + ct] = (red[0] + red[1]) + (red[2] + red[3]);
+      __syncthreads();                                                     // red is read before the next tile's staging
     } else {
       // distances of the tile into LDS (the staging buffers are free: the K loop ended on a barrier); padding is +inf
 #pragma unroll
@@ -253,6 +318,9 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
             best[0] = fminf(best[0], v);
           }
         }
+      } else if constexpr (MODE == PW_COUNT) {
+        const float* drow = Ds + er * PW_DLD + eh * 32;
+        for (int c = 0; c < 32; ++c) count += drow[c] < rrow ? 1 : 0;      // padding is +inf: never inside
       } else {
         // rows: u_in[er, k] |= any over this thread's 32 columns of d <= rv[n, k]
         const float* drow = Ds + er * PW_DLD + eh * 32;
@@ -283,17 +351,18 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(PairArgs a) {
 #pragma unroll
     for (int q = 0; q < KNN_KP; ++q) dst[q] = best[q];
   }
+  if (MODE == PW_COUNT && m < a.M) a.u_in[((size_t)m * a.nsplit + split) * 2 + eh] = count;
   if (MODE == PW_PR && m < a.M && rowbits)
     for (int k = 0; k < a.nk; ++k)
       if (rowbits >> k & 1) a.u_in[(size_t)m * a.nk + k] = 1;
 }
 
 template <int MODE>
-static void launch_pairwise(const PairArgs& a, hipStream_t st) {
+static void launch_pairwise(const typename PairArgsOf<MODE>::type& a, hipStream_t st, unsigned grid_y = 1) {
   const bool vec = a.D % 4 == 0 && ((uintptr_t)a.u & 15) == 0 && ((uintptr_t)a.v & 15) == 0;
   const unsigned grid = cdiv(a.M, PW_BM) * a.nsplit;
-  if (vec) hipLaunchKernelGGL((pairwise_kernel<MODE, true>), dim3(grid), dim3(PW_NT), 0, st, a);
-  else hipLaunchKernelGGL((pairwise_kernel<MODE, false>), dim3(grid), dim3(PW_NT), 0, st, a);
+  if (vec) hipLaunchKernelGGL((pairwise_kernel<MODE, true>), dim3(grid, grid_y), dim3(PW_NT), 0, st, a);
+  else hipLaunchKernelGGL((pairwise_kernel<MODE, false>), dim3(grid, grid_y), dim3(PW_NT), 0, st, a);
 }
 
 static bool pair_sizes_ok(long M, long N, long D) {
@@ -372,6 +441,65 @@ extern "C" int ldmae_pr_flags(const float* u, const float* nu, const float* ru, 
   PairArgs a{u, v, nu, nv, ru, rv, M, N, D, nsplit, tps, nk, nullptr, u_in, v_in};
   launch_pairwise<PW_PR>(a, as_stream(stream));
   LDMAE_CHECK_LAUNCH("pr_flags");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ ball counts (density / coverage)
+extern "C" long ldmae_ball_counts_partials_bytes(int M, int nsplit) {
+  if (M <= 0 || nsplit <= 0) return -1;
+  return (long)M * nsplit * 2 * (long)sizeof(int);
+}
+
+__global__ __launch_bounds__(256) void count_merge_kernel(const int* __restrict__ part, int M, int nparts, int* __restrict__ counts) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const int* p = part + (size_t)m * nparts;
+  int c = 0;
+  for (int e = 0; e < nparts; ++e) c += p[e];
+  counts[m] = c;
+}
+
+extern "C" int ldmae_ball_counts(const float* u, const float* nu, const float* ru, int M, const float* v, const float* nv, int N, int D, int nsplit,
+                                 int* partials, int* counts, void* stream) {
+  LDMAE_REQUIRE(u && nu && ru && v && nv && partials && counts && pair_sizes_ok(M, N, D), "ball_counts: bad arguments (M %d, N %d, D %d)", M, N, D);
+  LDMAE_REQUIRE(nsplit >= 1 && (long)M * nsplit < (1L << 30), "ball_counts: nsplit %d (>= 1, M * nsplit < 2^30)", nsplit);
+  const int col_tiles = (int)cdiv(N, PW_BN);
+  const int tps = (col_tiles + nsplit - 1) / nsplit;
+  PairArgs a{u, v, nu, nv, ru, nullptr, M, N, D, nsplit, tps, 1, nullptr, partials, nullptr};
+  launch_pairwise<PW_COUNT>(a, as_stream(stream));      // splits past the last column tile write zero counts
+  hipLaunchKernelGGL(count_merge_kernel, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), partials, M, nsplit * 2, counts);
+  LDMAE_CHECK_LAUNCH("ball_counts");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ KID (polynomial-kernel sums)
+extern "C" long ldmae_kid_workspace_bytes(int S, int m) {
+  if (S <= 0 || m <= 0) return -1;
+  return (long)S * 3 * cdiv(m, PW_BM) * cdiv(m, PW_BN) * (long)sizeof(double);
+}
+
+// out[s, which] = the tile partials of (s, which) added in ascending (row tile, column tile) order: one thread per sum
+__global__ __launch_bounds__(256) void kid_fold_kernel(const double* __restrict__ part, int nsums, int tiles, double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nsums) return;
+  const double* p = part + (size_t)i * tiles;
+  double s = 0.0;
+  for (int t = 0; t < tiles; ++t) s += p[t];
+  out[i] = s;
+}
+
+extern "C" int ldmae_kid_sums(const float* a, int Na, const float* b, int Nb, int D, const int* idx_a, const int* idx_b, int S, int m, float gamma,
+                              float coef0, int nsplit, void* workspace, double* out, void* stream) {
+  LDMAE_REQUIRE(a && b && idx_a && idx_b && workspace && out && pair_sizes_ok(Na, Nb, D), "kid_sums: bad arguments (Na %d, Nb %d, D %d)", Na, Nb, D);
+  LDMAE_REQUIRE(S >= 1 && 3L * S <= 65535 && m >= 2 && m <= Na && m <= Nb && nsplit >= 1,
+                "kid_sums: %d subsets (1..21845) of %d rows (2..min(Na, Nb) = %d), nsplit %d (>= 1)", S, m, Na < Nb ? Na : Nb, nsplit);
+  const int row_tiles = (int)cdiv(m, PW_BM), col_tiles = (int)cdiv(m, PW_BN);
+  const int tps = (col_tiles + nsplit - 1) / nsplit;
+  KidArgs p{{a, b, nullptr, nullptr, nullptr, nullptr, m, m, D, nsplit, tps, 0, nullptr, nullptr, nullptr}, idx_a, idx_b, (double*)workspace, gamma, coef0};
+  launch_pairwise<PW_KID>(p, as_stream(stream), 3u * S);      // every (row tile, column tile) is written: nsplit * tps >= column tiles
+  hipLaunchKernelGGL(kid_fold_kernel, dim3(cdiv(3L * S, 256)), dim3(256), 0, as_stream(stream), (const double*)workspace, 3 * S, row_tiles * col_tiles,
+                     out);
+  LDMAE_CHECK_LAUNCH("kid_sums");
   return 0;
 }
 

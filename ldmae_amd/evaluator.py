@@ -8,6 +8,12 @@ fc.weight of the same state dict without its bias, as the graph's softmax/logits
 f32 (ADM's own fallback when its f16 distances are not finite).
 
     python -m ldmae_amd.evaluator REF SAMPLE [--batch-size 64] [--weights P] [--device cuda]
+        [--kid [--kid-subsets 100] [--kid-subset-size 1000] [--kid-seed 2020]] [--density-coverage [--nearest-k 5]]
+
+--kid adds one line, `KID: <mean> +- <std>` (Binkowski et al. 2018: the unbiased MMD^2 with the cubic polynomial kernel over random
+subsets of the pool features); --density-coverage adds `Density:` and `Coverage:` (Naeem et al. 2020).  Neither writes anything into the
+.npz caches, and without the flags the output is what it was.  Agreement with torch-fidelity's KID and with the prdc package has NOT been
+checked (neither was available); the tests compare with f64 restatements of the papers' formulas.
 
 REF and SAMPLE are .npz files with arr_0 = uint8 [N, H, W, 3] (read a batch at a time), or folders of images (fid.list_images order).
 Like the reference, an .npz that lacks act / act_s gets act, act_s, mu, mu_s, sigma, sigma_s added (written to a temporary file, then
@@ -154,6 +160,45 @@ def inception_score_from_sums(h, S, n_rows, split_size=5000):
     return float(np.mean(scores))
 
 
+# ---------------------------------------------------------------------------------------------------- KID (Binkowski et al. 2018)
+def kid_subset_indices(n1, n2, num_subsets, subset_size, seed):
+    """(idx1 [S, m], idx2 [S, m]) int32: numpy.random.RandomState(seed); per subset choice(n1, m, replace=False) and THEN
+    choice(n2, m, replace=False) -- the order torch-fidelity documents for its KID.  Agreement with torch-fidelity's draws has NOT been
+    checked: that package was not available when this was written."""
+    n1, n2, S, m = int(n1), int(n2), int(num_subsets), int(subset_size)
+    if S < 1 or m < 2:
+        raise ValueError(f"kid_subset_indices: {S} subsets of {m} rows (at least 1 subset of at least 2 rows)")
+    if m > min(n1, n2):
+        raise ValueError(f"kid_subset_indices: subset_size {m} is above the smaller feature set ({min(n1, n2)} rows): "
+                         f"pass a subset_size of at most {min(n1, n2)}")
+    rng = np.random.RandomState(seed)
+    idx1, idx2 = np.empty((S, m), np.int32), np.empty((S, m), np.int32)
+    for s in range(S):
+        idx1[s] = rng.choice(n1, m, replace=False)
+        idx2[s] = rng.choice(n2, m, replace=False)
+    return idx1, idx2
+
+
+def kid_from_sums(sums, m):
+    """sums [S, 3] = (sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)) per subset of m rows ->
+    (mean, std) over the subsets of the unbiased mmd^2 = aa / (m (m - 1)) + bb / (m (m - 1)) - 2 ab / m^2, in host f64; std is numpy.std
+    (the population form)."""
+    s = np.asarray(sums, np.float64)
+    m = int(m)
+    if s.ndim != 2 or s.shape[1] != 3 or s.shape[0] < 1 or m < 2:
+        raise ValueError(f"kid_from_sums: sums {s.shape} must be [S, 3] with S >= 1, and m = {m} at least 2")
+    mmd2 = s[:, 0] / (m * (m - 1)) + s[:, 1] / (m * (m - 1)) - 2.0 * s[:, 2] / (m * m)
+    return float(np.mean(mmd2)), float(np.std(mmd2))
+
+
+def _check_nearest_k(nearest_k):
+    k = int(nearest_k)
+    if not 1 <= k <= 7:
+        raise ValueError(f"density_coverage: nearest_k {nearest_k} outside 1..7 (the k-NN kernel keeps the 8 smallest distances of a row, "
+                         "the self-distance among them)")
+    return k
+
+
 def _features_2d(x, what):
     """A [N, D] f32 array (numpy or torch) checked finite on the host side of the call, before any kernel."""
     if isinstance(x, torch.Tensor):
@@ -218,6 +263,22 @@ class ManifoldEstimator:
         in1, in2 = ops.pr_flags(self._dev(features_1), self._dev(r1), self._dev(features_2), self._dev(r2), nsplit=self.nsplit)
         # exact counts over n, as np.mean of the boolean flags gives them
         return (in2.sum(0).cpu().numpy().astype(np.float64) / in2.shape[0], in1.sum(0).cpu().numpy().astype(np.float64) / in1.shape[0])
+
+    def density_coverage(self, features_real, features_fake, nearest_k=5):
+        """(density, coverage) of Naeem et al. 2020: with r_i the squared distance of real row i to its nearest_k-th neighbour (sorted index
+        nearest_k of its distances to all real rows, the self-distance at index 0 -- manifold_radii with nhood_sizes=(nearest_k,), no
+        percentile clamp) and counts[i] = #{ fake j : d(i, j) < r_i }: density = sum_i counts[i] / (nearest_k N_fake), coverage = the
+        fraction of real rows with counts[i] > 0 (a real row's nearest fake lies inside its ball exactly when some fake does)."""
+        from . import ops
+        k = _check_nearest_k(nearest_k)
+        features_real = _features_2d(features_real, "density_coverage features_real")
+        features_fake = _features_2d(features_fake, "density_coverage features_fake")
+        if features_real.shape[1] != features_fake.shape[1]:
+            raise ValueError(f"density_coverage: feature widths {features_real.shape[1]} and {features_fake.shape[1]} differ")
+        real = self._dev(features_real)
+        radii = ManifoldEstimator((k,), None, self.eps, self.device, self.nsplit).manifold_radii(real)
+        counts = ops.ball_counts(real, self._dev(radii[:, 0]), self._dev(features_fake), nsplit=self.nsplit).cpu().numpy().astype(np.int64)
+        return float(counts.sum() / (k * features_fake.shape[0])), float(np.mean(counts > 0))
 
 
 class Evaluator:
@@ -301,6 +362,26 @@ class Evaluator:
         pr = self.manifold_estimator.evaluate_pr(activations_ref, radii_1, activations_sample, radii_2)
         return float(pr[0][0]), float(pr[1][0])
 
+    def compute_kid(self, act_ref, act_sample, num_subsets=100, subset_size=1000, seed=2020, gamma=None, coef0=1.0):
+        """(mean, std) over num_subsets subsets of the unbiased MMD^2 between subset_size rows of each feature set, with the cubic
+        polynomial kernel (gamma x.y + coef0)^3; gamma=None is 1 / D.  The subsets are kid_subset_indices(...); all of them run in one
+        launch (ops.kid_sums), the estimator itself in host f64 (kid_from_sums)."""
+        from . import ops
+        ref, sample = _features_2d(act_ref, "compute_kid act_ref"), _features_2d(act_sample, "compute_kid act_sample")
+        if ref.shape[1] != sample.shape[1]:
+            raise ValueError(f"compute_kid: feature widths {ref.shape[1]} and {sample.shape[1]} differ")
+        n = min(ref.shape[0], sample.shape[0])
+        if int(subset_size) > n:
+            raise ValueError(f"compute_kid: subset_size {subset_size} is above the smaller feature set ({n} rows): pass subset_size={n} or less")
+        idx1, idx2 = kid_subset_indices(ref.shape[0], sample.shape[0], num_subsets, subset_size, seed)
+        g = 1.0 / ref.shape[1] if gamma is None else float(gamma)
+        dev = self.manifold_estimator._dev
+        sums = ops.kid_sums(dev(ref), dev(sample), idx1, idx2, g, coef0, nsplit=self.manifold_estimator.nsplit)
+        return kid_from_sums(sums.cpu().numpy(), subset_size)
+
+    def compute_density_coverage(self, act_ref, act_sample, nearest_k=5):
+        return self.manifold_estimator.density_coverage(act_ref, act_sample, nearest_k)
+
 
 def activations_and_statistics(evaluator, path):
     """((pool, spatial), (stats, spatial stats)) of an input, with the reference's caching (evaluator.py:44-69): an .npz's act / act_s are
@@ -323,14 +404,25 @@ def activations_and_statistics(evaluator, path):
     return acts, stats
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="Inception Score, FID, sFID, precision and recall (the ADM evaluator) on the HIP Inception-v3")
+def build_parser():
+    ap = argparse.ArgumentParser(description="Inception Score, FID, sFID, precision and recall (the ADM evaluator) on the HIP Inception-v3; "
+                                             "optionally KID and density / coverage")
     ap.add_argument("ref_batch", help="reference batch: .npz with arr_0 uint8 [N, H, W, 3], or a folder of images")
     ap.add_argument("sample_batch", help="sample batch: .npz with arr_0 uint8 [N, H, W, 3], or a folder of images")
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--weights", default=None, help=f"{fid.WEIGHTS_NAME} (default: ${fid.WEIGHTS_ENV}, then torch.hub's checkpoints)")
     ap.add_argument("--device", default="cuda")
-    a = ap.parse_args(argv)
+    ap.add_argument("--kid", action="store_true", help="also print the Kernel Inception Distance (mean +- std over subsets) of the pool features")
+    ap.add_argument("--kid-subsets", type=int, default=100)
+    ap.add_argument("--kid-subset-size", type=int, default=1000)
+    ap.add_argument("--kid-seed", type=int, default=2020)
+    ap.add_argument("--density-coverage", action="store_true", help="also print density and coverage (Naeem et al. 2020) of the pool features")
+    ap.add_argument("--nearest-k", type=int, default=5)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     for p in (a.ref_batch, a.sample_batch):
         if not os.path.exists(p):
             raise SystemExit(f"no such file or folder: {p}")
@@ -349,6 +441,13 @@ def main(argv=None):
     out["precision"], out["recall"] = evaluator.compute_prec_recall(ref_acts[0], sample_acts[0])
     print("Precision:", out["precision"])
     print("Recall:", out["recall"])
+    if a.kid:
+        out["kid_mean"], out["kid_std"] = evaluator.compute_kid(ref_acts[0], sample_acts[0], a.kid_subsets, a.kid_subset_size, a.kid_seed)
+        print("KID:", out["kid_mean"], "+-", out["kid_std"])
+    if a.density_coverage:
+        out["density"], out["coverage"] = evaluator.compute_density_coverage(ref_acts[0], sample_acts[0], a.nearest_k)
+        print("Density:", out["density"])
+        print("Coverage:", out["coverage"])
     return out
 
 

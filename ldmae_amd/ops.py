@@ -1226,6 +1226,79 @@ def gelu_tanh_bwd(dout, pre):
     return dx
 
 
+# ----------------------------------------------------------------------------- KID and density / coverage (csrc/adm_eval.hip: PW_KID, PW_COUNT)
+# Two more passes of the ADM evaluator's pairwise core (row_sqnorms, default_col_splits and _pair_tiles are with its other wrappers below).
+# The kernels work on the caller's tensors as they are (copy=False); the KID index tables are HOST tables, checked and uploaded here.
+
+def ball_counts(u, ru, v, nu=None, nv=None, nsplit=None):
+    """u [M, D] with ONE radius per row ru [M] (squared distances, a column of knn_radii) and v [N, D] -> int32 [M]:
+    counts[i] = #{ j : d(i, j) < ru[i] }, strictly less, d the squared distance of knn_radii / pr_flags (density and coverage, Naeem et
+    al. 2020).  Integer sums: the same for every nsplit."""
+    _arg(u, "ball_counts u", torch.float32, ("M", "D"), copy=False)
+    M, D = u.shape
+    _arg(v, "ball_counts v", torch.float32, ("N", D), copy=False, like=u)
+    N = v.shape[0]
+    _arg(ru, "ball_counts ru", torch.float32, (M,), copy=False, like=u)
+    nu = row_sqnorms(u) if nu is None else nu
+    nv = row_sqnorms(v) if nv is None else nv
+    _arg(nu, "ball_counts nu", torch.float32, (M,), copy=False, like=u)
+    _arg(nv, "ball_counts nv", torch.float32, (N,), copy=False, like=u)
+    nsplit = default_col_splits(M, N) if nsplit is None else int(nsplit)
+    if nsplit < 1:
+        raise RuntimeError(f"ball_counts: nsplit {nsplit} (>= 1)")
+    nbytes = L.load().ldmae_ball_counts_partials_bytes(M, nsplit)
+    part = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=u.device)
+    counts = torch.empty(M, dtype=torch.int32, device=u.device)
+    call("ldmae_ball_counts", ptr(u), ptr(nu), ptr(ru), M, ptr(v), ptr(nv), N, D, nsplit, ptr(part), ptr(counts), stream())
+    return counts
+
+
+def check_kid_index_table(idx, n_rows, what):
+    """The range check ldmae_kid_sums leaves to its caller, on the HOST copy of one index table: [S, m] integers, every entry in [0, n_rows).
+    Returns the table as a contiguous int32 host tensor.  Raises ValueError naming the first bad subset and position."""
+    idx = torch.as_tensor(idx)
+    if idx.is_cuda:
+        raise ValueError(f"kid_sums: {what} is checked on its host copy; got a tensor on {idx.device}")
+    if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 2 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"kid_sums: {what} must be an [S, m] int32 / int64 table with S >= 1 and m >= 2, got {tuple(idx.shape)} {idx.dtype}")
+    bad = (idx < 0) | (idx >= int(n_rows))
+    if bool(bad.any()):
+        s, i = (int(t) for t in bad.nonzero()[0])
+        raise ValueError(f"kid_sums: {what}[{s}, {i}] = {int(idx[s, i])} (subset {s}, position {i}) is outside [0, {int(n_rows)})")
+    return idx.to(torch.int32).contiguous()
+
+
+def kid_sums(a, b, idx_a, idx_b, gamma, coef0=1.0, nsplit=None):
+    """The sums of KID's unbiased MMD^2 over S subsets in one launch (ldmae_kid_sums): a [Na, D], b [Nb, D] f32 on the device; idx_a / idx_b
+    [S, m] HOST index tables (numpy or torch, checked here against [0, Na) / [0, Nb) and uploaded; rows are read through them, not gathered)
+    -> f64 [S, 3] = (sum_{i != j} k(a_i, a_j), sum_{i != j} k(b_i, b_j), sum_{i, j} k(a_i, b_j)), k(x, y) = (gamma x.y + coef0)^3 with the dot
+    product, the fma and the two multiplies in f32 and the sums in f64.  Bitwise the same for every nsplit."""
+    _arg(a, "kid_sums a", torch.float32, ("Na", "D"), copy=False)
+    Na, D = a.shape
+    _arg(b, "kid_sums b", torch.float32, ("Nb", D), copy=False, like=a)
+    Nb = b.shape[0]
+    ia, ib = check_kid_index_table(idx_a, Na, "idx_a"), check_kid_index_table(idx_b, Nb, "idx_b")
+    if ia.shape != ib.shape:
+        raise ValueError(f"kid_sums: idx_a {tuple(ia.shape)} and idx_b {tuple(ib.shape)} must have one shape [S, m]")
+    S, m = ia.shape
+    if m > min(Na, Nb):
+        raise ValueError(f"kid_sums: subsets of {m} rows from {Na} / {Nb} feature rows")
+    if nsplit is None:                       # as default_col_splits, with the 3 S (subset, pair) planes of the grid counted in
+        row_tiles, col_tiles = _pair_tiles(m)[0], _pair_tiles(m)[1]
+        nsplit = max(1, min(col_tiles, -(-2048 // (row_tiles * 3 * S))))
+    nsplit = int(nsplit)
+    if nsplit < 1:
+        raise RuntimeError(f"kid_sums: nsplit {nsplit} (>= 1)")
+    ia, ib = ia.to(a.device), ib.to(a.device)
+    _arg(ia, "kid_sums idx_a", torch.int32, (S, m), copy=False, like=a)
+    _arg(ib, "kid_sums idx_b", torch.int32, (S, m), copy=False, like=a)
+    nbytes = L.load().ldmae_kid_workspace_bytes(S, m)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(S, 3, dtype=torch.float64, device=a.device)
+    call("ldmae_kid_sums", ptr(a), Na, ptr(b), Nb, D, ptr(ia), ptr(ib), S, m, float(gamma), float(coef0), nsplit, ptr(ws), ptr(out), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- FID evaluation (csrc/inception.hip), NHWC f32
 # A channel slice is (tensor [B, H, W, Ctot], offset, C): the kernels read / write channels [offset, offset + C) of every pixel.
 # From here to the end of the file the kernels work on the caller's tensors as they are: every _arg below says copy=False, or out=True for an output.

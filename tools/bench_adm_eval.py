@@ -3,9 +3,13 @@
   - evaluate_pr for 10 000 reference x 50 000 sample features: ms and TF/s at 2 N1 N2 D FLOP;
   - the softmax / Inception Score path for 50 000 rows (logits GEMM against a [1008, 2048] weight + softmax sums);
   - images/s of InceptionFID.adm_features at batch 250 (random weights in the real layout, 256 x 256 uint8 images);
-  - as a YARDSTICK ONLY (not part of the package): the same radii with torch.cdist + kthvalue on the GPU, in row blocks.
+  - KID: ops.kid_sums for 100 subsets of 1000 rows at D = 2048 (one launch); density / coverage: ops.ball_counts for 10 000 x 50 000;
+  - as a YARDSTICK ONLY (not part of the package): the same radii with torch.cdist + kthvalue on the GPU, in row blocks; the KID sums with
+    torch's gather + matmul in f32 and the ball counts with torch.cdist.
 
     python tools/bench_adm_eval.py [--iters 3] [--no-torch] [--json OUT]
+
+profiles/kid_dc_bench.txt holds the KID and density / coverage lines of one run.
 """
 import argparse
 import json
@@ -45,6 +49,27 @@ def torch_radii(x, k=3, rows=2048):
     for i in range(0, x.shape[0], rows):
         d = torch.cdist(x[i:i + rows], x).square_()
         out[i:i + rows] = d.kthvalue(k + 1, dim=1).values
+    return out
+
+
+def torch_kid(a, b, idx1, idx2, gamma, coef0=1.0):
+    """f32 restatement with torch's own kernels: gather the subsets, three batched products, cube, f64 sums -> [S, 3]."""
+    i1, i2 = torch.as_tensor(idx1, device=a.device).long(), torch.as_tensor(idx2, device=a.device).long()
+    out = torch.empty(i1.shape[0], 3, dtype=torch.float64, device=a.device)
+    for s in range(i1.shape[0]):
+        x, y = a[i1[s]], b[i2[s]]
+        kxx, kyy, kxy = (gamma * (x @ x.T) + coef0) ** 3, (gamma * (y @ y.T) + coef0) ** 3, (gamma * (x @ y.T) + coef0) ** 3
+        out[s, 0] = kxx.double().sum() - kxx.diagonal().double().sum()
+        out[s, 1] = kyy.double().sum() - kyy.diagonal().double().sum()
+        out[s, 2] = kxy.double().sum()
+    return out
+
+
+def torch_ball_counts(u, ru, v, rows=2048):
+    out = torch.empty(u.shape[0], dtype=torch.int32, device=u.device)
+    for i in range(0, u.shape[0], rows):
+        d = torch.cdist(u[i:i + rows], v).square_()
+        out[i:i + rows] = (d < ru[i:i + rows, None]).sum(1)
     return out
 
 
@@ -97,7 +122,36 @@ def main():
     res["metrics_50k_vs_10k_ms"] = total
     say(f"metric arithmetic of a 50k-sample / 10k-reference evaluation (2 radii passes + PR + IS): {total:.1f} ms")
 
+    # KID: 100 subsets of 1000 rows (the defaults of --kid) from the 10k reference and the 50k sample features, one launch
+    idx1, idx2 = ev.kid_subset_indices(f10.shape[0], f50.shape[0], 100, 1000, 2020)
+    t = timed(lambda: ops.kid_sums(f10, f50, idx1, idx2, 1.0 / D), a.iters)
+    tf = 2.0 * 3 * 100 * 1000 * 1000 * D / t / 1e12
+    res["kid_100x1000_ms"], res["kid_100x1000_tflops"] = t * 1e3, tf
+    say(f"kid_sums 100 subsets x 1000 rows D={D}: {t * 1e3:9.2f} ms  {tf:6.1f} TF/s  (host index check and upload included)")
+    mean, std = ev.kid_from_sums(ops.kid_sums(f10, f50, idx1, idx2, 1.0 / D).cpu().numpy(), 1000)
+    say(f"  (synthetic KID {mean:.6g} +- {std:.3g})")
+    # density / coverage: one ball-count pass, 10k real x 50k fake, radii of nearest_k = 5
+    r5 = ops.knn_radii(f10, (5,))[:, 0].contiguous()
+    n10, n50 = ops.row_sqnorms(f10), ops.row_sqnorms(f50)
+    t = timed(lambda: ops.ball_counts(f10, r5, f50, nu=n10, nv=n50), a.iters)
+    tf = 2.0 * 10_000 * 50_000 * D / t / 1e12
+    res["ball_counts_10k_50k_ms"], res["ball_counts_10k_50k_tflops"] = t * 1e3, tf
+    say(f"ball_counts 10000 x 50000 D={D}: {t * 1e3:9.2f} ms  {tf:6.1f} TF/s")
+    counts = ops.ball_counts(f10, r5, f50, nu=n10, nv=n50)
+    say(f"  (synthetic density {float(counts.sum()) / (5 * 50_000):.4f}, coverage {float((counts > 0).float().mean()):.4f})")
+
     if not a.no_torch:
+        try:
+            t = timed(lambda: torch_kid(f10, f50, idx1, idx2, 1.0 / D), a.iters)
+            tm, _ = ev.kid_from_sums(torch_kid(f10, f50, idx1, idx2, 1.0 / D).cpu().numpy(), 1000)
+            res["yardstick_torch_kid_100x1000_ms"] = t * 1e3
+            say(f"[yardstick only] torch f32 gather + matmul KID sums, 100 x 1000: {t * 1e3:9.2f} ms  (KID {tm:.6g}, ours {mean:.6g})")
+            t = timed(lambda: torch_ball_counts(f10, r5, f50), a.iters)
+            same = float((torch_ball_counts(f10, r5, f50) == counts).float().mean())
+            res["yardstick_torch_ball_counts_10k_50k_ms"] = t * 1e3
+            say(f"[yardstick only] torch.cdist ball counts 10000 x 50000: {t * 1e3:9.2f} ms  (rows with the same count: {same:.4f})")
+        except RuntimeError as e:
+            say(f"[yardstick only] torch KID / ball counts not run: {e}")
         try:
             t = timed(lambda: torch_radii(f10), a.iters)
             ok = bool(torch.allclose(torch_radii(f10), ops.knn_radii(f10, (3,))[:, 0], rtol=1e-3, atol=1e-3))
