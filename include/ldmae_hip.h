@@ -660,6 +660,51 @@ int ldmae_gemm_nt_qkv_rope_mx8(const void* Aq, const void* As, int lda, const vo
 #define LDMAE_MX8_COUNT_GEMM 2
 int ldmae_mx8_launch_counts(long* counts, int n, int reset);
 
+/* ---- Linear-probe and k-NN evaluation of tokenizer features (csrc/linprobe.hip, ldmae_amd/linear_probe.py) ----
+ * No atomics: every sum has one fixed order, two launches on the same inputs give the same bits.  The entry points that take a dtype code
+ * refuse every code they have no kernel for (the rule at the dtype codes above).
+ * token_mean (f32, bf16, fp16 -> f32): out [B, D] = (1 / N) sum_n x[b, n, col0 + d]; token row (b, n) starts at x + (b N + n) ldx, so a
+ *   channel slice of a wider token buffer is read in place.  f32 sums: 16 row groups of rows n = g, g + 16, ... in ascending order, the 16
+ *   group sums in ascending order, one true division by N.
+ * bn1d_fwd (f32): BatchNorm1d(affine = False).  training != 0: mean [D] = the f32 rounding of the column mean, var = the f32 rounding of
+ *   sum (x - mean)^2 / B with THAT mean (two passes, never E[x^2] - mean^2; both sums in f64), xhat = (x - mean) * (1 / sqrtf(var + eps));
+ *   run_mean = momentum mean + (1 - momentum) run_mean, run_var likewise with the unbiased variance (sum / (B - 1)), both in place;
+ *   save_mean / save_rstd [D] optional.  B = 1 is refused (torch does).  training == 0: mean = run_mean, var = run_var, nothing is updated.
+ * softmax_xent (f32): logits [B, C] with row stride ld, labels int64 [B].  loss [B] = m + log sum exp(l - m) - l[y] (m the row maximum);
+ *   dlogits (optional, row stride ldd) = (softmax - onehot) * grad_scale; rank [B] = #{c : l[c] > l[y]} + #{c < y : l[c] == l[y]} --
+ *   comparisons of the given f32 values only: top-1 is rank == 0, top-5 rank < 5.  Rows of C <= 4096 are read once and kept in registers.
+ *   The caller checks labels against [0, C) on their host copy (ops.check_labels); a label outside gives loss NaN, rank -1, a zero gradient
+ *   row and reads nothing.
+ * lars_norms + lars_step (f32): the update of the reference's VMAE/util/lars.py.  lars_norms: norms [2] = (|p|, |g + wd p|) over n elements:
+ *   squares and sums in f64, one partial pair per 4096 elements in the workspace (lars_workspace_bytes(n) bytes, 8-byte aligned), then one
+ *   block adds the partials and stores the two square roots as f32.  lars_step: norms != NULL (a tensor of more than one dimension):
+ *   dp = (g + wd p) * q, q = trust |p| / |dp| where both norms are positive, else 1; norms == NULL (a bias): dp = g; then mu = momentum mu +
+ *   dp, p -= lr mu (each line one fma).  The step reads the norms from device memory: nothing comes back to the host.
+ * topk_merge: sims [M, Nc] (row stride ld) are the similarities of M queries to bank rows col0 .. col0 + Nc - 1; vals / idx [M, k] are the
+ *   running lists, sorted by value descending, then index ascending, empty slots (-inf, -1) last (the caller starts from all-empty
+ *   lists).  After the call they hold the best k of the old list and the chunk.  Comparisons only: exact, whatever the chunking.  A NaN
+ *   similarity is never taken.  k <= LDMAE_TOPK_MAX_K.
+ * knn_vote: per query, score[c] = sum over the list's neighbours j (in list order) with bank_labels[idx_j] == c of exp(vals_j /
+ *   temperature); rank [M] = the rank of qlabels[m] among the scores by softmax_xent's rule (ties to the lower class).  The scores of a query
+ *   are held in LDS: C <= LDMAE_KNN_VOTE_MAX_C.  Empty slots, indices outside [0, nbank) and bank labels outside [0, C) add nothing; a query
+ *   label outside [0, C) gives rank -1.  scores (optional) [M, C] receives the class scores. */
+#define LDMAE_TOPK_MAX_K 256
+#define LDMAE_KNN_VOTE_MAX_C 12288
+int ldmae_token_mean(int dtype, const void* x, long ldx, int col0, float* out, int B, int N, int D, void* stream);
+int ldmae_bn1d_fwd(int dtype, const void* x, int ldx, void* xhat, int ldo, float* run_mean, float* run_var, float* save_mean, float* save_rstd,
+                   int B, int D, float eps, float momentum, int training, void* stream);
+int ldmae_softmax_xent(int dtype, const void* logits, int ld, const long long* labels, float* loss, void* dlogits, int ldd, int* rank, int B,
+                       int C, float grad_scale, void* stream);
+long ldmae_lars_workspace_bytes(long n);
+int ldmae_lars_norms(int dtype, const void* p, const void* g, long n, float wd, void* workspace, float* norms, void* stream);
+int ldmae_lars_step(int dtype, void* p, const void* g, void* mu, long n, const float* norms, float lr, float wd, float momentum, float trust,
+                    void* stream);
+/* out [M, D] = x [M, D] / max(sqrtf(sqnorms[m]), 1e-12) (torch's F.normalize; sqnorms from ldmae_row_sqnorms_f32); out may be x. */
+int ldmae_l2_normalize(const float* x, const float* sqnorms, float* out, long M, int D, void* stream);
+int ldmae_topk_merge(const float* sims, int ld, int M, int Nc, int col0, float* vals, int* idx, int k, void* stream);
+int ldmae_knn_vote(const float* vals, const int* idx, int M, int k, const long long* bank_labels, int nbank, const long long* qlabels, int C,
+                   float temperature, int* rank, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,16 @@ def draw_table(sizes, input_size, scale, ratio, generator):
     return torch.tensor(rows, dtype=torch.int32).reshape(-1, 8)
 
 
+def center_table(sizes):
+    """The same table without a draw: the centre square of the short side (top = (h - s) // 2, left = (w - s) // 2, s = min(h, w)), no flip --
+    the evaluation transform of the linear probe (resized to the input size by the same kernel)."""
+    rows = []
+    for h, w in np.asarray(sizes).tolist():
+        s = min(h, w)
+        rows.append([h, w, (h - s) // 2, (w - s) // 2, s, s, 0, 0])
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 8)
+
+
 class _Slot:
     """One batch in flight: pinned staging + tables, their device copies, and the two events that guard their reuse.  Every DEVICE buffer is
     allocated with the loader's side stream current, so it comes from that stream's pool of the caching allocator: a block the training loop has
@@ -107,12 +117,14 @@ class _Slot:
 
 
 class PackedBatchLoader:
-    """Iterates (images [B, 3, S, S] on `device`, labels i64 [B] on the host) over `sampler`'s indices, always dropping the last partial batch.
+    """Iterates (images [B, 3, S, S] on `device`, labels i64 [B] on the host) over `sampler`'s indices, dropping the last partial batch unless
+    drop_last=False (then it is yielded with its own, smaller B).  center=True: no draw -- every sample is the centre square of its short side,
+    unflipped (center_table).
     The epoch is `sampler.epoch` (DistributedSampler.set_epoch) unless set_epoch() is called here; the rank is `sampler.rank` unless given.
     `last_table` describes the batch last yielded: {"index" i64 [B], "offset" i64 [B], "geom" i32 [B, 8], "epoch", "batch"} (host tensors)."""
 
     def __init__(self, dataset, sampler, batch_size, input_size, seed, device, scale=(0.75, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), prefetch=2,
-                 out_dtype=torch.float32, mean=0.5, std=0.5, rank=None):
+                 out_dtype=torch.float32, mean=0.5, std=0.5, rank=None, center=False, drop_last=True):
         self.dataset, self.sampler, self.batch_size, self.input_size, self.seed = dataset, sampler, int(batch_size), int(input_size), int(seed)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -122,13 +134,14 @@ class PackedBatchLoader:
         self.scale, self.ratio, self.prefetch, self.out_dtype, self.mean, self.std = scale, ratio, max(1, int(prefetch)), out_dtype, mean, std
         self.rank = int(rank if rank is not None else getattr(sampler, "rank", 0))
         self.epoch, self.last_table = None, None
+        self.center, self.drop_last = bool(center), bool(drop_last)
         self._side, self._slots, self._active = None, None, False        # made on the first iteration, kept for the loader's life
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
 
     def __len__(self):
-        return len(self.sampler) // self.batch_size
+        return len(self.sampler) // self.batch_size if self.drop_last else -(-len(self.sampler) // self.batch_size)
 
     # ---- producer: everything that needs no kernel, for batch k into slot k % prefetch
     def _fill(self, slot, idx, epoch, k):
@@ -144,13 +157,13 @@ class PackedBatchLoader:
         for b, i in enumerate(idx):
             stage[starts[b]:starts[b] + nbytes[b]] = ds.raw(int(i))
         g = torch.Generator().manual_seed(batch_seed(self.seed, self.rank, epoch, k))
-        geom = draw_table(ds.sizes[idx], self.input_size, self.scale, self.ratio, g)
+        geom = center_table(ds.sizes[idx]) if self.center else draw_table(ds.sizes[idx], self.input_size, self.scale, self.ratio, g)
         offsets = torch.from_numpy(starts)
         from ldmae_amd import ops
         ops.check_crop_table(offsets, geom, pos)              # the kernel trusts the device copy of these
-        slot.offsets_h.copy_(offsets)
-        slot.geom_h.copy_(geom)
-        slot.nbytes = pos
+        slot.offsets_h[:len(idx)].copy_(offsets)
+        slot.geom_h[:len(idx)].copy_(geom)
+        slot.nbytes, slot.rows = pos, len(idx)
         return {"index": torch.from_numpy(np.asarray(idx, dtype=np.int64)), "offset": offsets, "geom": geom, "epoch": epoch, "batch": k}
 
     def _produce(self, batches, epoch, free_q, ready_q, stop):
@@ -179,7 +192,7 @@ class PackedBatchLoader:
         from ldmae_amd import ops
         epoch = self.epoch if self.epoch is not None else int(getattr(self.sampler, "epoch", 0))
         order = np.fromiter(iter(self.sampler), dtype=np.int64)
-        nb = len(order) // self.batch_size
+        nb = len(order) // self.batch_size if self.drop_last else -(-len(order) // self.batch_size)
         batches = [order[k * self.batch_size:(k + 1) * self.batch_size] for k in range(nb)]
         if self._active:
             raise RuntimeError("PackedBatchLoader: one iteration at a time (the staging slots belong to the loader)")
@@ -203,7 +216,7 @@ class PackedBatchLoader:
                 with torch.cuda.device(self.device):
                     cur = torch.cuda.current_stream()
                     cur.wait_event(slot.uploaded)
-                    out = ops.crop_resize_flip(slot.blob[:slot.nbytes], slot.offsets_d, slot.geom_d, self.input_size, self.mean, self.std, self.out_dtype)
+                    out = ops.crop_resize_flip(slot.blob[:slot.nbytes], slot.offsets_d[:slot.rows], slot.geom_d[:slot.rows], self.input_size, self.mean, self.std, self.out_dtype)
                     slot.consumed.record(cur)
                     for t in (slot.blob, slot.offsets_d, slot.geom_d):      # side-stream memory read on this stream: should the loader be dropped with the
                         t.record_stream(cur)                                # kernel still queued, the allocator holds the blocks back until it has run

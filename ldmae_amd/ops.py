@@ -1299,6 +1299,184 @@ def kid_sums(a, b, idx_a, idx_b, gamma, coef0=1.0, nsplit=None):
     return out
 
 
+# ----------------------------------------------------------------------------- linear probe and k-NN (csrc/linprobe.hip), DESIGN.md section 23
+# The kernels work on the caller's tensors as they are (copy=False, out=True).  Label tables are HOST tables: check_labels checks and uploads them.
+TOPK_MAX_K = 256            # LDMAE_TOPK_MAX_K
+KNN_VOTE_MAX_C = 12288      # LDMAE_KNN_VOTE_MAX_C
+
+
+def check_labels(labels, num_classes, device, what="labels"):
+    """The range check the kernels leave to their caller, on the HOST copy of a label vector: [B] integers, every entry in [0, num_classes).
+    Returns the int64 device copy.  Raises ValueError naming the first bad entry."""
+    labels = torch.as_tensor(labels)
+    if labels.is_cuda:
+        raise ValueError(f"{what} are checked on their host copy; got a tensor on {labels.device}")
+    if labels.dim() != 1 or labels.numel() < 1 or labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what} must be a non-empty [B] int32 / int64 vector, got {tuple(labels.shape)} {labels.dtype}")
+    bad = (labels < 0) | (labels >= int(num_classes))
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0])
+        raise ValueError(f"{what}[{i}] = {int(labels[i])} is outside [0, {int(num_classes)})")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"ldmae_amd ops need tensors on a HIP device (no CPU fallback); got {device}")
+    return labels.to(device, torch.int64).contiguous()
+
+
+def _device_labels(labels, num_classes, like, n, what):
+    """Host labels: checked and uploaded; a device int64 vector is taken as one check_labels has returned."""
+    if not (torch.is_tensor(labels) and labels.is_cuda):
+        labels = check_labels(labels, num_classes, like.device, what)
+    return _arg(labels, what, torch.int64, (n,), copy=False, like=like)
+
+
+def token_mean(x, col0=0, d=None):
+    """x [B, N, W] f32 / bf16 / fp16, channels adjacent, token rows W' >= W apart (a channel slice of a wider buffer is read in place)
+    -> f32 [B, d]: the mean over the N tokens of channels [col0, col0 + d) (d None: all from col0).  Fixed summation order."""
+    if x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise RuntimeError(f"token_mean x: a [B, N, W] float32 / bfloat16 / float16 tensor expected, got {tuple(x.shape)} {x.dtype}")
+    B, N, W = x.shape
+    d = W - int(col0) if d is None else int(d)
+    if B < 1 or N < 1 or col0 < 0 or d < 1 or col0 + d > W:
+        raise RuntimeError(f"token_mean: channels [{col0}, {col0 + d}) of {tuple(x.shape)}")
+    ldx = x.stride(1) if N > 1 else (x.stride(0) if B > 1 else W)
+    if (W > 1 and x.stride(2) != 1) or ldx < W or (B > 1 and x.stride(0) != N * ldx):
+        raise RuntimeError(f"token_mean x: the kernel reads token rows with adjacent channels at one row stride; got strides {tuple(x.stride())} "
+                           f"for shape {tuple(x.shape)}")
+    out = torch.empty(B, d, dtype=torch.float32, device=x.device)
+    call("ldmae_token_mean", dt(x.dtype), ptr(x), ldx, int(col0), ptr(out), B, N, d, stream())
+    return out
+
+
+def bn1d_fwd(x, run_mean, run_var, training=True, eps=1e-6, momentum=0.1, out=None, save=False):
+    """BatchNorm1d(affine=False) of x [B, D] f32 (rows may be strided) -> xhat [B, D].  training: batch statistics (two-pass biased variance),
+    run_mean / run_var [D] updated IN PLACE (momentum, unbiased variance); B = 1 is refused.  Not training: normalises with the running
+    statistics.  save=True (training): also returns (mean, rstd)."""
+    _arg(x, "bn1d_fwd x", torch.float32, ("B", "D"), rows=True, copy=False)
+    B, D = x.shape
+    if training and B < 2:
+        raise ValueError(f"bn1d_fwd: Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    _arg(run_mean, "bn1d_fwd run_mean", torch.float32, (D,), out=True, like=x)
+    _arg(run_var, "bn1d_fwd run_var", torch.float32, (D,), out=True, like=x)
+    if out is None:
+        out = torch.empty(B, D, dtype=torch.float32, device=x.device)
+    else:
+        _arg(out, "bn1d_fwd out", torch.float32, (B, D), rows=True, out=True, like=x)
+    sm = torch.empty(D, dtype=torch.float32, device=x.device) if save and training else None
+    sr = torch.empty(D, dtype=torch.float32, device=x.device) if save and training else None
+    call("ldmae_bn1d_fwd", F32, ptr(x), _ld(x), ptr(out), _ld(out), ptr(run_mean), ptr(run_var), ptr(sm), ptr(sr), B, D, float(eps), float(momentum),
+         1 if training else 0, stream())
+    return (out, sm, sr) if save and training else out
+
+
+def softmax_xent(logits, labels, num_classes=None, grad_scale=None, dlogits=None):
+    """logits [B, W] f32 (rows may be strided; the first num_classes columns count, default all), labels [B]: a HOST vector (checked against
+    [0, C) and uploaded here) or the device vector check_labels returned -> (loss [B] f32, rank [B] i32, dlogits or None).  grad_scale given:
+    dlogits [B, C] = (softmax - onehot) * grad_scale, written into `dlogits` if passed (rows may be strided; columns beyond C untouched).
+    rank = #{c : l[c] > l[y]} + #{c < y : l[c] == l[y]}: top-1 is rank == 0, top-5 rank < 5."""
+    _arg(logits, "softmax_xent logits", torch.float32, ("B", "W"), rows=True, copy=False)
+    B, W = logits.shape
+    C = W if num_classes is None else int(num_classes)
+    if not 1 <= C <= W:
+        raise RuntimeError(f"softmax_xent: {C} classes in rows of {W} logits")
+    labels = _device_labels(labels, C, logits, B, "softmax_xent labels")
+    if grad_scale is None:
+        if dlogits is not None:
+            raise RuntimeError("softmax_xent: dlogits needs grad_scale")
+    elif dlogits is None:
+        dlogits = torch.empty(B, C, dtype=torch.float32, device=logits.device)
+    else:
+        _arg(dlogits, "softmax_xent dlogits", torch.float32, (B, "W >= C"), rows=True, out=True, like=logits)
+        if dlogits.shape[1] < C:
+            raise RuntimeError(f"softmax_xent dlogits: {dlogits.shape[1]} columns for {C} classes")
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    rank = torch.empty(B, dtype=torch.int32, device=logits.device)
+    call("ldmae_softmax_xent", F32, ptr(logits), _ld(logits), ptr(labels), ptr(loss), ptr(dlogits), 0 if dlogits is None else max(_ld(dlogits), C),
+         ptr(rank), B, C, float(grad_scale or 0.0), stream())
+    return loss, rank, dlogits
+
+
+def lars_norms(p, g, weight_decay=0.0, out=None):
+    """(|p|, |g + wd p|) of two f32 tensors of one size -> f32 [2] on the device (two-stage fixed-order reduction, sums in f64)."""
+    _arg(p, "lars_norms p", torch.float32, copy=False)
+    _arg(g, "lars_norms g", torch.float32, numel=p.numel(), copy=False, like=p)
+    if p.numel() < 1:
+        raise RuntimeError("lars_norms: empty tensor")
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=p.device)
+    else:
+        _arg(out, "lars_norms out", torch.float32, (2,), out=True, like=p)
+    nbytes = L.load().ldmae_lars_workspace_bytes(p.numel())
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=p.device)
+    call("ldmae_lars_norms", F32, ptr(p), ptr(g), p.numel(), float(weight_decay), ptr(ws), ptr(out), stream())
+    return out
+
+
+def lars_step(p, g, mu, lr, norms=None, weight_decay=0.0, momentum=0.9, trust=0.001):
+    """One LARS update of p and mu IN PLACE (the reference's util/lars.py).  norms (f32 [2] from lars_norms, read on the device): the tensor has
+    more than one dimension -- dp = (g + wd p) * q, q = trust |p| / |dp| where both are positive, else 1.  norms None: a bias -- dp = g.
+    Then mu = momentum mu + dp, p -= lr mu."""
+    _arg(p, "lars_step p", torch.float32, out=True)
+    _arg(g, "lars_step g", torch.float32, numel=p.numel(), copy=False, like=p)
+    _arg(mu, "lars_step mu", torch.float32, numel=p.numel(), out=True, like=p)
+    _arg(norms, "lars_step norms", torch.float32, (2,), copy=False, like=p)
+    if p.numel() < 1:
+        raise RuntimeError("lars_step: empty tensor")
+    call("ldmae_lars_step", F32, ptr(p), ptr(g), ptr(mu), p.numel(), ptr(norms), float(lr), float(weight_decay), float(momentum), float(trust), stream())
+    return p
+
+
+def l2_normalize(x):
+    """f32 [M, D] -> x / max(|x_m|, 1e-12) row by row (F.normalize): row_sqnorms, then one scaling pass."""
+    _arg(x, "l2_normalize x", torch.float32, ("M", "D"), copy=False)
+    out = torch.empty_like(x)
+    call("ldmae_l2_normalize", ptr(x), ptr(row_sqnorms(x)), ptr(out), x.shape[0], x.shape[1], stream())
+    return out
+
+
+def topk_empty(m, k, device):
+    """All-empty running lists of topk_merge: (values [m, k] = -inf, indices [m, k] = -1)."""
+    if not 1 <= int(k) <= TOPK_MAX_K:
+        raise ValueError(f"topk: k = {k} neighbours; the merge kernel keeps 1 .. {TOPK_MAX_K}")
+    return (torch.full((m, k), float("-inf"), dtype=torch.float32, device=device), torch.full((m, k), -1, dtype=torch.int32, device=device))
+
+
+def topk_merge(sims, col0, vals, idx):
+    """Merge the chunk sims [M, Nc] f32 (rows may be strided; column j is bank row col0 + j) into the running lists vals / idx [M, k] IN PLACE:
+    sorted by value descending, then index ascending, empty slots (-inf, -1) last.  Exact: comparisons only."""
+    _arg(sims, "topk_merge sims", torch.float32, ("M", "Nc"), rows=True, copy=False)
+    M, Nc = sims.shape
+    _arg(vals, "topk_merge vals", torch.float32, (M, "k"), out=True, like=sims)
+    k = vals.shape[1]
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"topk_merge: k = {k} neighbours; the kernel keeps 1 .. {TOPK_MAX_K}")
+    _arg(idx, "topk_merge idx", torch.int32, (M, k), out=True, like=sims)
+    if col0 < 0 or col0 + Nc >= 2 ** 31:
+        raise RuntimeError(f"topk_merge: bank rows [{col0}, {col0 + Nc}) leave the int32 index range")
+    call("ldmae_topk_merge", ptr(sims), _ld(sims), M, Nc, int(col0), ptr(vals), ptr(idx), k, stream())
+    return vals, idx
+
+
+def knn_vote(vals, idx, bank_labels, query_labels, num_classes, temperature=0.07, return_scores=False):
+    """The weighted k-NN vote (DINO's protocol): score[c] = sum of exp(sim / T) over the neighbours of class c, in list order -> rank [M] i32 of
+    the query's own class (softmax_xent's rule, ties to the lower class).  vals / idx [M, k] from topk_merge; the label vectors are HOST
+    vectors (checked here) or what check_labels returned.  return_scores: also the f32 [M, C] scores."""
+    _arg(vals, "knn_vote vals", torch.float32, ("M", "k"), copy=False)
+    M, k = vals.shape
+    _arg(idx, "knn_vote idx", torch.int32, (M, k), copy=False, like=vals)
+    C = int(num_classes)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"knn_vote: k = {k} neighbours; the kernel takes 1 .. {TOPK_MAX_K}")
+    if not 1 <= C <= KNN_VOTE_MAX_C:
+        raise ValueError(f"knn_vote: {C} classes; the scores of a query are held in LDS, KNN_VOTE_MAX_C = {KNN_VOTE_MAX_C} fit")
+    nbank = int(torch.as_tensor(bank_labels).numel())
+    bank_labels = _device_labels(bank_labels, C, vals, nbank, "knn_vote bank_labels")
+    query_labels = _device_labels(query_labels, C, vals, M, "knn_vote query_labels")
+    rank = torch.empty(M, dtype=torch.int32, device=vals.device)
+    scores = torch.empty(M, C, dtype=torch.float32, device=vals.device) if return_scores else None
+    call("ldmae_knn_vote", ptr(vals), ptr(idx), M, k, ptr(bank_labels), nbank, ptr(query_labels), C, float(temperature), ptr(rank), ptr(scores), stream())
+    return (rank, scores) if return_scores else rank
+
+
 # ----------------------------------------------------------------------------- FID evaluation (csrc/inception.hip), NHWC f32
 # A channel slice is (tensor [B, H, W, Ctot], offset, C): the kernels read / write channels [offset, offset + C) of every pixel.
 # From here to the end of the file the kernels work on the caller's tensors as they are: every _arg below says copy=False, or out=True for an output.

@@ -676,7 +676,9 @@ class MaskedAutoencoderViT(nn.Module):
         return loss, pred, mask, vis_loss, mask_loss, kl_loss
 
     # ---- docking functions (:817-973)
-    def _encode(self, x):
+    def _encode_tokens(self, x, to_latent=True):
+        """Images -> the encoder's tokens after the closing LayerNorm [B, N, embed_dim], or (to_latent) the `to_latent` output [B, N, (2) latent]:
+        the one docking path of _encode and encode_features."""
         dtype, tf32 = self._docking_dtype(self.blocks, rows=x.shape[0] * self.patch_embed.num_patches)
         with torch.autocast(device_type="cuda", enabled=False):
             x = self._embed(x, dtype)
@@ -688,9 +690,24 @@ class MaskedAutoencoderViT(nn.Module):
             else:
                 x = self._run(self.blocks, x, dtype, tf32)
                 x = _LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps)
-            x = _latent_map(self.to_latent, x)
+            if to_latent:
+                x = _latent_map(self.to_latent, x)
+        return x
+
+    def _encode(self, x):
+        x = self._encode_tokens(x)
         g = self.latent_resolution
         return x.reshape(x.shape[0], g, g, -1).permute(0, 3, 1, 2)
+
+    def encode_features(self, x, which="latent"):
+        """Frozen-encoder features for the linear probe and the k-NN classifier (ldmae_amd/linear_probe.py), under no_grad on _encode's path:
+        "encoder": the tokens after the closing LayerNorm [B, N, embed_dim]; "latent": the posterior mean = the first latent_dim channels of
+        the `to_latent` output, token-major [B, N, latent_dim] (a channel slice of it: what the DiT is trained on, before normalisation)."""
+        if which not in ("encoder", "latent"):
+            raise ValueError(f"encode_features: which = {which!r} (encoder or latent)")
+        with torch.no_grad():
+            t = self._encode_tokens(x, to_latent=which == "latent")
+        return t[..., :self.latent_dim] if which == "latent" else t
 
     def encode(self, x, return_dict=True):
         m = self._encode(x)
