@@ -67,6 +67,7 @@ template <> __device__ __forceinline__ f16 from_f<f16>(float v) { return (f16)v;
 // forward outputs of the fp16 GEMM epilogues SATURATE instead (mx = 65504; mx = infinity: no-op, the gradient GEMMs); NaN kept
 __device__ __forceinline__ float sat_f16(float v, float mx) { return v == v ? __builtin_amdgcn_fmed3f(v, -mx, mx) : v; }
 __device__ __forceinline__ float4 sat_f16(float4 v, float mx) { return make_float4(sat_f16(v.x, mx), sat_f16(v.y, mx), sat_f16(v.z, mx), sat_f16(v.w, mx)); }
+__device__ __forceinline__ f16 to_f16_sat(float v) { return (f16)sat_f16(v, 65504.f); }      // one rounding, round to nearest even
 // 8- / 4-element register vectors of a 2-byte activation type
 template <typename T> struct Pack;
 template <> struct Pack<bf16> { typedef bf16x8 v8; typedef bf16x4 v4; };
@@ -164,6 +165,13 @@ __device__ __forceinline__ float wave_max(float v) {
 template <int W> __device__ __forceinline__ float group_sum(float v) {
 #pragma unroll
   for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum over the aligned group of L lanes (a power of two <= 64) this lane is in, nearest partner first: the LPIPS heads, forward and backward
+template <int L> __device__ __forceinline__ float lane_group_sum(float v) {
+#pragma unroll
+  for (int o = 1; o < L; o <<= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 

@@ -9,9 +9,10 @@
 // The element type T and with it the MFMA are template parameters, deduced from the LDS arrays: f16 (the default everywhere above) or bf16
 // (v_mfma_f32_16x16x32_bf16: the LPIPS data gradient of lpips_f16.hip, whose operands need f32's exponent range).
 #pragma once
-#include "common.h"
+#include "conv_igemm_common.h"
 
 constexpr int CH_BM = 128, CH_BN = 128, CH_BK = 32, CH_LD = 48, CH_NT = 256;
+typedef ConvTile<CH_BM, CH_BN, 8> ChTile;
 
 template <class T> struct ConvMfma16;
 template <> struct ConvMfma16<f16> {

@@ -4,9 +4,10 @@
 // so each lane fetches its four A (B) values of a step with ONE ds_read_b128 instead of four ds_read_b32.  The sum is over the same products,
 // in a different order (f32 rounding only).  Row stride 20 floats: the eight 16-B reads of a ds_read_b128 phase hit disjoint banks.
 #pragma once
-#include "common.h"
+#include "conv_igemm_common.h"
 
 constexpr int CV_BM = 128, CV_BN = 64, CV_BK = 16, CV_LD = 20, CV_NT = 256;
+typedef ConvTile<CV_BM, CV_BN, 4> CvTile;
 
 // Staging: thread tid owns k-columns [lc, lc + 4) of A rows lr and lr + 64 and of B row lr (lr = tid >> 2, lc = (tid & 3) * 4).
 // fetch_a(p, k0) -> the float4 of A row lr + 64 p at K-step k0; fetch_b(k0) -> the float4 of B row lr; advance() moves the caller's (tap,

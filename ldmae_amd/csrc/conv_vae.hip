@@ -132,26 +132,19 @@ __global__ __launch_bounds__(CV_NT) void conv_vae_kernel(const float* __restrict
                                                          VaeGeom g) {
   __shared__ __attribute__((aligned(16))) float As[2][CV_BM * CV_LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][CV_BN * CV_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (g.Cout + CV_BN - 1) / CV_BN;
-  const int m0 = (int)(blockIdx.x / tiles_n) * CV_BM, n0 = (int)(blockIdx.x % tiles_n) * CV_BN;
-  const int lr = tid >> 2, lc = (tid & 3) * 4;
-  int iy0[2], ix0[2], sb[2];
+  const CvTile t(g.Cout);
+  ConvRow row[2];
+  int sb[2];
   const float* xb[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
-    const int ox = m % g.Wo, t = m / g.Wo, oy = t % g.Ho, b = t / g.Ho;
-    iy0[p] = oy * g.stride - g.pad;
-    ix0[p] = ox * g.stride - g.pad;
-    xb[p] = x + (size_t)b * g.H * g.W * g.Cin;
-    sb[p] = b * g.G;
+    row[p] = conv_row(t, p, g.M, g.Ho, g.Wo, g.stride, g.stride, g.pad, g.pad);
+    xb[p] = x + (size_t)row[p].b * g.H * g.W * g.Cin;
+    sb[p] = row[p].b * g.G;
   }
-  const float* wrow = w + (size_t)min(n0 + lr, g.Cout - 1) * g.K;
-  // (tap, channel) of this thread's first k, advanced by BK per step without divisions; Cin % 4 == 0, so a float4 never straddles taps
-  int ci = lc, kx = 0, ky = 0;
-  while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+  const float* wrow = conv_weight_row(w, t.n0 + t.lr, g.Cout, g.K);
+  int ci = t.lc, kx = 0, ky = 0;                   // Cin % 4 == 0, so a float4 never straddles taps
+  TAP_WRAP(ci, kx, ky, g.Cin, g.ks)
   // norm-act: gamma / beta of the four channels and their group, the same for both A rows of a step
   float4 ga = make_float4(0.f, 0.f, 0.f, 0.f), be = ga;
   int gi[4] = {0, 0, 0, 0};
@@ -169,7 +162,7 @@ __global__ __launch_bounds__(CV_NT) void conv_vae_kernel(const float* __restrict
   };
   coef();
   auto fetch_a = [&](int p, int) -> float4 {
-    const int iy = iy0[p] + ky, ix = ix0[p] + kx;
+    const int iy = row[p].iy0 + ky, ix = row[p].ix0 + kx;
     if (ky < g.ks && (unsigned)iy < (unsigned)g.Hv && (unsigned)ix < (unsigned)g.Wv) {
       float4 v = *(const float4*)(xb[p] + ((size_t)(iy >> g.up) * g.W + (ix >> g.up)) * g.Cin + ci);
       if (NORM == 1) {
@@ -186,99 +179,102 @@ __global__ __launch_bounds__(CV_NT) void conv_vae_kernel(const float* __restrict
     }
     return make_float4(0.f, 0.f, 0.f, 0.f);
   };
-  auto fetch_b = [&](int k0) -> float4 {
-    const int k = k0 + lc;                                 // K % 4 == 0
-    if (k < g.K) return *(const float4*)(wrow + k);
-    return make_float4(0.f, 0.f, 0.f, 0.f);
-  };
+  auto fetch_b = [&](int k0) { return fetch_weight_row<float4>(wrow, k0 + t.lc, g.K); };
   auto advance = [&]() {
     ci += CV_BK;
-    while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+    TAP_WRAP(ci, kx, ky, g.Cin, g.ks)
     coef();
   };
 
   f32x4 acc[4][2];
   conv_igemm_f32_mainloop(As, Bs, (g.K + CV_BK - 1) / CV_BK, fetch_a, fetch_b, advance, acc);
-  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-  // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block; out = acc + bias + res
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn * 32 + j * 16 + r16;
-    if (n >= g.Cout) continue;
-    const float bn = bias ? bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + i * 16 + q4 + r;
-        if (m < g.M) {
-          float v = acc[i][j][r] + bn;
-          if (res) v += res[(size_t)m * g.Cout + n];
-          out[(size_t)m * g.Cout + n] = v;
-        }
-      }
-  }
+  CONV_EPILOGUE(acc, 2, t, g.M, g.Cout, conv_bias(bias), [&](int m, int n, float a, float bn) {
+    float v = a + bn;                                      // out = acc + bias + res
+    if (res) v += res[(size_t)m * g.Cout + n];
+    out[(size_t)m * g.Cout + n] = v;
+  });
 }
 
+// (norm, silu) -> instantiation; a norm code without a kernel is refused, never mapped to another one
 static int launch_conv_vae(const char* name, int norm, int silu, const float* x, const float* w, const float* bias, const float* res, const float* mean,
                            const float* rstd, const float* gamma, const float* beta, float* out, const VaeGeom& g, void* stream) {
-  const unsigned grid = cdiv(g.M, CV_BM) * cdiv(g.Cout, CV_BN);
-  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * g.M * g.Cout * g.K) : -1;
 #define LDMAE_VAE_LAUNCH(NORM, SILU) \
-  hipLaunchKernelGGL((conv_vae_kernel<NORM, SILU>), dim3(grid), dim3(CV_NT), 0, as_stream(stream), x, w, bias, res, mean, rstd, gamma, beta, out, g)
+  return conv_launch<CV_BM, CV_BN, CV_NT>(name, conv_vae_kernel<NORM, SILU>, g.M, g.Cout, g.K, stream, x, w, bias, res, mean, rstd, gamma, beta, out, g)
   if (norm == 0) LDMAE_VAE_LAUNCH(0, false);
-  else if (norm == 1 && silu) LDMAE_VAE_LAUNCH(1, true);
-  else if (norm == 1) LDMAE_VAE_LAUNCH(1, false);
-  else if (silu) LDMAE_VAE_LAUNCH(2, true);
-  else LDMAE_VAE_LAUNCH(2, false);
+  if (norm == 1 && silu) LDMAE_VAE_LAUNCH(1, true);
+  if (norm == 1) LDMAE_VAE_LAUNCH(1, false);
+  if (norm == 2 && silu) LDMAE_VAE_LAUNCH(2, true);
+  if (norm == 2) LDMAE_VAE_LAUNCH(2, false);
 #undef LDMAE_VAE_LAUNCH
-  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
-  LDMAE_CHECK_LAUNCH(name);
+  LDMAE_FAIL(LDMAE_ERR_INVALID, "%s: no kernel for norm code %d", name, norm);
+}
+
+// What the two precisions of an entry point differ in besides its name: the channel multiple of a 16-byte fragment, the tile, and the row
+// limit (the fp16 entries keep one tile of headroom below 2^31).
+struct VaeLimits { int mult, bm, bn; long m_max; };
+constexpr VaeLimits VAE_F32{4, CV_BM, CV_BN, 1L << 31}, VAE_F16{8, CH_BM, CH_BN, (1L << 31) - CH_BM};
+
+// The argument checks of conv3x3_vae_nhwc_* after the mode's, and the mode's geometry.
+static int vae_geom_3x3(const char* name, const VaeLimits& lim, int mode, const void* x, const void* w, const void* out, const float* mean,
+                        const float* rstd, const float* gamma, const float* beta, int G, int B, int H, int W, int Cin, int Cout, VaeGeom& g) {
+  LDMAE_REQUIRE(x && w && out, "%s: null pointer (only bias and res may be NULL)", name);
+  LDMAE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "%s: B=%d H=%d W=%d Cin=%d Cout=%d must be positive", name, B, H, W, Cin, Cout);
+  LDMAE_REQUIRE(Cin % lim.mult == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "%s: Cin=%d must be a multiple of %d and x, w 16-B aligned", name,
+                Cin, lim.mult);
+  g = VaeGeom{};
+  g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.ks = 3;
+  g.Hv = H; g.Wv = W; g.up = 0; g.stride = 1; g.pad = 1; g.Ho = H; g.Wo = W; g.G = 1; g.cpg = Cin;
+  if (mode == LDMAE_VAE_NORM_ACT) {
+    LDMAE_REQUIRE(mean && rstd && gamma && beta && G > 0, "%s: norm-act needs mean, rstd, gamma, beta and a positive group count", name);
+    LDMAE_REQUIRE(Cin % G == 0, "%s: %d channels are not divisible into %d groups", name, Cin, G);
+    LDMAE_REQUIRE(((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0, "%s: gamma and beta must be 16-B aligned", name);
+    g.G = G; g.cpg = Cin / G;
+  } else if (mode == LDMAE_VAE_DOWN) {
+    LDMAE_REQUIRE(H >= 2 && W >= 2, "%s: down needs at least 2 x 2 pixels", name);
+    g.stride = 2; g.pad = 0; g.Ho = (H + 1 - 3) / 2 + 1; g.Wo = (W + 1 - 3) / 2 + 1;      // pad (0, 1, 0, 1): right and bottom only
+  } else if (mode == LDMAE_VAE_UP) {
+    g.up = 1; g.Hv = 2 * H; g.Wv = 2 * W; g.Ho = 2 * H; g.Wo = 2 * W;
+  }
+  const long M = (long)B * g.Ho * g.Wo, K = 9L * Cin;
+  LDMAE_REQUIRE(M < lim.m_max && M * Cout < (1L << 40) && (long)B * H * W * Cin < (1L << 40) && K < (1L << 24) &&
+                    (long)cdiv(M, lim.bm) * cdiv(Cout, lim.bn) < (1L << 31),
+                "%s: problem too large", name);
+  g.M = (int)M; g.K = (int)K;
+  return 0;
+}
+
+// The same for conv1x1_res_nhwc_*: M pixels of one row, so no tap ever leaves the frame.
+static int vae_geom_1x1(const char* name, const VaeLimits& lim, const void* x, const void* w, const void* out, int M, int Cin, int Cout, VaeGeom& g) {
+  LDMAE_REQUIRE(x && w && out, "%s: null pointer (only bias and res may be NULL)", name);
+  LDMAE_REQUIRE(M > 0 && Cin > 0 && Cout > 0, "%s: M=%d Cin=%d Cout=%d must be positive", name, M, Cin, Cout);
+  LDMAE_REQUIRE(Cin % lim.mult == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "%s: Cin=%d must be a multiple of %d and x, w 16-B aligned", name,
+                Cin, lim.mult);
+  LDMAE_REQUIRE((long)M < lim.m_max && (long)M * Cout < (1L << 40) && (long)M * Cin < (1L << 40) && Cin < (1 << 24) &&
+                    (long)cdiv(M, lim.bm) * cdiv(Cout, lim.bn) < (1L << 31),
+                "%s: problem too large", name);
+  g = VaeGeom{};
+  g.B = 1; g.H = 1; g.W = M; g.Cin = Cin; g.Cout = Cout; g.ks = 1;
+  g.Hv = 1; g.Wv = M; g.up = 0; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = M; g.G = 1; g.cpg = Cin;
+  g.M = M; g.K = Cin;
   return 0;
 }
 
 extern "C" int ldmae_conv3x3_vae_nhwc_f32(int mode, const float* x, const float* w, const float* bias, const float* res, const float* mean,
                                           const float* rstd, const float* gamma, const float* beta, int G, int silu, float* out, int B, int H, int W,
                                           int Cin, int Cout, void* stream) {
+  const char* name = "conv3x3_vae_nhwc_f32";
   LDMAE_REQUIRE(mode == LDMAE_VAE_PLAIN || mode == LDMAE_VAE_NORM_ACT || mode == LDMAE_VAE_DOWN || mode == LDMAE_VAE_UP,
-                "conv3x3_vae_nhwc_f32: mode %d (0 plain, 1 norm-act, 2 down, 3 up)", mode);
-  LDMAE_REQUIRE(x && w && out, "conv3x3_vae_nhwc_f32: null pointer (only bias and res may be NULL)");
-  LDMAE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_vae_nhwc_f32: B=%d H=%d W=%d Cin=%d Cout=%d must be positive", B, H, W, Cin, Cout);
-  LDMAE_REQUIRE(Cin % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv3x3_vae_nhwc_f32: Cin=%d must be a multiple of 4 and x, w 16-B aligned",
-                Cin);
-  VaeGeom g{};
-  g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.ks = 3;
-  g.Hv = H; g.Wv = W; g.up = 0; g.stride = 1; g.pad = 1; g.Ho = H; g.Wo = W; g.G = 1; g.cpg = Cin;
-  int norm = 0;
-  if (mode == LDMAE_VAE_NORM_ACT) {
-    LDMAE_REQUIRE(mean && rstd && gamma && beta && G > 0, "conv3x3_vae_nhwc_f32: norm-act needs mean, rstd, gamma, beta and a positive group count");
-    LDMAE_REQUIRE(Cin % G == 0, "conv3x3_vae_nhwc_f32: %d channels are not divisible into %d groups", Cin, G);
-    LDMAE_REQUIRE(((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0, "conv3x3_vae_nhwc_f32: gamma and beta must be 16-B aligned");
-    g.G = G; g.cpg = Cin / G;
-    norm = g.cpg % 4 == 0 ? 1 : 2;
-  } else if (mode == LDMAE_VAE_DOWN) {
-    LDMAE_REQUIRE(H >= 2 && W >= 2, "conv3x3_vae_nhwc_f32: down needs at least 2 x 2 pixels");
-    g.stride = 2; g.pad = 0; g.Ho = (H + 1 - 3) / 2 + 1; g.Wo = (W + 1 - 3) / 2 + 1;      // pad (0, 1, 0, 1): right and bottom only
-  } else if (mode == LDMAE_VAE_UP) {
-    g.up = 1; g.Hv = 2 * H; g.Wv = 2 * W; g.Ho = 2 * H; g.Wo = 2 * W;
-  }
-  const long M = (long)B * g.Ho * g.Wo, K = 9L * Cin;
-  LDMAE_REQUIRE(M < (1L << 31) && M * Cout < (1L << 40) && (long)B * H * W * Cin < (1L << 40) && K < (1L << 24), "conv3x3_vae_nhwc_f32: problem too large");
-  g.M = (int)M; g.K = (int)K;
-  return launch_conv_vae("conv3x3_vae_nhwc_f32", norm, silu, x, w, bias, res, mean, rstd, gamma, beta, out, g, stream);
+                "%s: mode %d (0 plain, 1 norm-act, 2 down, 3 up)", name, mode);
+  VaeGeom g;
+  if (const int rc = vae_geom_3x3(name, VAE_F32, mode, x, w, out, mean, rstd, gamma, beta, G, B, H, W, Cin, Cout, g)) return rc;
+  const int norm = mode != LDMAE_VAE_NORM_ACT ? 0 : g.cpg % 4 == 0 ? 1 : 2;
+  return launch_conv_vae(name, norm, silu, x, w, bias, res, mean, rstd, gamma, beta, out, g, stream);
 }
 
 extern "C" int ldmae_conv1x1_res_nhwc_f32(const float* x, const float* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout,
                                           void* stream) {
-  LDMAE_REQUIRE(x && w && out, "conv1x1_res_nhwc_f32: null pointer (only bias and res may be NULL)");
-  LDMAE_REQUIRE(M > 0 && Cin > 0 && Cout > 0, "conv1x1_res_nhwc_f32: M=%d Cin=%d Cout=%d must be positive", M, Cin, Cout);
-  LDMAE_REQUIRE(Cin % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv1x1_res_nhwc_f32: Cin=%d must be a multiple of 4 and x, w 16-B aligned",
-                Cin);
-  LDMAE_REQUIRE((long)M * Cout < (1L << 40) && (long)M * Cin < (1L << 40) && Cin < (1 << 24), "conv1x1_res_nhwc_f32: problem too large");
-  VaeGeom g{};
-  g.B = 1; g.H = 1; g.W = M; g.Cin = Cin; g.Cout = Cout; g.ks = 1;                          // M pixels of one row: no tap ever leaves the frame
-  g.Hv = 1; g.Wv = M; g.up = 0; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = M; g.G = 1; g.cpg = Cin;
-  g.M = M; g.K = Cin;
+  VaeGeom g;
+  if (const int rc = vae_geom_1x1("conv1x1_res_nhwc_f32", VAE_F32, x, w, out, M, Cin, Cout, g)) return rc;
   return launch_conv_vae("conv1x1_res_nhwc_f32", 0, 0, x, w, bias, res, nullptr, nullptr, nullptr, nullptr, out, g, stream);
 }
 
@@ -288,8 +284,6 @@ extern "C" int ldmae_conv1x1_res_nhwc_f32(const float* x, const float* w, const 
 // operand is fp16(gn_act(x)): normalise and SiLU in f32 by the definition above, then one rounding; a tap outside the frame is exactly 0
 // and bypasses the activation.  The weight comes packed as fp16 [Cout, ks, ks, Cin]; Cin % 8 == 0, so a 16-B fp16 fragment never
 // straddles a tap.  XF16: the input tensor is already fp16 (what groupnorm_apply_nhwc_f16out wrote: the two-pass form), plain gather only.
-__device__ __forceinline__ f16 to_f16_sat(float v) { return (f16)sat_f16(v, 65504.f); }
-
 // NORM 0: raw operand; 1: norm-act, cpg % 8 == 0 (the eight channels of a fragment share a group); 2: cpg % 4 == 0 (each half of a fragment
 // has its own group); 3: norm-act, any cpg.
 template <int NORM, bool SILU, bool XF16>
@@ -299,27 +293,20 @@ __global__ __launch_bounds__(CH_NT) void conv_vae_f16_kernel(const void* __restr
                                                              const float* __restrict__ beta, float* __restrict__ out, VaeGeom g) {
   __shared__ __attribute__((aligned(16))) f16 As[2][CH_BM * CH_LD];
   __shared__ __attribute__((aligned(16))) f16 Bs[2][CH_BN * CH_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (g.Cout + CH_BN - 1) / CH_BN;
-  const int m0 = (int)(blockIdx.x / tiles_n) * CH_BM, n0 = (int)(blockIdx.x % tiles_n) * CH_BN;
-  const int lr = tid >> 2, lc = (tid & 3) * 8;
-  int iy0[2], ix0[2], sb[2];
+  const ChTile t(g.Cout);
+  ConvRow row[2];
+  int sb[2];
   size_t xb[2];
   const f16* wrow[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
-    const int ox = m % g.Wo, t = m / g.Wo, oy = t % g.Ho, b = t / g.Ho;
-    iy0[p] = oy * g.stride - g.pad;
-    ix0[p] = ox * g.stride - g.pad;
-    xb[p] = (size_t)b * g.H * g.W * g.Cin;
-    sb[p] = b * g.G;
-    wrow[p] = w + (size_t)min(n0 + lr + p * 64, g.Cout - 1) * g.K;      // rows past Cout fetch the last filter; never stored
+    row[p] = conv_row(t, p, g.M, g.Ho, g.Wo, g.stride, g.stride, g.pad, g.pad);
+    xb[p] = (size_t)row[p].b * g.H * g.W * g.Cin;
+    sb[p] = row[p].b * g.G;
+    wrow[p] = conv_weight_row(w, t.n0 + t.lr + p * 64, g.Cout, g.K);
   }
-  // (tap, channel) of this thread's first k, advanced by BK per step without divisions; a BK step may span several taps (Cin < BK)
-  int ci = lc, kx = 0, ky = 0;
-  while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+  int ci = t.lc, kx = 0, ky = 0;
+  TAP_WRAP(ci, kx, ky, g.Cin, g.ks)
   // norm-act: gamma / beta of the eight channels and their groups, the same for both A rows of a step
   float ga[8], be[8];
   int gi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -342,7 +329,7 @@ __global__ __launch_bounds__(CH_NT) void conv_vae_f16_kernel(const void* __restr
   };
   coef();
   auto fetch_a = [&](int p) -> f16x8 {
-    const int iy = iy0[p] + ky, ix = ix0[p] + kx;
+    const int iy = row[p].iy0 + ky, ix = row[p].ix0 + kx;
     f16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
     if (ky < g.ks && (unsigned)iy < (unsigned)g.Hv && (unsigned)ix < (unsigned)g.Wv) {
       const size_t off = xb[p] + ((size_t)(iy >> g.up) * g.W + (ix >> g.up)) * g.Cin + ci;
@@ -366,109 +353,59 @@ __global__ __launch_bounds__(CH_NT) void conv_vae_f16_kernel(const void* __restr
     }
     return r;
   };
-  auto fetch_b = [&](int p, int k0) -> f16x8 {
-    const int k = k0 + lc;                                 // K % 8 == 0
-    if (k < g.K) return *(const f16x8*)(wrow[p] + k);
-    return (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-  };
+  auto fetch_b = [&](int p, int k0) { return fetch_weight_row<f16x8>(wrow[p], k0 + t.lc, g.K); };
   auto advance = [&]() {
     ci += CH_BK;
-    while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.ks) { kx = 0; ++ky; } }
+    TAP_WRAP(ci, kx, ky, g.Cin, g.ks)
     coef();
   };
 
   f32x4 acc[4][4];
   conv_igemm_f16_mainloop(As, Bs, (g.K + CH_BK - 1) / CH_BK, fetch_a, fetch_b, advance, acc);
-  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-  // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block; out = acc + bias + res
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + wn * 64 + j * 16 + r16;
-    if (n >= g.Cout) continue;
-    const float bn = bias ? bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + i * 16 + q4 + r;
-        if (m < g.M) {
-          float v = acc[i][j][r] + bn;
-          if (res) v += res[(size_t)m * g.Cout + n];
-          out[(size_t)m * g.Cout + n] = v;
-        }
-      }
-  }
+  CONV_EPILOGUE(acc, 4, t, g.M, g.Cout, conv_bias(bias), [&](int m, int n, float a, float bn) {
+    float v = a + bn;                                      // out = acc + bias + res
+    if (res) v += res[(size_t)m * g.Cout + n];
+    out[(size_t)m * g.Cout + n] = v;
+  });
 }
 
 static int launch_conv_vae_f16(const char* name, int norm, int silu, bool xf16, const void* x, const void* w, const float* bias, const float* res,
                                const float* mean, const float* rstd, const float* gamma, const float* beta, float* out, const VaeGeom& g,
                                void* stream) {
-  const unsigned grid = cdiv(g.M, CH_BM) * cdiv(g.Cout, CH_BN);
-  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * g.M * g.Cout * g.K) : -1;
-#define LDMAE_VAE16_LAUNCH(NORM, SILU, XF16)                                                                                            \
-  hipLaunchKernelGGL((conv_vae_f16_kernel<NORM, SILU, XF16>), dim3(grid), dim3(CH_NT), 0, as_stream(stream), x, (const f16*)w, bias, res, mean, \
-                     rstd, gamma, beta, out, g)
+#define LDMAE_VAE16_LAUNCH(NORM, SILU, XF16)                                                                                                  \
+  return conv_launch<CH_BM, CH_BN, CH_NT>(name, conv_vae_f16_kernel<NORM, SILU, XF16>, g.M, g.Cout, g.K, stream, x, (const f16*)w, bias, res, mean, \
+                                          rstd, gamma, beta, out, g)
   if (norm == 0 && xf16) LDMAE_VAE16_LAUNCH(0, false, true);
-  else if (norm == 0) LDMAE_VAE16_LAUNCH(0, false, false);
-  else if (norm == 1 && silu) LDMAE_VAE16_LAUNCH(1, true, false);
-  else if (norm == 1) LDMAE_VAE16_LAUNCH(1, false, false);
-  else if (norm == 2 && silu) LDMAE_VAE16_LAUNCH(2, true, false);
-  else if (norm == 2) LDMAE_VAE16_LAUNCH(2, false, false);
-  else if (silu) LDMAE_VAE16_LAUNCH(3, true, false);
-  else LDMAE_VAE16_LAUNCH(3, false, false);
+  if (norm == 0) LDMAE_VAE16_LAUNCH(0, false, false);
+  if (xf16) LDMAE_FAIL(LDMAE_ERR_INVALID, "%s: no kernel for an fp16 input under norm code %d", name, norm);
+  if (norm == 1 && silu) LDMAE_VAE16_LAUNCH(1, true, false);
+  if (norm == 1) LDMAE_VAE16_LAUNCH(1, false, false);
+  if (norm == 2 && silu) LDMAE_VAE16_LAUNCH(2, true, false);
+  if (norm == 2) LDMAE_VAE16_LAUNCH(2, false, false);
+  if (norm == 3 && silu) LDMAE_VAE16_LAUNCH(3, true, false);
+  if (norm == 3) LDMAE_VAE16_LAUNCH(3, false, false);
 #undef LDMAE_VAE16_LAUNCH
-  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
-  LDMAE_CHECK_LAUNCH(name);
-  return 0;
+  LDMAE_FAIL(LDMAE_ERR_INVALID, "%s: no kernel for norm code %d", name, norm);
 }
 
 extern "C" int ldmae_conv3x3_vae_nhwc_f16(int mode, int x_dtype, const void* x, const void* w, const float* bias, const float* res, const float* mean,
                                           const float* rstd, const float* gamma, const float* beta, int G, int silu, float* out, int B, int H, int W,
                                           int Cin, int Cout, void* stream) {
+  const char* name = "conv3x3_vae_nhwc_f16";
   LDMAE_REQUIRE(mode == LDMAE_VAE_PLAIN || mode == LDMAE_VAE_NORM_ACT || mode == LDMAE_VAE_DOWN || mode == LDMAE_VAE_UP,
-                "conv3x3_vae_nhwc_f16: mode %d (0 plain, 1 norm-act, 2 down, 3 up)", mode);
-  LDMAE_REQUIRE(x_dtype == LDMAE_F32 || x_dtype == LDMAE_F16, "conv3x3_vae_nhwc_f16: x_dtype %d (LDMAE_F32 or LDMAE_F16)", x_dtype);
-  LDMAE_REQUIRE(x_dtype == LDMAE_F32 || mode == LDMAE_VAE_PLAIN, "conv3x3_vae_nhwc_f16: an fp16 input is taken in plain mode only, got mode %d", mode);
-  LDMAE_REQUIRE(x && w && out, "conv3x3_vae_nhwc_f16: null pointer (only bias and res may be NULL)");
-  LDMAE_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_vae_nhwc_f16: B=%d H=%d W=%d Cin=%d Cout=%d must be positive", B, H, W, Cin, Cout);
-  LDMAE_REQUIRE(Cin % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv3x3_vae_nhwc_f16: Cin=%d must be a multiple of 8 and x, w 16-B aligned",
-                Cin);
-  VaeGeom g{};
-  g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.ks = 3;
-  g.Hv = H; g.Wv = W; g.up = 0; g.stride = 1; g.pad = 1; g.Ho = H; g.Wo = W; g.G = 1; g.cpg = Cin;
-  int norm = 0;
-  if (mode == LDMAE_VAE_NORM_ACT) {
-    LDMAE_REQUIRE(mean && rstd && gamma && beta && G > 0, "conv3x3_vae_nhwc_f16: norm-act needs mean, rstd, gamma, beta and a positive group count");
-    LDMAE_REQUIRE(Cin % G == 0, "conv3x3_vae_nhwc_f16: %d channels are not divisible into %d groups", Cin, G);
-    LDMAE_REQUIRE(((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0, "conv3x3_vae_nhwc_f16: gamma and beta must be 16-B aligned");
-    g.G = G; g.cpg = Cin / G;
-    norm = g.cpg % 8 == 0 ? 1 : g.cpg % 4 == 0 ? 2 : 3;
-  } else if (mode == LDMAE_VAE_DOWN) {
-    LDMAE_REQUIRE(H >= 2 && W >= 2, "conv3x3_vae_nhwc_f16: down needs at least 2 x 2 pixels");
-    g.stride = 2; g.pad = 0; g.Ho = (H + 1 - 3) / 2 + 1; g.Wo = (W + 1 - 3) / 2 + 1;      // pad (0, 1, 0, 1): right and bottom only
-  } else if (mode == LDMAE_VAE_UP) {
-    g.up = 1; g.Hv = 2 * H; g.Wv = 2 * W; g.Ho = 2 * H; g.Wo = 2 * W;
-  }
-  const long M = (long)B * g.Ho * g.Wo, K = 9L * Cin;
-  LDMAE_REQUIRE(M < (1L << 31) - CH_BM && M * Cout < (1L << 40) && (long)B * H * W * Cin < (1L << 40) && K < (1L << 24), "conv3x3_vae_nhwc_f16: problem too large");
-  g.M = (int)M; g.K = (int)K;
-  LDMAE_REQUIRE((long)cdiv(M, CH_BM) * cdiv(Cout, CH_BN) < (1L << 31), "conv3x3_vae_nhwc_f16: problem too large");
-  return launch_conv_vae_f16("conv3x3_vae_nhwc_f16", norm, silu, x_dtype == LDMAE_F16, x, w, bias, res, mean, rstd, gamma, beta, out, g, stream);
+                "%s: mode %d (0 plain, 1 norm-act, 2 down, 3 up)", name, mode);
+  LDMAE_REQUIRE(x_dtype == LDMAE_F32 || x_dtype == LDMAE_F16, "%s: x_dtype %d (LDMAE_F32 or LDMAE_F16)", name, x_dtype);
+  LDMAE_REQUIRE(x_dtype == LDMAE_F32 || mode == LDMAE_VAE_PLAIN, "%s: an fp16 input is taken in plain mode only, got mode %d", name, mode);
+  VaeGeom g;
+  if (const int rc = vae_geom_3x3(name, VAE_F16, mode, x, w, out, mean, rstd, gamma, beta, G, B, H, W, Cin, Cout, g)) return rc;
+  const int norm = mode != LDMAE_VAE_NORM_ACT ? 0 : g.cpg % 8 == 0 ? 1 : g.cpg % 4 == 0 ? 2 : 3;
+  return launch_conv_vae_f16(name, norm, silu, x_dtype == LDMAE_F16, x, w, bias, res, mean, rstd, gamma, beta, out, g, stream);
 }
 
 extern "C" int ldmae_conv1x1_res_nhwc_f16(const float* x, const void* w, const float* bias, const float* res, float* out, int M, int Cin, int Cout,
                                           void* stream) {
-  LDMAE_REQUIRE(x && w && out, "conv1x1_res_nhwc_f16: null pointer (only bias and res may be NULL)");
-  LDMAE_REQUIRE(M > 0 && Cin > 0 && Cout > 0, "conv1x1_res_nhwc_f16: M=%d Cin=%d Cout=%d must be positive", M, Cin, Cout);
-  LDMAE_REQUIRE(Cin % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv1x1_res_nhwc_f16: Cin=%d must be a multiple of 8 and x, w 16-B aligned",
-                Cin);
-  LDMAE_REQUIRE((long)M < (1L << 31) - CH_BM && (long)M * Cout < (1L << 40) && (long)M * Cin < (1L << 40) && Cin < (1 << 24) &&
-                    (long)cdiv(M, CH_BM) * cdiv(Cout, CH_BN) < (1L << 31),
-                "conv1x1_res_nhwc_f16: problem too large");
-  VaeGeom g{};
-  g.B = 1; g.H = 1; g.W = M; g.Cin = Cin; g.Cout = Cout; g.ks = 1;                          // M pixels of one row: no tap ever leaves the frame
-  g.Hv = 1; g.Wv = M; g.up = 0; g.stride = 1; g.pad = 0; g.Ho = 1; g.Wo = M; g.G = 1; g.cpg = Cin;
-  g.M = M; g.K = Cin;
+  VaeGeom g;
+  if (const int rc = vae_geom_1x1("conv1x1_res_nhwc_f16", VAE_F16, x, w, out, M, Cin, Cout, g)) return rc;
   return launch_conv_vae_f16("conv1x1_res_nhwc_f16", 0, 0, false, x, w, bias, res, nullptr, nullptr, nullptr, nullptr, out, g, stream);
 }
 

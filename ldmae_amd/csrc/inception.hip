@@ -9,7 +9,7 @@
 #include "conv_igemm_f32.h"
 
 // ------------------------------------------------------------------------------------------------ convolution
-// The tile shape and the MFMA main loop are conv_igemm_f32.h (shared with the LPIPS data gradient of lpips_bwd.hip).
+// The tile shape and the MFMA main loop are conv_igemm_f32.h, the skeleton around them conv_igemm_common.h.
 
 struct ConvGeom {
   int B, H, W, Cin, ldx, xoff;        // input [B, H, W, ldx], channels [xoff, xoff + Cin)
@@ -25,28 +25,19 @@ __global__ __launch_bounds__(CV_NT) void conv_igemm_f32_kernel(const float* __re
                                                                float* __restrict__ out, ConvGeom g) {
   __shared__ __attribute__((aligned(16))) float As[2][CV_BM * CV_LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][CV_BN * CV_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (g.Cout + CV_BN - 1) / CV_BN;
-  const int m0 = (int)(blockIdx.x / tiles_n) * CV_BM, n0 = (int)(blockIdx.x % tiles_n) * CV_BN;
-  // staging: thread tid owns k-columns [lc, lc + 4) of A rows lr and lr + 64 and of B row lr
-  const int lr = tid >> 2, lc = (tid & 3) * 4;
+  const CvTile t(g.Cout);
   int iy0[2], ix0[2];
   const float* xb[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
-    const int ox = m % g.Wo, t = m / g.Wo, oy = t % g.Ho, b = t / g.Ho;
-    iy0[p] = oy * g.sh - g.ph;
-    ix0[p] = ox * g.sw - g.pw;
-    xb[p] = x + (size_t)b * g.H * g.W * g.ldx + g.xoff;
+    const ConvRow r = conv_row(t, p, g.M, g.Ho, g.Wo, g.sh, g.sw, g.ph, g.pw);
+    iy0[p] = r.iy0;
+    ix0[p] = r.ix0;
+    xb[p] = x + (size_t)r.b * g.H * g.W * g.ldx + g.xoff;
   }
-  const float* wrow = w + (size_t)min(n0 + lr, g.Cout - 1) * g.K;
-  // (tap, channel) of this thread's first k, advanced by BK per step without divisions (VEC path)
-  int ci = lc, kx = 0, ky = 0;
-  if (VEC) {
-    while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.kw) { kx = 0; ++ky; } }
-  }
+  const float* wrow = conv_weight_row(w, t.n0 + t.lr, g.Cout, g.K);
+  int ci = t.lc, kx = 0, ky = 0;                           // VEC: (tap, channel) of this thread's first k
+  if (VEC) TAP_WRAP(ci, kx, ky, g.Cin, g.kw)
   auto fetch_a = [&](int p, int k0) -> float4 {
     if constexpr (VEC) {
       const int iy = iy0[p] + ky, ix = ix0[p] + kx;
@@ -57,7 +48,7 @@ __global__ __launch_bounds__(CV_NT) void conv_igemm_f32_kernel(const float* __re
       float v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int k = k0 + lc + j;
+        const int k = k0 + t.lc + j;
         const int c = k % g.Cin, tap = k / g.Cin, ty = tap / g.kw, tx = tap % g.kw;
         const int iy = iy0[p] + ty, ix = ix0[p] + tx;
         v[j] = (k < g.K && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W) ? xb[p][((size_t)iy * g.W + ix) * g.ldx + c] : 0.f;
@@ -66,44 +57,23 @@ __global__ __launch_bounds__(CV_NT) void conv_igemm_f32_kernel(const float* __re
     }
   };
   auto fetch_b = [&](int k0) -> float4 {
-    const int k = k0 + lc;
-    if (VEC) {                                             // K % 4 == 0
-      if (k < g.K) return *(const float4*)(wrow + k);
-      return make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    const int k = k0 + t.lc;
+    if (VEC) return fetch_weight_row<float4>(wrow, k, g.K);      // K % 4 == 0
     float v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = k + j < g.K ? wrow[k + j] : 0.f;
     return make_float4(v[0], v[1], v[2], v[3]);
   };
   auto advance = [&]() {
-    if (VEC) {
-      ci += CV_BK;
-      while (ci >= g.Cin) { ci -= g.Cin; if (++kx == g.kw) { kx = 0; ++ky; } }
-    }
+    if (VEC) { ci += CV_BK; TAP_WRAP(ci, kx, ky, g.Cin, g.kw) }
   };
 
   f32x4 acc[4][2];
   conv_igemm_f32_mainloop(As, Bs, (g.K + CV_BK - 1) / CV_BK, fetch_a, fetch_b, advance, acc);
-  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-  // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn * 32 + j * 16 + r16;
-    if (n >= g.Cout) continue;
-    const float bn = bias ? bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + i * 16 + q4 + r;
-        if (m < g.M) {
-          float v = acc[i][j][r] + bn;
-          if (RELU) v = fmaxf(v, 0.f);
-          out[(size_t)m * g.ldo + g.ooff + n] = v;
-        }
-      }
-  }
+  CONV_EPILOGUE(acc, 2, t, g.M, g.Cout, conv_bias(bias), [&](int m, int n, float a, float bn) {
+    const float v = a + bn;
+    out[(size_t)m * g.ldo + g.ooff + n] = RELU ? fmaxf(v, 0.f) : v;
+  });
 }
 
 extern "C" int ldmae_conv2d_nhwc_f32(const float* x, int ldx, int xoff, const float* w, const float* bias, float* out, int ldo, int ooff, int B, int H,
@@ -118,18 +88,13 @@ extern "C" int ldmae_conv2d_nhwc_f32(const float* x, int ldx, int xoff, const fl
   LDMAE_REQUIRE(M < (1L << 31) && (long)B * H * W * ldx < (1L << 40) && K < (1L << 24), "conv2d_nhwc_f32: problem too large");
   ConvGeom g{B, H, W, Cin, ldx, xoff, Ho, Wo, Cout, ldo, ooff, kh, kw, sh, sw, ph, pw, (int)M, (int)K};
   const bool vec = Cin % 4 == 0 && xoff % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0;
-  const unsigned grid = cdiv(M, CV_BM) * cdiv(Cout, CV_BN);
-  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * M * Cout * K) : -1;
-  if (vec) {
-    if (relu) hipLaunchKernelGGL((conv_igemm_f32_kernel<true, true>), dim3(grid), dim3(CV_NT), 0, as_stream(stream), x, w, bias, out, g);
-    else hipLaunchKernelGGL((conv_igemm_f32_kernel<true, false>), dim3(grid), dim3(CV_NT), 0, as_stream(stream), x, w, bias, out, g);
-  } else {
-    if (relu) hipLaunchKernelGGL((conv_igemm_f32_kernel<false, true>), dim3(grid), dim3(CV_NT), 0, as_stream(stream), x, w, bias, out, g);
-    else hipLaunchKernelGGL((conv_igemm_f32_kernel<false, false>), dim3(grid), dim3(CV_NT), 0, as_stream(stream), x, w, bias, out, g);
-  }
-  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
-  LDMAE_CHECK_LAUNCH("conv2d_nhwc_f32");
-  return 0;
+#define LDMAE_CONV_LAUNCH(VEC, RELU) \
+  return conv_launch<CV_BM, CV_BN, CV_NT>("conv2d_nhwc_f32", conv_igemm_f32_kernel<VEC, RELU>, M, Cout, K, stream, x, w, bias, out, g)
+  if (vec && relu) LDMAE_CONV_LAUNCH(true, true);
+  if (vec) LDMAE_CONV_LAUNCH(true, false);
+  if (relu) LDMAE_CONV_LAUNCH(false, true);
+  LDMAE_CONV_LAUNCH(false, false);
+#undef LDMAE_CONV_LAUNCH
 }
 
 // ------------------------------------------------------------------------------------------------ pools

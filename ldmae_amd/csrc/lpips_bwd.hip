@@ -22,26 +22,19 @@ __global__ __launch_bounds__(CV_NT) void conv3x3_relu_dgrad_kernel(const float* 
                                                                    float* __restrict__ dx, DgradGeom g) {
   __shared__ __attribute__((aligned(16))) float As[2][CV_BM * CV_LD];
   __shared__ __attribute__((aligned(16))) float Bs[2][CV_BN * CV_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (g.Cx + CV_BN - 1) / CV_BN;
-  const int m0 = (int)(blockIdx.x / tiles_n) * CV_BM, n0 = (int)(blockIdx.x % tiles_n) * CV_BN;
-  const int lr = tid >> 2, lc = (tid & 3) * 4;
-  int iy0[2], ix0[2];
+  const CvTile t(g.Cx);
+  ConvRow row[2];
   size_t base[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
-    const int ox = m % g.W, t = m / g.W, oy = t % g.H, b = t / g.H;
-    iy0[p] = oy - 1;
-    ix0[p] = ox - 1;
-    base[p] = (size_t)b * g.H * g.W * g.Cy;
+    row[p] = conv_row(t, p, g.M, g.H, g.W, 1, 1, 1, 1);
+    base[p] = (size_t)row[p].b * g.H * g.W * g.Cy;
   }
-  const float* wrow = w + (size_t)min(n0 + lr, g.Cx - 1) * g.K;
-  int ci = lc, kx = 0, ky = 0;                             // (tap, channel) of this thread's first k; Cy % 4 == 0: a float4 never straddles taps
-  while (ci >= g.Cy) { ci -= g.Cy; if (++kx == 3) { kx = 0; ++ky; } }
+  const float* wrow = conv_weight_row(w, t.n0 + t.lr, g.Cx, g.K);
+  int ci = t.lc, kx = 0, ky = 0;                           // Cy % 4 == 0: a float4 never straddles taps
+  TAP_WRAP(ci, kx, ky, g.Cy, 3)
   auto fetch_a = [&](int p, int) -> float4 {
-    const int iy = iy0[p] + ky, ix = ix0[p] + kx;
+    const int iy = row[p].iy0 + ky, ix = row[p].ix0 + kx;
     if (ky < 3 && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W) {
       const size_t o = base[p] + ((size_t)iy * g.W + ix) * g.Cy + ci;
       const float4 d = *(const float4*)(dy + o), a = *(const float4*)(y + o);
@@ -49,30 +42,11 @@ __global__ __launch_bounds__(CV_NT) void conv3x3_relu_dgrad_kernel(const float* 
     }
     return make_float4(0.f, 0.f, 0.f, 0.f);
   };
-  auto fetch_b = [&](int k0) -> float4 {
-    const int k = k0 + lc;
-    if (k < g.K) return *(const float4*)(wrow + k);
-    return make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto advance = [&]() {
-    ci += CV_BK;
-    while (ci >= g.Cy) { ci -= g.Cy; if (++kx == 3) { kx = 0; ++ky; } }
-  };
+  auto fetch_b = [&](int k0) { return fetch_weight_row<float4>(wrow, k0 + t.lc, g.K); };
+  auto advance = [&]() { ci += CV_BK; TAP_WRAP(ci, kx, ky, g.Cy, 3) };
   f32x4 acc[4][2];
   conv_igemm_f32_mainloop(As, Bs, (g.K + CV_BK - 1) / CV_BK, fetch_a, fetch_b, advance, acc);
-  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn * 32 + j * 16 + r16;
-    if (n >= g.Cx) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + i * 16 + q4 + r;
-        if (m < g.M) dx[(size_t)m * g.Cx + n] = acc[i][j][r];
-      }
-  }
+  CONV_EPILOGUE(acc, 2, t, g.M, g.Cx, conv_no_col(), [&](int m, int n, float a, int) { dx[(size_t)m * g.Cx + n] = a; });
 }
 
 extern "C" int ldmae_conv3x3_relu_dgrad_nhwc_f32(const float* dy, const float* y, const float* w_rot, float* dx, int B, int H, int W, int Cy, int Cx,
@@ -83,12 +57,7 @@ extern "C" int ldmae_conv3x3_relu_dgrad_nhwc_f32(const float* dy, const float* y
   const long M = (long)B * H * W, K = 9L * Cy;
   LDMAE_REQUIRE(M < (1L << 31) && M * Cy < (1L << 40) && K < (1L << 24), "conv3x3_relu_dgrad: problem too large");
   DgradGeom g{B, H, W, Cy, Cx, (int)M, (int)K};
-  const unsigned grid = cdiv(M, CV_BM) * cdiv(Cx, CV_BN);
-  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * M * Cx * K) : -1;
-  hipLaunchKernelGGL(conv3x3_relu_dgrad_kernel, dim3(grid), dim3(CV_NT), 0, as_stream(stream), dy, y, w_rot, dx, g);
-  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
-  LDMAE_CHECK_LAUNCH("conv3x3_relu_dgrad");
-  return 0;
+  return conv_launch<CV_BM, CV_BN, CV_NT>("conv3x3_relu_dgrad", conv3x3_relu_dgrad_kernel, M, Cx, K, stream, dy, y, w_rot, dx, g);
 }
 
 // ------------------------------------------------------------------------------------------------ 2x2 / 2 max-pool backward
@@ -156,13 +125,6 @@ extern "C" int ldmae_maxpool2x2_bwd_nhwc_xf16(const float* dy, const void* x, fl
 // d0 / d1 [B, h, w, C]: gradient to the input / target half; null = not wanted.  ACC: add into them instead of overwriting.
 constexpr int LB_NT = 256;
 
-template <int L>
-__device__ __forceinline__ float lane_group_sum_bwd(float v) {
-#pragma unroll
-  for (int o = 1; o < L; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int C, bool ACC, typename T>
 __global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const T* __restrict__ f, const float* __restrict__ lw, const float* __restrict__ gout,
                                                                 float* __restrict__ d0, float* __restrict__ d1, int B, int HW, int chunks) {
@@ -188,8 +150,8 @@ __global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const T* __restr
       s0 += a[v].x * a[v].x + a[v].y * a[v].y + a[v].z * a[v].z + a[v].w * a[v].w;
       s1 += c[v].x * c[v].x + c[v].y * c[v].y + c[v].z * c[v].z + c[v].w * c[v].w;
     }
-    s0 = lane_group_sum_bwd<L>(s0);
-    s1 = lane_group_sum_bwd<L>(s1);
+    s0 = lane_group_sum<L>(s0);
+    s1 = lane_group_sum<L>(s1);
     const float nrm0 = sqrtf(s0), nrm1 = sqrtf(s1);
     const float r0 = 1.f / (nrm0 + 1e-10f), r1 = 1.f / (nrm1 + 1e-10f);
     float dot0 = 0.f, dot1 = 0.f;
@@ -202,8 +164,8 @@ __global__ __launch_bounds__(LB_NT) void lpips_layer_bwd_kernel(const T* __restr
       dot0 += t[v].x * a[v].x + t[v].y * a[v].y + t[v].z * a[v].z + t[v].w * a[v].w;
       dot1 += t[v].x * c[v].x + t[v].y * c[v].y + t[v].z * c[v].z + t[v].w * c[v].w;
     }
-    dot0 = lane_group_sum_bwd<L>(dot0);
-    dot1 = lane_group_sum_bwd<L>(dot1);
+    dot0 = lane_group_sum<L>(dot0);
+    dot1 = lane_group_sum<L>(dot1);
     if (o0) {
       const float k0 = nrm0 > 0.f ? r0 : 0.f, q0 = nrm0 > 0.f ? dot0 * r0 * r0 / nrm0 : 0.f;
 #pragma unroll

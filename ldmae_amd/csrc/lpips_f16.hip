@@ -17,72 +17,39 @@ struct Vgg16Geom {
   int M, K;
 };
 
-// The (tap, channel) cursor of a thread's 8-element fragment; C % 8 == 0, so a fragment never straddles a tap.  A BK step may walk over
-// several taps (C < BK), hence the loop.
-struct TapCursor {
-  int ci, kx, ky;
-  __device__ __forceinline__ void init(int lc, int C) { ci = lc; kx = 0; ky = 0; wrap(C); }
-  __device__ __forceinline__ void wrap(int C) { while (ci >= C) { ci -= C; if (++kx == 3) { kx = 0; ++ky; } } }
-  __device__ __forceinline__ void step(int C) { ci += CH_BK; wrap(C); }
-};
-
 // ------------------------------------------------------------------------------------------------ forward: conv3x3 + bias + ReLU, fp16 -> fp16
 __global__ __launch_bounds__(CH_NT) void conv3x3_relu_f16_kernel(const f16* __restrict__ x, const f16* __restrict__ w, const float* __restrict__ bias,
                                                                  f16* __restrict__ out, Vgg16Geom g) {
   __shared__ __attribute__((aligned(16))) f16 As[2][CH_BM * CH_LD];
   __shared__ __attribute__((aligned(16))) f16 Bs[2][CH_BN * CH_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (g.Cout + CH_BN - 1) / CH_BN;
-  const int m0 = (int)(blockIdx.x / tiles_n) * CH_BM, n0 = (int)(blockIdx.x % tiles_n) * CH_BN;
-  const int lr = tid >> 2, lc = (tid & 3) * 8;
-  int iy0[2], ix0[2];
+  const ChTile t(g.Cout);
+  ConvRow row[2];
   size_t xb[2];
   const f16* wrow[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
-    const int ox = m % g.W, t = m / g.W, oy = t % g.H, b = t / g.H;
-    iy0[p] = oy - 1;
-    ix0[p] = ox - 1;
-    xb[p] = (size_t)b * g.H * g.W * g.Cin;
-    wrow[p] = w + (size_t)min(n0 + lr + p * 64, g.Cout - 1) * g.K;      // rows past Cout fetch the last filter; never stored
+    row[p] = conv_row(t, p, g.M, g.H, g.W, 1, 1, 1, 1);
+    xb[p] = (size_t)row[p].b * g.H * g.W * g.Cin;
+    wrow[p] = conv_weight_row(w, t.n0 + t.lr + p * 64, g.Cout, g.K);
   }
-  TapCursor cur;
-  cur.init(lc, g.Cin);
+  TapCursor<CH_BK> cur;
+  cur.init(t.lc, g.Cin, 3);
   auto fetch_a = [&](int p) -> f16x8 {
-    const int iy = iy0[p] + cur.ky, ix = ix0[p] + cur.kx;
+    const int iy = row[p].iy0 + cur.ky, ix = row[p].ix0 + cur.kx;
     if (cur.ky < 3 && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W)
       return *(const f16x8*)(x + xb[p] + ((size_t)iy * g.W + ix) * g.Cin + cur.ci);
     return (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
   };
-  auto fetch_b = [&](int p, int k0) -> f16x8 {
-    const int k = k0 + lc;                                 // K % 8 == 0
-    if (k < g.K) return *(const f16x8*)(wrow[p] + k);
-    return (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-  };
-  auto advance = [&]() { cur.step(g.Cin); };
+  auto fetch_b = [&](int p, int k0) { return fetch_weight_row<f16x8>(wrow[p], k0 + t.lc, g.K); };
+  auto advance = [&]() { cur.step(g.Cin, 3); };
 
   f32x4 acc[4][4];
   conv_igemm_f16_mainloop(As, Bs, (g.K + CH_BK - 1) / CH_BK, fetch_a, fetch_b, advance, acc);
-  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-  // epilogue: D row (lane >> 4) * 4 + r, column lane & 15 of each 16 x 16 block; out = fp16_sat(max(acc + bias, 0))
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + wn * 64 + j * 16 + r16;
-    if (n >= g.Cout) continue;
-    const float bn = bias ? bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + i * 16 + q4 + r;
-        if (m < g.M) {
-          const float v = acc[i][j][r] + bn;
-          out[(size_t)m * g.Cout + n] = (f16)sat_f16(v > 0.f ? v : (v == v ? 0.f : v), 65504.f);      // NaN stays NaN
-        }
-      }
-  }
+  // out = fp16_sat(max(acc + bias, 0)); NaN stays NaN
+  CONV_EPILOGUE(acc, 4, t, g.M, g.Cout, conv_bias(bias), [&](int m, int n, float a, float bn) {
+    const float v = a + bn;
+    out[(size_t)m * g.Cout + n] = to_f16_sat(v > 0.f ? v : (v == v ? 0.f : v));
+  });
 }
 
 extern "C" int ldmae_conv3x3_relu_nhwc_f16(const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
@@ -96,12 +63,7 @@ extern "C" int ldmae_conv3x3_relu_nhwc_f16(const void* x, const void* w, const f
                     (long)cdiv(M, CH_BM) * cdiv(Cout, CH_BN) < (1L << 31),
                 "conv3x3_relu_nhwc_f16: problem too large");
   Vgg16Geom g{B, H, W, Cin, Cout, (int)M, (int)K};
-  const unsigned grid = cdiv(M, CH_BM) * cdiv(Cout, CH_BN);
-  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * M * Cout * K) : -1;
-  hipLaunchKernelGGL(conv3x3_relu_f16_kernel, dim3(grid), dim3(CH_NT), 0, as_stream(stream), (const f16*)x, (const f16*)w, bias, (f16*)out, g);
-  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
-  LDMAE_CHECK_LAUNCH("conv3x3_relu_nhwc_f16");
-  return 0;
+  return conv_launch<CH_BM, CH_BN, CH_NT>("conv3x3_relu_nhwc_f16", conv3x3_relu_f16_kernel, M, Cout, K, stream, (const f16*)x, (const f16*)w, bias, (f16*)out, g);
 }
 
 // ------------------------------------------------------------------------------------------------ 2x2 / 2 max pool, fp16
@@ -140,27 +102,20 @@ __global__ __launch_bounds__(CH_NT) void conv3x3_relu_dgrad_bf16_kernel(const fl
                                                                         float* __restrict__ dx, Vgg16Geom g) {
   __shared__ __attribute__((aligned(16))) bf16 As[2][CH_BM * CH_LD];
   __shared__ __attribute__((aligned(16))) bf16 Bs[2][CH_BN * CH_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (g.Cout + CH_BN - 1) / CH_BN;
-  const int m0 = (int)(blockIdx.x / tiles_n) * CH_BM, n0 = (int)(blockIdx.x % tiles_n) * CH_BN;
-  const int lr = tid >> 2, lc = (tid & 3) * 8;
-  int iy0[2], ix0[2];
+  const ChTile t(g.Cout);
+  ConvRow row[2];
   size_t base[2];
   const bf16* wrow[2];
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    const int m = min(m0 + lr + p * 64, g.M - 1);          // rows past M fetch a real pixel; their results are never stored
-    const int ox = m % g.W, t = m / g.W, oy = t % g.H, b = t / g.H;
-    iy0[p] = oy - 1;
-    ix0[p] = ox - 1;
-    base[p] = (size_t)b * g.H * g.W * g.Cin;
-    wrow[p] = w + (size_t)min(n0 + lr + p * 64, g.Cout - 1) * g.K;
+    row[p] = conv_row(t, p, g.M, g.H, g.W, 1, 1, 1, 1);
+    base[p] = (size_t)row[p].b * g.H * g.W * g.Cin;
+    wrow[p] = conv_weight_row(w, t.n0 + t.lr + p * 64, g.Cout, g.K);
   }
-  TapCursor cur;
-  cur.init(lc, g.Cin);
+  TapCursor<CH_BK> cur;
+  cur.init(t.lc, g.Cin, 3);
   auto fetch_a = [&](int p) -> bf16x8 {
-    const int iy = iy0[p] + cur.ky, ix = ix0[p] + cur.kx;
+    const int iy = row[p].iy0 + cur.ky, ix = row[p].ix0 + cur.kx;
     bf16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
     if (cur.ky < 3 && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W) {
       const size_t o = base[p] + ((size_t)iy * g.W + ix) * g.Cin + cur.ci;
@@ -172,28 +127,12 @@ __global__ __launch_bounds__(CH_NT) void conv3x3_relu_dgrad_bf16_kernel(const fl
     }
     return r;
   };
-  auto fetch_b = [&](int p, int k0) -> bf16x8 {
-    const int k = k0 + lc;                                 // K % 8 == 0
-    if (k < g.K) return *(const bf16x8*)(wrow[p] + k);
-    return (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-  };
-  auto advance = [&]() { cur.step(g.Cin); };
+  auto fetch_b = [&](int p, int k0) { return fetch_weight_row<bf16x8>(wrow[p], k0 + t.lc, g.K); };
+  auto advance = [&]() { cur.step(g.Cin, 3); };
 
   f32x4 acc[4][4];
   conv_igemm_f16_mainloop(As, Bs, (g.K + CH_BK - 1) / CH_BK, fetch_a, fetch_b, advance, acc);
-  const int q4 = (lane >> 4) * 4, r16 = lane & 15;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + wn * 64 + j * 16 + r16;
-    if (n >= g.Cout) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 64 + i * 16 + q4 + r;
-        if (m < g.M) dx[(size_t)m * g.Cout + n] = acc[i][j][r];
-      }
-  }
+  CONV_EPILOGUE(acc, 4, t, g.M, g.Cout, conv_no_col(), [&](int m, int n, float a, int) { dx[(size_t)m * g.Cout + n] = a; });
 }
 
 extern "C" int ldmae_conv3x3_relu_dgrad_nhwc_bf16(const float* dy, const void* y, const void* w_rot, float* dx, int B, int H, int W, int Cy, int Cx,
@@ -207,10 +146,5 @@ extern "C" int ldmae_conv3x3_relu_dgrad_nhwc_bf16(const float* dy, const void* y
                     (long)cdiv(M, CH_BM) * cdiv(Cx, CH_BN) < (1L << 31),
                 "conv3x3_relu_dgrad_bf16: problem too large");
   Vgg16Geom g{B, H, W, Cy, Cx, (int)M, (int)K};
-  const unsigned grid = cdiv(M, CH_BM) * cdiv(Cx, CH_BN);
-  const long pidx = ldmae_prof_is_on() ? ldmae_prof_begin(as_stream(stream), 2.0 * M * Cx * K) : -1;
-  hipLaunchKernelGGL(conv3x3_relu_dgrad_bf16_kernel, dim3(grid), dim3(CH_NT), 0, as_stream(stream), dy, (const f16*)y, (const bf16*)w_rot, dx, g);
-  if (pidx >= 0) ldmae_prof_end(pidx, as_stream(stream));
-  LDMAE_CHECK_LAUNCH("conv3x3_relu_dgrad_bf16");
-  return 0;
+  return conv_launch<CH_BM, CH_BN, CH_NT>("conv3x3_relu_dgrad_bf16", conv3x3_relu_dgrad_bf16_kernel, M, Cx, K, stream, dy, (const f16*)y, (const bf16*)w_rot, dx, g);
 }

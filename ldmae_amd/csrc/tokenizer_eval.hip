@@ -32,9 +32,9 @@ __global__ __launch_bounds__(256) void lpips_prep_f16_kernel(const float* __rest
   const long n = i / HW, p = i % HW;
   const float* src = (n < B ? in0 + n * 3 * HW : in1 + (n - B) * 3 * HW) + p;
   f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-  v[0] = (f16)sat_f16((src[0] - (-0.030f)) / 0.458f, 65504.f);
-  v[1] = (f16)sat_f16((src[HW] - (-0.088f)) / 0.448f, 65504.f);
-  v[2] = (f16)sat_f16((src[2 * HW] - (-0.188f)) / 0.450f, 65504.f);
+  v[0] = to_f16_sat((src[0] - (-0.030f)) / 0.458f);
+  v[1] = to_f16_sat((src[HW] - (-0.088f)) / 0.448f);
+  v[2] = to_f16_sat((src[2 * HW] - (-0.188f)) / 0.450f);
   *(f16x8*)(out + i * 8) = v;
 }
 
@@ -62,13 +62,6 @@ extern "C" int ldmae_lpips_prep(const float* input, const float* target, float* 
 // group), then d = sum_c w_c (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 from the same registers -- equal halves give exactly 0.
 // grid (chunks, B): block (k, b) walks pixels k * PPB + j * chunks * PPB of image b and writes its sum of d to part[b * chunks + k].
 constexpr int LP_NT = 256, LP_MAX_CHUNKS = 128;
-
-template <int L>
-__device__ __forceinline__ float lane_group_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < L; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 template <int C, typename T>
 __global__ __launch_bounds__(LP_NT) void lpips_layer_kernel(const T* __restrict__ f, const float* __restrict__ lw, float* __restrict__ part,

@@ -99,11 +99,11 @@ def _conv_inputs(B, H, W, Cin, Cout, seed):
     return x, w, 0.3 * _randn(Cout, seed=seed + 2), 1 + 0.1 * _randn(Cin, seed=seed + 3), 0.1 * _randn(Cin, seed=seed + 4)
 
 
-def _check_norm_act(name, x, w, bias, res, gamma, beta):
+def _check_norm_act(name, x, w, bias, res, gamma, beta, silu=True):
     ops = _ops()
     xc, wc = x.cuda(), w.cuda()
     stats = ops.groupnorm_stats_nhwc(xc, G, EPS)
-    a, y = _act64(x, stats[0].cpu(), stats[1].cpu(), gamma, beta)
+    a, y = _act64(x, stats[0].cpu(), stats[1].cpu(), gamma, beta, silu)
     ref, S = _conv64(a, w), _conv64(a.abs(), w.abs())
     sig = _conv64(a.abs() * gc._sig_err(y), w.abs())
     for t in (bias, res):
@@ -111,9 +111,10 @@ def _check_norm_act(name, x, w, bias, res, gamma, beta):
             ref, S = ref + t.double(), S + t.double().abs()
     bound = gc.sum_bound(ref, S, 9 * x.shape[3], F32) + sig
     cu = lambda t: None if t is None else t.cuda()
-    fused = ops.conv3x3_vae_nhwc(xc, wc, cu(bias), mode=ops.VAE_NORM_ACT, res=cu(res), stats=stats, gamma=gamma.cuda(), beta=beta.cuda())
+    fused = ops.conv3x3_vae_nhwc(xc, wc, cu(bias), mode=ops.VAE_NORM_ACT, res=cu(res), stats=stats, gamma=gamma.cuda(), beta=beta.cuda(),
+                                 silu=silu)
     r1 = gc.check(name + " fused", fused.cpu(), ref, bound)
-    act = ops.groupnorm_apply_nhwc(xc, stats, gamma.cuda(), beta.cuda(), silu=True)
+    act = ops.groupnorm_apply_nhwc(xc, stats, gamma.cuda(), beta.cuda(), silu=silu)
     two = ops.conv3x3_vae_nhwc(act, wc, cu(bias), mode=ops.VAE_PLAIN, res=cu(res))
     r2 = gc.check(name + " two-pass", two.cpu(), ref, bound)
     print(f"{name}: fused x{r1:.3g}, two-pass x{r2:.3g} of bound")
@@ -125,12 +126,18 @@ def _check_norm_act(name, x, w, bias, res, gamma, beta):
 CONV_SHAPES = [(2, 9, 7, 32, 32), (2, 18, 18, 64, 96), (1, 5, 3, 512, 128)]
 
 
-@pytest.mark.parametrize("with_res_bias", [False, True])
-@pytest.mark.parametrize("B,H,W,Cin,Cout", CONV_SHAPES)
-def test_conv_norm_act(B, H, W, Cin, Cout, with_res_bias):
+# every case with SiLU, as the tokenizers run it, plus one without per instantiation conv_vae_kernel<NORM, false> that only such a call
+# reaches (1 and 16 channels per group: NORM 2 and 1), against the same reference and bound (its sigmoid term then only widens it)
+NORM_ACT_CASES = [(*s, rb, True) for rb in (False, True) for s in CONV_SHAPES] + [(*CONV_SHAPES[0], False, False), (*CONV_SHAPES[2], False, False)]
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,with_res_bias,silu", NORM_ACT_CASES,
+                         ids=["-".join(map(str, c[:6])) + ("" if c[6] else "-nosilu") for c in NORM_ACT_CASES])
+def test_conv_norm_act(B, H, W, Cin, Cout, with_res_bias, silu):
     x, w, bias, gamma, beta = _conv_inputs(B, H, W, Cin, Cout, seed=Cin + Cout)
     res = _randn(B, H, W, Cout, seed=5) if with_res_bias else None
-    _check_norm_act(f"norm-act {B}x{H}x{W} {Cin}->{Cout} res/bias={with_res_bias}", x, w, bias if with_res_bias else None, res, gamma, beta)
+    _check_norm_act(f"norm-act {B}x{H}x{W} {Cin}->{Cout} res/bias={with_res_bias} silu={silu}", x, w, bias if with_res_bias else None, res, gamma, beta,
+                    silu)
 
 
 def test_conv_norm_act_border_taps_are_zero():

@@ -48,14 +48,14 @@ def _randn(*shape, seed=0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=F32)
 
 
-def _act64(x, mean, rstd, gamma, beta):
-    """(a, y, t) in f64, NHWC, from the statistics as returned (f32 values): t = gamma (x - mean) rstd, y = t + beta, a = silu(y)."""
+def _act64(x, mean, rstd, gamma, beta, silu=True):
+    """(a, y, t) in f64, NHWC, from the statistics as returned (f32 values): t = gamma (x - mean) rstd, y = t + beta, a = silu(y) (or y)."""
     cpg = x.shape[3] // mean.shape[1]
     mu = mean.double().repeat_interleave(cpg, 1)[:, None, None, :]
     rs = rstd.double().repeat_interleave(cpg, 1)[:, None, None, :]
     t = gamma.double() * (x.double() - mu) * rs
     y = t + beta.double()
-    return y * torch.sigmoid(y), y, t
+    return (y * torch.sigmoid(y) if silu else y), y, t
 
 
 def _conv64(a, w, stride=1, pad=(1, 1, 1, 1)):
@@ -98,18 +98,18 @@ def _pack16(w):
     return _ops().cast(w.cuda().contiguous(), torch.float16)
 
 
-def _norm_act(name, x, w, bias, res, gamma, beta, form):
+def _norm_act(name, x, w, bias, res, gamma, beta, form, silu=True):
     ops = _ops()
     xc, w16 = x.cuda(), _pack16(w)
     stats = ops.groupnorm_stats_nhwc(xc, G, EPS)
-    a, y, t = _act64(x, stats[0].cpu(), stats[1].cpu(), gamma, beta)
+    a, y, t = _act64(x, stats[0].cpu(), stats[1].cpu(), gamma, beta, silu)
     d = 1.1 * (3 * U * t.abs() + U * y.abs()) + a.abs() * (gc._sig_err(y) + 2 * U)
     cu = lambda v: None if v is None else v.cuda()
     if form == "fused":
         got = ops.conv3x3_vae_nhwc(xc, w16, cu(bias), mode=ops.VAE_NORM_ACT, res=cu(res), stats=stats, gamma=gamma.cuda(), beta=beta.cuda(),
-                                   precision="tf32")
+                                   silu=silu, precision="tf32")
     else:
-        act = ops.groupnorm_apply_nhwc(xc, stats, gamma.cuda(), beta.cuda(), silu=True, out_dtype=torch.float16)
+        act = ops.groupnorm_apply_nhwc(xc, stats, gamma.cuda(), beta.cuda(), silu=silu, out_dtype=torch.float16)
         assert act.dtype == torch.float16
         got = ops.conv3x3_vae_nhwc(act, w16, cu(bias), mode=ops.VAE_PLAIN, res=cu(res), precision="tf32")
     ref = _check_both(f"{name} {form}", got.cpu(), a, w, 9 * x.shape[3], (bias, res), d=d)
@@ -120,16 +120,22 @@ def _norm_act(name, x, w, bias, res, gamma, beta, form):
 NORM_SHAPES = [(2, 9, 7, 32, 32), (2, 18, 18, 64, 96), (1, 5, 3, 512, 128), (1, 6, 5, 128, 3)]
 
 
-@pytest.mark.parametrize("form", ["fused", "two-pass"])
-@pytest.mark.parametrize("with_res_bias", [False, True])
-@pytest.mark.parametrize("B,H,W,Cin,Cout", NORM_SHAPES)
-def test_conv_norm_act(B, H, W, Cin, Cout, with_res_bias, form):
+# every case with SiLU, as the tokenizers run it, plus one fused case without per instantiation conv_vae_f16_kernel<NORM, false, false> that
+# only such a call reaches (1, 4 and 16 channels per group: NORM 3, 2 and 1), against the same references and bounds (their sigmoid term then
+# only widens them)
+NORM_ACT_CASES = [(*s, rb, f, True) for f in ("fused", "two-pass") for rb in (False, True) for s in NORM_SHAPES] + \
+                 [(*NORM_SHAPES[i], False, "fused", False) for i in (0, 3, 2)]
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,with_res_bias,form,silu", NORM_ACT_CASES,
+                         ids=["-".join(map(str, c[:7])) + ("" if c[7] else "-nosilu") for c in NORM_ACT_CASES])
+def test_conv_norm_act(B, H, W, Cin, Cout, with_res_bias, form, silu):
     x, w, bias, gamma, beta = _conv_inputs(B, H, W, Cin, Cout, seed=Cin + Cout)
     res = _randn(B, H, W, Cout, seed=5) if with_res_bias else None
-    _norm_act(f"norm-act {B}x{H}x{W} {Cin}->{Cout} res/bias={with_res_bias}", x, w, bias if with_res_bias else None, res, gamma, beta, form)
+    _norm_act(f"norm-act {B}x{H}x{W} {Cin}->{Cout} res/bias={with_res_bias} silu={silu}", x, w, bias if with_res_bias else None, res, gamma, beta, form,
+              silu)
 
 
-# a BK = 32 step spans taps (Cin = 8, 16, 40); K = 72, 144, 360 leave tails of 8, 16 and 8; Cout = 512 is four N tiles
 @pytest.mark.parametrize("B,H,W,Cin,Cout", [(2, 7, 5, 8, 40), (1, 4, 4, 16, 512), (2, 5, 6, 40, 72)])
 def test_conv_plain(B, H, W, Cin, Cout):
     ops = _ops()
