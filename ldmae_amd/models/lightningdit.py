@@ -156,6 +156,13 @@ def _dmod_times_w(dmod, adaw):
     return ops.gemm_nt(dmod, ops.cast_weight(adaw, torch.float32, True, False)[1])
 
 
+def _mod_cols(t, D, nmod):
+    """(shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp), :246: the column chunks [B, D] of a block's modulation vectors `t`
+    [B, nmod * D] or of their gradient buffer.  nmod 4 (wo_shift, :242: modulate without the shift): None for the two shifts."""
+    cols = (0, 1, 2, 3, 4, 5) if nmod == 6 else (None, 0, 1, None, 2, 3)
+    return tuple(None if c is None else t[:, c * D:(c + 1) * D] for c in cols)
+
+
 def _dw_into_grad(sg, dy, x, param, direct):
     """Weight gradient dy^T x.  `direct` (the training driver opted in: LightningDiT.direct_param_grads) and the parameter already has a
     contiguous f32 `.grad` (a view of the optimizer's gradient slab): the TN GEMM's deterministic slab reduce ADDS into it (beta = 1, what
@@ -218,6 +225,68 @@ def _qk_layernorm_bwd(dq, dk, dv, saved, qnw, knw, cos, sin, B, N, H, hd, dtype,
     dkw, dkb = ops.layernorm_bwd(ops.rope(dk, cos, sin, transposed=True).view(-1, hd), k32, knw, muk, rsk, dxk)
     dqkv = ops.heads_merge(ops.cast(dxq, dtype).view(B, H, N, hd), ops.cast(dxk, dtype).view(B, H, N, hd), dv, B, N, H, hd)
     return dqkv, dqw, dqb, dkw, dkb, (ops.colsum(dqkv) if with_bias else None)
+
+
+def _attn_fwd(a, W, qkvb, qnw, knw, qnb, knb, cos, sin, B, N, H, hd, eps, dtype, fused, store_raw_qk=True, mx8=False):
+    """The attention front end of _DiTBlockFn, _AttentionFn and _block_fwd_mx8: qkv Linear (:68) -> q_norm / k_norm (:70) -> RoPE (:71-73) ->
+    softmax attention (:75-88).  -> (qkv [M, 3D] == [B,N,3,H,hd], q, k, v head-major, o [B,N,D], lse, saved tuple of the nn.LayerNorm QK-norm
+    or None).  What differs between the callers: `fused` -- may q_norm / k_norm / RoPE run in the qkv GEMM's epilogue where it covers the shape
+    (bitwise the GEMM + qknorm_rope_fwd pair); store_raw_qk -- does that epilogue store the pre-norm q / k (only a backward reads them); mx8 --
+    the block-scaled fp8 GEMMs: a = (quantised activations, scales), W = (quantised weight, scales), dtype bfloat16, no nn.LayerNorm form."""
+    scale = hd ** -0.5
+    qk_saved = v = None
+    if mx8:
+        fused = fused and ops.gemm_nt_qkv_rope_mx8_ok(a[0], W[0], B, N, H, hd)      # not XL's head dim 72, nor token counts off the epilogue's grid
+        if fused:
+            qkv, q, k = ops.gemm_nt_qkv_rope_mx8(*a, *W, qkvb, qnw, knw, cos, sin, B, N, H, hd, eps, store_raw_qk=store_raw_qk)
+        else:
+            qkv = ops.gemm_nt_mx8(*a, *W, qkvb)
+    else:
+        fused = fused and qnb is None and dtype == torch.bfloat16 and ops.gemm_nt_qkv_rope_ok(a, W, B, N, H, hd)
+        if fused:
+            qkv, q, k = ops.gemm_nt_qkv_rope(a, W, qkvb, qnw, knw, cos, sin, B, N, H, hd, eps, store_raw_qk=store_raw_qk)
+        else:
+            qkv = ops.gemm_nt(a, W, qkvb)                # [M, 3D] == [B,N,3,H,hd]
+    if qnb is None and dtype == torch.bfloat16:      # v is consumed where the qkv Linear wrote it: no head-major copy of v (nor of dv in backward)
+        if not fused:
+            q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps, copy_v=False)
+        # QK-RMSNorm bounds |q|, |k| by max|w| sqrt(hd) and the rotation keeps norms: a proven score bound, so the softmax runs with a
+        # static shift (no running maximum in the kernel).  use_qknorm=False (qnw None; q_norm = nn.Identity, :60-61): nothing bounds the
+        # scores, the kernel tracks the running maximum.
+        o, lse = ops.attention_fwd_pv(q, k, qkv, scale, bound=ops.qk_score_bound(qnw, knw, hd, scale) if qnw is not None else None)
+        return qkv, q, k, v, o, lse, None
+    if qnb is not None:                              # nn.LayerNorm QK-norm: composed path (see _qk_layernorm_fwd)
+        q, k, v, qk_saved = _qk_layernorm_fwd(qkv, qnw, qnb, knw, knb, cos, sin, B, N, H, hd, dtype)
+    else:
+        q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps)
+    o, lse = ops.attention_fwd(q, k, v, scale)
+    return qkv, q, k, v, o, lse, qk_saved
+
+
+def _attn_bwd(q, k, v, qkv, o, do, lse, qk_saved, qnw, knw, cos, sin, B, N, H, hd, eps, dtype, with_bias, fused_qkn):
+    """Backward of _attn_fwd from do to -> (dqkv [B,N,3,H,hd], dqn, dkn, dqnb, dknb, dbqkv).  with_bias=False (the input-gradient-only backward):
+    no column sums for the qkv bias where a kernel lets us turn them off (dbqkv None there).  fused_qkn: may the QK-norm / RoPE backward run
+    inside the attention backward's epilogues (bf16, head dim 64 / 128, N % 64 == 0: no head-major dq / dk); it forms the weight and bias
+    sums whatever with_bias says."""
+    scale = hd ** -0.5
+    dqnb = dknb = None
+    # the nn.LayerNorm form always has a head-major v (heads_split), so none of the packed-v arms below can be handed its weights
+    assert qk_saved is None or v is not None
+    if v is None and fused_qkn and hd in (64, 128) and N % 64 == 0 and _FUSED_QKN_BWD:
+        dqkv, dqn, dkn, dbqkv = ops.attention_bwd_pv_qknorm(q, k, qkv, o, do, lse, scale, qnw, knw, cos, sin, eps)
+        return dqkv, dqn, dkn, dqnb, dknb, dbqkv
+    if v is None:
+        dq, dk, dqkv = ops.attention_bwd_pv(q, k, qkv, o, do, lse, scale)            # dv lands in the v slot of dqkv
+        dv = None
+    else:
+        dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, scale)
+        dqkv = None
+    if qk_saved is not None:                         # nn.LayerNorm QK-norm (composed path)
+        dqkv, dqn, dqnb, dkn, dknb, dbqkv = _qk_layernorm_bwd(dq, dk, dv, qk_saved, qnw, knw, cos, sin, B, N, H, hd, dtype, with_bias=with_bias)
+    else:                                            # (with_bias=False: three values)
+        dqkv, dqn, dkn, *db = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, with_bias=with_bias, dqkv=dqkv)
+        dbqkv = db[0] if db else None
+    return dqkv, dqn, dkn, dqnb, dknb, dbqkv
 
 
 class _GradChain:
@@ -309,12 +378,7 @@ def _block_fwd_mx8(x2, B, N, D, H, hd, eps, cos, sin, sh1, s1, g1, sh2, s2, g2, 
     Wqkv, Wp, W12, W3 = (ops.cached_weight_mx8(w) for w in (qkvw, pw, w12, w3))
     # attention branch
     a1q, a1s, _ = ops.rmsnorm_modulate_fwd_mx8(x2, n1w, sh1, s1, N, eps)
-    if ops.gemm_nt_qkv_rope_mx8_ok(a1q, Wqkv[0], B, N, H, hd):
-        qkv, q, k = ops.gemm_nt_qkv_rope_mx8(a1q, a1s, Wqkv[0], Wqkv[1], qkvb, qnw, knw, cos, sin, B, N, H, hd, eps, store_raw_qk=False)
-    else:                                  # XL's head dim 72, token counts off the fused epilogue's grid
-        qkv = ops.gemm_nt_mx8(a1q, a1s, Wqkv[0], Wqkv[1], qkvb)
-        q, k, _ = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps, copy_v=False)
-    o, _ = ops.attention_fwd_pv(q, k, qkv, hd ** -0.5, bound=ops.qk_score_bound(qnw, knw, hd, hd ** -0.5) if qnw is not None else None)
+    o = _attn_fwd((a1q, a1s), Wqkv, qkvb, qnw, knw, None, None, cos, sin, B, N, H, hd, eps, torch.bfloat16, fused=True, store_raw_qk=False, mx8=True)[4]
     oq, osc = ops.mx8_quantize(o.view(M, D))
     xmid, _ = ops.gemm_nt_gate_res_mx8(oq, osc, Wp[0], Wp[1], pb, x2, g1, N)
     # MLP branch
@@ -323,6 +387,13 @@ def _block_fwd_mx8(x2, B, N, D, H, hd, eps, cos, sin, sh1, s1, g1, sh2, s2, g2, 
     hq, hsc = ops.mx8_quantize(hid)
     xout, _ = ops.gemm_nt_gate_res_mx8(hq, hsc, W3[0], W3[1], b3, xmid, g2, N)
     return xout.view(B, N, D)
+
+
+# _DiTBlockFn.forward's arguments after ctx, the forward-only `gemm_precision` left out (it never reaches a backward): backward files its
+# gradients under these names and returns them in this order, so a new argument cannot shift the gradient of another
+_BLOCK_ARGS = ("x", "sc", "cos", "sin", "H", "eps", "dtype", "inplace", "chain", "idx", "direct", "fwd_only", "mod_all", "swiglu",
+               "n1w", "qkvw", "qkvb", "qnw", "knw", "qnb", "knb", "pw", "pb", "n2w", "w12", "b12", "w3", "b3", "adaw", "adab", "input_only")
+_BLOCK_SMALL = ("n1w", "qkvb", "qnw", "knw", "pb", "n2w", "b12", "b3", "qnb", "knb")      # norm weights, biases, QK-norm weights / biases
 
 
 class _DiTBlockFn(torch.autograd.Function):
@@ -343,11 +414,7 @@ class _DiTBlockFn(torch.autograd.Function):
             mod = mod_all[:, idx * nmod * D:(idx + 1) * nmod * D]
         else:
             mod = ops.gemm_nt(sc, adaw, adab, out_dtype=torch.float32)                   # [B, 6D] f32
-        if nmod == 6:
-            sh1, s1, g1, sh2, s2, g2 = (mod[:, i * D:(i + 1) * D] for i in range(6))      # :246 chunk order
-        else:
-            s1, g1, s2, g2 = (mod[:, i * D:(i + 1) * D] for i in range(4))                # :242 (wo_shift: modulate without the shift)
-            sh1 = sh2 = None
+        sh1, s1, g1, sh2, s2, g2 = _mod_cols(mod, D, nmod)
         # forward-only calls (torch.no_grad sampling: forward_with_cfg) skip everything only the backward pass reads: the transposed
         # weight copies, the pre-gate branch outputs y1 / y2 and h12 = [x1 | x2] of the SwiGLU (1.6 GB per XL/1 block at batch 128).
         # The flag comes from the module (grad mode is always off in here and needs_input_grad ignores torch.no_grad()).
@@ -377,26 +444,8 @@ class _DiTBlockFn(torch.autograd.Function):
             xm1, rstd1 = handed[1], handed[2]
         else:
             xm1, rstd1 = ops.rmsnorm_modulate_fwd(x2, n1w, sh1, s1, N, dtype, eps)
-        qk_saved = None
-        fused_qkv = qnb is None and dtype == torch.bfloat16 and ops.gemm_nt_qkv_rope_ok(xm1, Wqkv, B, N, H, hd)
-        if not fused_qkv:
-            qkv = ops.gemm_nt(xm1, Wqkv, qkvb)                                           # [M, 3D] == [B,N,3,H,hd]
-        if qnb is not None:              # nn.LayerNorm QK-norm: composed path (see _qk_layernorm_fwd)
-            q, k, v, qk_saved = _qk_layernorm_fwd(qkv, qnw, qnb, knw, knb, cos, sin, B, N, H, hd, dtype)
-            o, lse = ops.attention_fwd(q, k, v, hd ** -0.5)
-        elif dtype == torch.bfloat16:    # v is consumed where the qkv Linear wrote it: no head-major copy of v (nor of dv in backward)
-            if fused_qkv:                # q_norm / k_norm / RoPE in the qkv GEMM's epilogue (bitwise the pair below; forward-only calls skip the pre-norm q / k)
-                qkv, q, k = ops.gemm_nt_qkv_rope(xm1, Wqkv, qkvb, qnw, knw, cos, sin, B, N, H, hd, eps, store_raw_qk=bwd)
-                v = None
-            else:
-                q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps, copy_v=False)
-            # QK-RMSNorm bounds |q|, |k| by max|w| sqrt(hd) and the rotation keeps norms: a proven score bound, so the softmax runs with a
-            # static shift (no running maximum in the kernel).  use_qknorm=False (qnw None; q_norm = nn.Identity, :60-61): nothing bounds the
-            # scores, the kernel tracks the running maximum.
-            o, lse = ops.attention_fwd_pv(q, k, qkv, hd ** -0.5, bound=ops.qk_score_bound(qnw, knw, hd, hd ** -0.5) if qnw is not None else None)      # [B,N,D]
-        else:
-            q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps)
-            o, lse = ops.attention_fwd(q, k, v, hd ** -0.5)
+        qkv, q, k, v, o, lse, qk_saved = _attn_fwd(xm1, Wqkv, qkvb, qnw, knw, qnb, knb, cos, sin, B, N, H, hd, eps, dtype,
+                                                   fused=True, store_raw_qk=bwd)      # (forward-only calls skip the pre-norm q / k)
         if resnorm:
             y1 = ops.gemm_nt(o.view(M, D), Wp, pb)
             _, xm2, rstd2 = ops.res_rmsnorm_modulate_fwd(x2, y1, g1, None, None, n2w, sh2, s2, N, eps)
@@ -415,7 +464,7 @@ class _DiTBlockFn(torch.autograd.Function):
             n1w_next = chain.nxt.get(idx)
             if n1w_next is not None:     # the next block's norm1 rides along (its column slice of mod_all: shift_msa, scale_msa first)
                 modn = mod_all[:, (idx + 1) * nmod * D:(idx + 2) * nmod * D]
-                shn, sn = (modn[:, :D], modn[:, D:2 * D]) if nmod == 6 else (None, modn[:, :D])
+                shn, sn = _mod_cols(modn, D, nmod)[:2]
                 xout, xm1n, rstd1n = ops.res_rmsnorm_modulate_fwd(x2, y1, g1, y2, g2, n1w_next, shn, sn, N, eps, want_xout=True)
                 chain.fwd[idx + 1] = (xout.data_ptr(), xm1n, rstd1n)
             else:                        # last block: the final layer keeps its own norm
@@ -425,84 +474,34 @@ class _DiTBlockFn(torch.autograd.Function):
         if not bwd:
             return xout.view(B, N, D)
         ctx.input_only = bool(input_only)
-        if input_only:
-            # LightningDiT.input_grad_only: dx is wanted and nothing else.  Saved: what the dx chain reads (the weight-gradient GEMMs' left
-            # operands xm1 / xm2 / hid, SiLU(c) and the adaLN weight are not); y1 / y2 stay because the fused norm + gate backward reads them
-            ctx.save_for_backward(x2, cos, sin, mod, rstd1, qkv, q, k, v, o, lse, y1, xmid, rstd2, h12, y2, n1w, qnw, knw, n2w,
-                                  WqkvT, WpT, W12T, W3T, *(qk_saved or ()))
-            ctx.dims = (B, N, D, H, hd, eps, dtype)
-            ctx.swiglu, ctx.qk_ln, ctx.nmod, ctx.inplace = bool(swiglu), qk_saved is not None, nmod, bool(inplace)
-            ctx.chain, ctx.idx = chain, idx
-            if chain is not None:
-                chain.up[idx] = (y2, mod)
-            return xout.view(B, N, D)
-        ctx.save_for_backward(x2, sc, cos, sin, mod, rstd1, xm1, qkv, q, k, v, o, lse, y1, xmid, rstd2, xm2, h12, hid, y2,
-                              n1w, qnw, knw, n2w, adaw, WqkvT, WpT, W12T, W3T, *(qk_saved or ()))
+        # LightningDiT.input_grad_only: dx is wanted and nothing else.  What only the parameter gradients read -- the weight-gradient GEMMs' left
+        # operands xm1 / xm2 / hid, SiLU(c) and the adaLN weight -- is not kept alive: its slot holds None.  y1 / y2 stay because the fused
+        # norm + gate backward reads them
+        po = (lambda t_: None) if input_only else (lambda t_: t_)      # noqa: E731
+        ctx.save_for_backward(x2, po(sc), cos, sin, mod, rstd1, po(xm1), qkv, q, k, v, o, lse, y1, xmid, rstd2, po(xm2), h12, po(hid), y2,
+                              n1w, qnw, knw, n2w, po(adaw), WqkvT, WpT, W12T, W3T, *(qk_saved or ()))
         ctx.dims = (B, N, D, H, hd, eps, dtype)
         ctx.swiglu, ctx.qk_ln = bool(swiglu), qk_saved is not None
         ctx.nmod = nmod
         ctx.inplace = bool(inplace)
         ctx.chain, ctx.idx = chain, idx
-        ctx.direct, ctx.wparams = bool(direct), (qkvw, pw, w12, w3)      # (padded hidden: w12 / w3 are the padded copies -- no .grad, so the direct path declines them)
-        ctx.sparams = (n1w, qkvb, qnw, knw, pb, n2w, b12, b3, qnb, knb) if direct else None
+        # the parameters the gradients go to (padded hidden: w12 / w3 are the padded copies -- no .grad, so the direct path declines them).  Not
+        # under input_only: nothing reads them there, and the padded copies (35 MB per LightningDiT-L block) would live as long as the graph
+        ctx.direct = bool(direct) and not input_only
+        ctx.wparams = None if input_only else (qkvw, pw, w12, w3)
+        ctx.sparams = (n1w, qkvb, qnw, knw, pb, n2w, b12, b3, qnb, knb) if ctx.direct else None      # in _BLOCK_SMALL's order
         if chain is not None:
             chain.up[idx] = (y2, mod)
         return xout.view(B, N, D)
 
     @staticmethod
-    def _backward_input_only(ctx, gout):
-        """The dx chain of backward() below, launch for launch, and nothing else: no weight-gradient GEMM, no side stream, no bias / norm-weight /
-        QK-norm-weight reduction that a kernel lets us turn off, no adaLN gradients, no .grad writes.  Kernels that form a parameter gradient
-        as a by-product of the pass that produces dx (the fused norm + gate backward, the attention backward with the QK-norm epilogue, the
-        norm backward's weight and modulation sums) run unchanged and the by-product is dropped: dx has the bits of the full backward."""
-        (x2, cos, sin, mod, rstd1, qkv, q, k, v, o, lse, y1, xmid, rstd2, h12, y2, n1w, qnw, knw, n2w, WqkvT, WpT, W12T, W3T) = ctx.saved_tensors[:24]
-        qk_saved = ctx.saved_tensors[24:] if ctx.qk_ln else None
-        B, N, D, H, hd, eps, dtype = ctx.dims
-        M = B * N
-        dx = gout.contiguous().view(M, D)
-        if not ctx.inplace and dx.data_ptr() == gout.data_ptr():
-            dx = dx.clone()
-        chain, idx = ctx.chain, ctx.idx
-        c_sh1, c_s1, c_g1, c_sh2, c_s2, c_g2 = (0, 1, 2, 3, 4, 5) if ctx.nmod == 6 else (None, 0, 1, None, 2, 3)
-        col = lambda t_, c_: None if c_ is None else t_[:, c_ * D:(c_ + 1) * D]      # noqa: E731
-        s1, g1, s2, g2 = col(mod, c_s1), col(mod, c_g1), col(mod, c_s2), col(mod, c_g2)
-        # ---- MLP branch
-        pre = chain.pre.pop(idx, None) if chain is not None else None
-        if pre is not None and pre[0] == dx.data_ptr():
-            _, dy2, _, dmod = pre
-        else:
-            dmod = chain.dmod(idx, mod) if chain is not None else torch.empty(mod.shape, dtype=mod.dtype, device=mod.device)
-            dy2 = ops.gate_bwd(dx, y2, g2, None, N, dtype)
-        if ctx.swiglu:
-            dh12 = ops.gemm_nt_swiglu_bwd(dy2, W3T, h12)
-        else:
-            dh12 = ops.gelu_tanh_bwd(ops.gemm_nt(dy2, W3T), h12)
-        dxm2 = ops.gemm_nt(dh12, W12T)
-        _, dy1, _ = ops.rmsnorm_modulate_bwd_gate(dxm2, xmid, n2w, s2, rstd2, dx, col(dmod, c_sh2), col(dmod, c_s2), y1, g1, col(dmod, c_g1), N, dtype)
-        # ---- attention branch
-        do = ops.gemm_nt(dy1, WpT)
-        if qk_saved is not None:
-            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
-            dqkv = _qk_layernorm_bwd(dq, dk, dv, qk_saved, qnw, knw, cos, sin, B, N, H, hd, dtype, with_bias=False)[0]
-        elif v is None and hd in (64, 128) and N % 64 == 0 and _FUSED_QKN_BWD:
-            dqkv = ops.attention_bwd_pv_qknorm(q, k, qkv, o, do, lse, hd ** -0.5, qnw, knw, cos, sin, eps)[0]
-        elif v is None:
-            dq, dk, dqkv = ops.attention_bwd_pv(q, k, qkv, o, do, lse, hd ** -0.5)
-            dqkv = ops.qknorm_rope_bwd(dq, dk, None, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, dqkv=dqkv)[0]
-        else:
-            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
-            dqkv = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, B, N, H, hd, eps)[0]
-        dxm1 = ops.gemm_nt(dqkv.view(M, 3 * D), WqkvT)
-        if chain is not None:
-            chain.norm_bwd(idx, dxm1, x2, n1w, s1, rstd1, dx, col(dmod, c_sh1), col(dmod, c_s1), N, dtype)
-        else:
-            ops.rmsnorm_modulate_bwd(dxm1, x2, n1w, s1, rstd1, dx, col(dmod, c_sh1), col(dmod, c_s1), N)
-        return (dx.view(B, N, D),) + (None,) * 30
-
-    @staticmethod
     def backward(ctx, gout):
-        if ctx.input_only:
-            return _DiTBlockFn._backward_input_only(ctx, gout)
+        """Both modes.  io (LightningDiT.input_grad_only): the dx chain and nothing else -- no weight-gradient GEMM, no side stream, no bias /
+        norm-weight / QK-norm-weight reduction that a kernel lets us turn off, no adaLN gradients, no .grad writes.  Kernels that form a
+        parameter gradient as a by-product of the pass that produces dx (the fused norm + gate backward, the attention backward with the
+        QK-norm epilogue, the norm backward's weight and modulation sums) run unchanged and the by-product is dropped: dx has the bits of
+        the full backward because it comes out of the same statements."""
+        io = ctx.input_only
         (x2, sc, cos, sin, mod, rstd1, xm1, qkv, q, k, v, o, lse, y1, xmid, rstd2, xm2, h12, hid, y2,
          n1w, qnw, knw, n2w, adaw, WqkvT, WpT, W12T, W3T) = ctx.saved_tensors[:29]
         qk_saved = ctx.saved_tensors[29:] if ctx.qk_ln else None
@@ -516,81 +515,81 @@ class _DiTBlockFn(torch.autograd.Function):
         if not ctx.inplace and dx.data_ptr() == gout.data_ptr():
             dx = dx.clone()
         chain, idx = ctx.chain, ctx.idx
-        # column chunk of each modulation vector in mod / dmod: (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp), :246; no shifts with wo_shift, :242
-        c_sh1, c_s1, c_g1, c_sh2, c_s2, c_g2 = (0, 1, 2, 3, 4, 5) if ctx.nmod == 6 else (None, 0, 1, None, 2, 3)
-        col = lambda t_, c_: None if c_ is None else t_[:, c_ * D:(c_ + 1) * D]      # noqa: E731
-        s1, g1, s2, g2 = col(mod, c_s1), col(mod, c_g1), col(mod, c_s2), col(mod, c_g2)
-        sg = ops.SideGemms(dx.device, enabled=dtype == torch.bfloat16)      # weight gradients: off the critical path
+        _, s1, g1, _, s2, g2 = _mod_cols(mod, D, ctx.nmod)
+        sg = None if io else ops.SideGemms(dx.device, enabled=dtype == torch.bfloat16)      # weight gradients: off the critical path
+        qkvw_p, pw_p, w12_p, w3_p = (None,) * 4 if io else ctx.wparams
+        notify = []
+
+        def dweight(dy, x_, param):      # dy^T x_ into .grad or for autograd (see _dw_into_grad); io: none
+            if io:
+                return None
+            g_, ready = _dw_into_grad(sg, dy, x_, param, ctx.direct)
+            notify.append((ready, param))
+            return g_
+
+        grads = {}
         # ---- MLP branch
         pre = chain.pre.pop(idx, None) if chain is not None else None
-        if pre is not None and pre[0] == dx.data_ptr():      # the next member's backward already gated this dx (see _GradChain)
-            _, dy2, db3, dmod = pre
+        gated = pre is not None and pre[0] == dx.data_ptr()      # the next member's backward already gated this dx (see _GradChain)
+        dmod = pre[3] if gated else chain.dmod(idx, mod) if chain is not None else torch.empty(mod.shape, dtype=mod.dtype, device=mod.device)
+        dsh1, ds1, dg1, dsh2, ds2, dg2 = _mod_cols(dmod, D, ctx.nmod)
+        if gated:
+            dy2, grads["b3"] = pre[1], pre[2]
+        elif io:
+            dy2 = ops.gate_bwd(dx, y2, g2, None, N, dtype)
         else:
-            dmod = chain.dmod(idx, mod) if chain is not None else torch.empty(mod.shape, dtype=mod.dtype, device=mod.device)
-            dy2, db3 = ops.gate_bwd(dx, y2, g2, col(dmod, c_g2), N, dtype, with_bias=True)   # bias grads where dy is produced
-        qkvw_p, pw_p, w12_p, w3_p = ctx.wparams
-        notify = []
-        dW3, r = _dw_into_grad(sg, dy2, hid, w3_p, ctx.direct); notify.append((r, w3_p))
+            dy2, grads["b3"] = ops.gate_bwd(dx, y2, g2, dg2, N, dtype, with_bias=True)   # bias grads where dy is produced
+        grads["w3"] = dweight(dy2, hid, w3_p)
         if ctx.swiglu:
-            dh12, db12 = ops.gemm_nt_swiglu_bwd(dy2, W3T, h12, with_bias=True)
+            dh12 = ops.gemm_nt_swiglu_bwd(dy2, W3T, h12, with_bias=not io)
+            if not io:
+                dh12, grads["b12"] = dh12
         else:                            # timm Mlp: fc2's input gradient through the tanh-GELU backward; fc1's bias gradient = its column sums
             dh12 = ops.gelu_tanh_bwd(ops.gemm_nt(dy2, W3T), h12)
-            db12 = ops.colsum(dh12)
-        dW12, r = _dw_into_grad(sg, dh12, xm2, w12_p, ctx.direct); notify.append((r, w12_p))
+            if not io:
+                grads["b12"] = ops.colsum(dh12)
+        grads["w12"] = dweight(dh12, xm2, w12_p)
         dxm2 = ops.gemm_nt(dh12, W12T)
         # norm2 backward and the attention branch's gate backward in one pass (the updated dx is consumed from registers)
-        # (ctx.resnorm: the mid-block row was never stored -- `xmid` is x2 and the kernel rebuilds the row from (x2, y1, g1))
-        dn2, dy1, dbp = ops.rmsnorm_modulate_bwd_gate(dxm2, xmid, n2w, s2, rstd2, dx, col(dmod, c_sh2), col(dmod, c_s2),
-                                                      y1, g1, col(dmod, c_g1), N, dtype, recompute=ctx.resnorm)
+        # (ctx.resnorm, never set under io: the mid-block row was never stored -- `xmid` is x2 and the kernel rebuilds the row from (x2, y1, g1))
+        grads["n2w"], dy1, grads["pb"] = ops.rmsnorm_modulate_bwd_gate(dxm2, xmid, n2w, s2, rstd2, dx, dsh2, ds2, y1, g1, dg1, N, dtype, recompute=ctx.resnorm)
         # ---- attention branch
-        dWp, r = _dw_into_grad(sg, dy1, o.view(M, D), pw_p, ctx.direct); notify.append((r, pw_p))
+        grads["pw"] = dweight(dy1, o.view(M, D), pw_p)
         do = ops.gemm_nt(dy1, WpT)
-        dqnb = dknb = None
-        if qk_saved is not None:         # nn.LayerNorm QK-norm (composed path)
-            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
-            dqkv, dqn, dqnb, dkn, dknb, dbqkv = _qk_layernorm_bwd(dq, dk, dv, qk_saved, qnw, knw, cos, sin, B, N, H, hd, dtype)
-        elif v is None and hd in (64, 128) and N % 64 == 0 and _FUSED_QKN_BWD:      # QK-norm / RoPE backward inside the attention backward's epilogues: no head-major dq / dk
-            dqkv, dqn, dkn, dbqkv = ops.attention_bwd_pv_qknorm(q, k, qkv, o, do, lse, hd ** -0.5, qnw, knw, cos, sin, eps)
-        elif v is None:
-            dq, dk, dqkv = ops.attention_bwd_pv(q, k, qkv, o, do, lse, hd ** -0.5)          # dv lands in the v slot of dqkv
-            dqkv, dqn, dkn, dbqkv = ops.qknorm_rope_bwd(dq, dk, None, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, with_bias=True, dqkv=dqkv)
-        else:
-            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
-            dqkv, dqn, dkn, dbqkv = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, with_bias=True)
+        dqkv, grads["qnw"], grads["knw"], grads["qnb"], grads["knb"], grads["qkvb"] = _attn_bwd(
+            q, k, v, qkv, o, do, lse, qk_saved, qnw, knw, cos, sin, B, N, H, hd, eps, dtype, with_bias=not io, fused_qkn=True)
         dqkv = dqkv.view(M, 3 * D)
-        dWqkv, r = _dw_into_grad(sg, dqkv, xm1, qkvw_p, ctx.direct); notify.append((r, qkvw_p))
+        grads["qkvw"] = dweight(dqkv, xm1, qkvw_p)
         dxm1 = ops.gemm_nt(dqkv, WqkvT)
         if chain is not None:
-            dn1 = chain.norm_bwd(idx, dxm1, x2, n1w, s1, rstd1, dx, col(dmod, c_sh1), col(dmod, c_s1), N, dtype)
+            grads["n1w"] = chain.norm_bwd(idx, dxm1, x2, n1w, s1, rstd1, dx, dsh1, ds1, N, dtype)
         else:
-            dn1 = ops.rmsnorm_modulate_bwd(dxm1, x2, n1w, s1, rstd1, dx, col(dmod, c_sh1), col(dmod, c_s1), N)
+            grads["n1w"] = ops.rmsnorm_modulate_bwd(dxm1, x2, n1w, s1, rstd1, dx, dsh1, ds1, N)
+        grads["x"] = dx.view(B, N, D)
+        if io:                           # dx alone: the by-products filed above are dropped
+            return tuple(grads[n_] if n_ == "x" else None for n_ in _BLOCK_ARGS)
         # ---- adaLN: per block in f32, or (batched) nothing here -- block 0, the last to run, returns the shared dmod buffer for mod_all
-        dmod_all = None
-        if ctx.batched_ada:
-            dadaw = dadab = dsc = None
-            if idx == 0:
-                dmod_all = chain.dmod_all
-        else:
-            dadaw, dadab = ops.gemm_tn(dmod, sc), ops.colsum(dmod)
-            dsc = _dmod_times_w(dmod, adaw)
+        if not ctx.batched_ada:
+            grads["adaw"], grads["adab"] = ops.gemm_tn(dmod, sc), ops.colsum(dmod)
+            grads["sc"] = _dmod_times_w(dmod, adaw)
+        elif idx == 0:
+            grads["mod_all"] = chain.dmod_all
         if ctx.hs is not None:                         # padded SwiGLU hidden: hand autograd the real units' rows / columns
-            dW12, db12, dW3 = _unpad_swiglu_grads(dW12, db12, dW3, *ctx.hs)
+            grads["w12"], grads["b12"], grads["w3"] = _unpad_swiglu_grads(grads["w12"], grads["b12"], grads["w3"], *ctx.hs)
         sg.join()
-        # the eight small gradients of the block (norm weights, biases, QK-norm weights): with `direct`, ONE launch adds them into their .grad
+        # the small gradients of the block (norm weights, biases, QK-norm weights): with `direct`, ONE launch adds them into their .grad
         # views instead of one AccumulateGrad add each
-        small = [dn1, dbqkv, dqn, dkn, dbp, dn2, db12, db3, dqnb, dknb]
         if ctx.sparams is not None:
-            pairs = [(p_, g_) for p_, g_ in zip(ctx.sparams, small) if p_ is not None]      # use_qknorm=False: no q_norm / k_norm weights
+            pairs = [(p_, grads[n_]) for p_, n_ in zip(ctx.sparams, _BLOCK_SMALL) if p_ is not None]      # use_qknorm=False: no q_norm / k_norm weights
             if all(g_ is not None and p_.grad is not None and p_.grad.dtype == torch.float32 and p_.grad.is_contiguous() and p_.grad.shape == g_.shape
                    for p_, g_ in pairs):
                 ops.multi_add_([p_.grad for p_, _ in pairs], [g_ for _, g_ in pairs])
                 notify.extend((getattr(p_, "_ldmae_grad_ready", None), p_) for p_, _ in pairs)
-                dn1 = dbqkv = dqn = dkn = dbp = dn2 = db12 = db3 = dqnb = dknb = None
+                grads.update(dict.fromkeys(_BLOCK_SMALL))
         for r, p_ in notify:          # gradients written straight into .grad: tell the reducer (no-op without one)
             if r is not None:
                 r(p_)
-        return (dx.view(B, N, D), dsc, None, None, None, None, None, None, None, None, None, None, dmod_all, None,
-                dn1, dWqkv, dbqkv, dqn, dkn, dqnb, dknb, dWp, dbp, dn2, dW12, db12, dW3, db3, dadaw, dadab, None)
+        return tuple(grads.get(n_) for n_ in _BLOCK_ARGS)
 
 
 class _AttentionFn(torch.autograd.Function):
@@ -604,17 +603,7 @@ class _AttentionFn(torch.autograd.Function):
         xa = ops.cast(x.contiguous().view(M, D), dtype)
         Wqkv, WqkvT = _wcopies(qkvw, dtype, True)
         Wp, WpT = _wcopies(pw, dtype, True)
-        qkv = ops.gemm_nt(xa, Wqkv, qkvb)
-        qk_saved = None
-        if qnb is not None:              # nn.LayerNorm QK-norm (use_rmsnorm=False): composed path
-            q, k, v, qk_saved = _qk_layernorm_fwd(qkv, qnw, qnb, knw, knb, cos, sin, B, N, H, hd, dtype)
-            o, lse = ops.attention_fwd(q, k, v, hd ** -0.5)
-        elif dtype == torch.bfloat16:
-            q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps, copy_v=False)
-            o, lse = ops.attention_fwd_pv(q, k, qkv, hd ** -0.5, bound=ops.qk_score_bound(qnw, knw, hd, hd ** -0.5) if qnw is not None else None)
-        else:
-            q, k, v = ops.qknorm_rope_fwd(qkv, qnw, knw, cos, sin, B, N, H, hd, eps)
-            o, lse = ops.attention_fwd(q, k, v, hd ** -0.5)
+        qkv, q, k, v, o, lse, qk_saved = _attn_fwd(xa, Wqkv, qkvb, qnw, knw, qnb, knb, cos, sin, B, N, H, hd, eps, dtype, fused=False)
         out = ops.gemm_nt(o.view(M, D), Wp, pb)
         ctx.save_for_backward(xa, cos, sin, qkv, q, k, v, o, lse, qnw, knw, WqkvT, WpT, *(qk_saved or ()))
         ctx.dims = (B, N, D, H, hd, eps, x.dtype)
@@ -629,16 +618,10 @@ class _AttentionFn(torch.autograd.Function):
         dy = ops.cast(g.contiguous().view(M, D), xa.dtype)
         dWp, dbp = ops.gemm_tn(dy, o.view(M, D), with_bias=True)
         do = ops.gemm_nt(dy, WpT)
-        dqnb = dknb = None
-        if ctx.qk_ln:
-            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
-            dqkv, dqn, dqnb, dkn, dknb, dbqkv = _qk_layernorm_bwd(dq, dk, dv, ctx.saved_tensors[13:], qnw, knw, cos, sin, B, N, H, hd, xa.dtype)
-        elif v is None:
-            dq, dk, dqkv = ops.attention_bwd_pv(q, k, qkv, o, do, lse, hd ** -0.5)
-            dqkv, dqn, dkn, dbqkv = ops.qknorm_rope_bwd(dq, dk, None, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, with_bias=True, dqkv=dqkv)
-        else:
-            dq, dk, dv = ops.attention_bwd(q, k, v, o, do, lse, hd ** -0.5)
-            dqkv, dqn, dkn, dbqkv = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, B, N, H, hd, eps, with_bias=True)
+        # fused_qkn=False (and fused=False in forward): the stand-alone module's historical path, kept launch for launch -- attention_bwd_pv +
+        # qknorm_rope_bwd where the block takes the attention backward with the QK-norm epilogue
+        dqkv, dqn, dkn, dqnb, dknb, dbqkv = _attn_bwd(q, k, v, qkv, o, do, lse, ctx.saved_tensors[13:] if ctx.qk_ln else None, qnw, knw, cos, sin,
+                                                      B, N, H, hd, eps, xa.dtype, with_bias=True, fused_qkn=False)
         dqkv = dqkv.view(M, 3 * D)
         dWqkv = ops.gemm_tn(dqkv, xa)
         dx = ops.gemm_nt(dqkv, WqkvT).view(B, N, D).to(xdt) if ctx.needs_input_grad[0] else None

@@ -243,6 +243,36 @@ def test_input_only_backward_leaves_preset_grads_alone():
     assert all(torch.equal(p.grad, torch.full_like(p, 3.0)) for p in m.parameters() if p.requires_grad)
 
 
+@pytest.mark.parametrize("prec,B", [("f32", 2), ("bf16", 8)])
+def test_input_only_graph_keeps_the_full_layout_without_the_weight_gradient_operands(prec, B):
+    """One saved-tensor layout for both modes: under input_grad_only() a block node has the 29 slots of the full mode, and those that only
+    the parameter gradients read -- SiLU(c), xm1, xm2, hid, the adaLN weight (slots 1, 6, 16, 18, 24) -- hold None, so nothing is kept alive
+    for them."""
+    from test_gpu_resnorm_fused import _block_nodes
+    m = _dit()
+    x, t, y, _ = _inputs(B)
+    with m.input_grad_only(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=prec == "bf16"):
+        out = m(x.clone().requires_grad_(True), t, y)
+    nodes = _block_nodes(out.grad_fn)
+    assert len(nodes) == 2
+    for n in nodes:
+        sv = n.saved_tensors
+        assert len(sv) == 29
+        assert [i for i, s in enumerate(sv) if s is None] == sorted([1, 6, 16, 18, 24] + ([10] if prec == "bf16" else []))      # (bf16: no head-major v, slot 10)
+        assert sv[0].shape == (B * 64, 128) and sv[13].shape == (B * 64, 128) and sv[15].shape == (B * 64,)
+        # nor through the node's attributes: the zero-padded f32 copies of w12 / w3 (SwiGLU width 341 here) are not held for the backward
+        assert n.wparams is None and n.sparams is None and n.direct is False
+
+
+def test_block_gradients_are_returned_by_argument_name():
+    import inspect
+    from ldmae_amd.models import lightningdit as L
+    params = list(inspect.signature(L._DiTBlockFn.forward).parameters)
+    assert params[0] == "ctx" and params[-1] == "gemm_precision"      # forward-only: never reaches a backward
+    assert len(L._BLOCK_ARGS) == 31 and list(L._BLOCK_ARGS) == params[1:-1]
+    assert set(L._BLOCK_SMALL) <= set(L._BLOCK_ARGS)
+
+
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 def test_training_backward_is_the_earlier_code_path(prec, monkeypatch):
     """Mode off: dx and every parameter gradient of a training-style backward have the bits of the three backward passes as they stood before
