@@ -52,79 +52,9 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_kernel(const float* __res
                                                               const float* __restrict__ shift, const float* __restrict__ scale,
                                                               int mod_ld, OutT* __restrict__ out, float* __restrict__ rstd, int M, int D,
                                                               int rpb, float eps, int center = 0) {
-  // center (guarded form only): LayerNorm WITHOUT affine parameters (the use_rmsnorm=False blocks, lightningdit.py:200-201) = the RMS norm of
-  // the centred row, w = NULL -> 1: y = (x - mean) * rsqrt(mean((x - mean)^2) + eps) * (1 + scale) + shift
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nch = D >> 2;
-  float4 wv[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) { const int c = lane + 64 * i; wv[i] = c < nch ? (w ? *(const float4*)(w + 4 * c) : f4(1.f)) : f4(0.f); }
-  if constexpr (FULL) {
-    const int m0 = (blockIdx.x * 4 + wave) * 4, b = m0 / rpb;
-    float4 sc1[NCH], sh[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      sc1[i] = scale ? f4(1.f) + *(const float4*)(scale + (size_t)b * mod_ld + 4 * lane + 256 * i) : f4(1.f);
-      sh[i] = shift ? *(const float4*)(shift + (size_t)b * mod_ld + 4 * lane + 256 * i) : f4(0.f);
-    }
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + r;
-      float4 xv[NCH];
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) xv[i] = *(const float4*)(x + (size_t)m * D + 4 * lane + 256 * i);
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) ss += hsum(xv[i] * xv[i]);
-      ss = wave_sum(ss);
-      const float rs = rsqrtf(ss / (float)D + eps);
-      if (lane == 0 && rstd) rstd[m] = rs;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        float4 y = (xv[i] * rs) * wv[i];
-        if (scale) y = y * sc1[i];
-        if (shift) y = y + sh[i];
-        store4<OutT>(out + (size_t)m * D + 4 * lane + 256 * i, y);
-      }
-    }
-    return;
-  }
-  for (int r = 0; r < 4; ++r) {
-    const int m = (blockIdx.x * 4 + wave) * 4 + r;
-    if (m >= M) return;
-    const int b = m / rpb;
-    float4 xv[NCH];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int c = lane + 64 * i;
-      xv[i] = c < nch ? *(const float4*)(x + (size_t)m * D + 4 * c) : f4(0.f);
-      ss += hsum(xv[i] * xv[i]);
-    }
-    if (center) {
-      float s1 = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) s1 += hsum(xv[i]);
-      const float mean = wave_sum(s1) / (float)D;
-      ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        if (lane + 64 * i < nch) xv[i] = xv[i] - f4(mean);
-        ss += hsum(xv[i] * xv[i]);
-      }
-    }
-    ss = wave_sum(ss);
-    const float rs = rsqrtf(ss / (float)D + eps);
-    if (lane == 0 && rstd) rstd[m] = rs;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        float4 y = (xv[i] * rs) * wv[i];
-        if (scale) y = y * (f4(1.f) + *(const float4*)(scale + (size_t)b * mod_ld + 4 * c));
-        if (shift) y = y + *(const float4*)(shift + (size_t)b * mod_ld + 4 * c);
-        store4<OutT>(out + (size_t)m * D + 4 * c, y);
-      }
-    }
-  }
+#define NORM_EMIT(m, a, b, y) store4<OutT>(out + (size_t)(m) * D + (a) + (b), y)
+#include "norm_mod_rows.inc"
+#undef NORM_EMIT
 }
 
 // x^2 + y^2 + z^2 + w^2 with the roundings the GUARDED form of rmsnorm_mod_fwd_kernel has.  Its `ss += hsum(xv * xv)` sits in a loop of
@@ -142,7 +72,8 @@ template <bool FMA> __device__ __forceinline__ float sumsq4_guarded(float4 a) {
 // The gated residual(s) in front of the norm, formed in registers: r = gate_res4(x, gate_a[b], ya), then r = gate_res4(r, gate_b[b], yb) when
 // yb is given (the second residual of a block, whose first was never stored).  r is written to xout (f32) and / or normalised + modulated into
 // `out` exactly as rmsnorm_mod_fwd_kernel does with a row it loads: same row-to-wave mapping, same order of the sum of squares, same output
-// arithmetic, statement for statement -- xout / out / rstd have the bits of the EPI_GATE_RES epilogue followed by that kernel.  ya / yb are the
+// arithmetic, following norm_mod_rows.inc statement for statement (its load half and sumsq4_guarded differ by design, so it does not
+// include that text) -- xout / out / rstd have the bits of the EPI_GATE_RES epilogue followed by that kernel.  ya / yb are the
 // branch outputs AS STORED in the activation type (what the epilogue adds).  Everything a row needs from HBM is requested before its first use.
 template <int NCH, typename T, bool FULL = false>
 __global__ __launch_bounds__(256) void res_rmsnorm_mod_fwd_kernel(const float* __restrict__ x, const T* __restrict__ ya,
@@ -236,11 +167,39 @@ __global__ __launch_bounds__(256) void res_rmsnorm_mod_fwd_kernel(const float* _
   }
 }
 
+// ------------------------------------------------------------------ shared by the backward row kernels
+// a float4 AS STORED in the activation type: rounded to T and widened again
+template <typename T> __device__ __forceinline__ float4 as_stored(float4 d) {
+  return make_float4(to_f<T>(from_f<T>(d.x)), to_f<T>(from_f<T>(d.y)), to_f<T>(from_f<T>(d.z)), to_f<T>(from_f<T>(d.w)));
+}
+// The gated-residual backward of four channels of one row, written once for gate_bwd_kernel and for the GATE tail of rmsnorm_mod_bwd_kernel
+// (which promises that kernel's bits): g is the gradient of the residual stream, gv the gate, y4 the expression that loads the branch output
+// (evaluated only where the gate gradient is wanted).  acc_g += g * y;  dy = g * gate, rounded to T and stored;  acc_b += dy AS STORED --
+// the bias gradient of the Linear that produced the branch = column sums of dy as the weight-gradient GEMM reads it, formed here while the
+// values are in registers instead of inside the TN GEMM.  mul_rn: never contracted into the bias sum.
+#define GATE_BWD_TAIL(T, want_g, want_b, acc_g, acc_b, g, y4, gv, dyp) do { \
+    if (want_g) acc_g = acc_g + (g) * (y4); \
+    const float4 d_ = mul_rn(g, gv); \
+    store4<T>(dyp, d_); \
+    if (want_b) acc_b = acc_b + as_stored<T>(d_); \
+  } while (0)
+// The flush of a workgroup's accumulators into its partial row(s).  WAVE_SETS_TO_LDS(WAVE_SET(N, 0, a) ... WAVE_SET(N, N - 1, z)): the N
+// per-wave accumulator sets go to LDS as red[wave][set][D] (a lane holds columns 4 * (lane + 64 * i) .. + 3 of chunk i), then a barrier;
+// WAVE_SETS_SUM(N, k, i) is element i of set k summed over the four waves in the fixed order (w0 + w1) + (w2 + w3).  Macros over the
+// kernel's own red / lane / wave / nch / D: as __forceinline__ functions they changed the compiled code of every kernel that used them
+// (register allocation, and the descriptor of the wide ones), and these kernels are pinned to each other bitwise.
+#define WAVE_SET(N, k, acc) *(float4*)(red + (wave * N + k) * D + 4 * c) = acc[i];
+#define WAVE_SETS_TO_LDS(SETS) do { \
+    _Pragma("unroll") for (int i = 0; i < NCH; ++i) { const int c = lane + 64 * i; if (c < nch) { SETS } } \
+    __syncthreads(); \
+  } while (0)
+#define WAVE_SETS_SUM(N, k, i) ((red[(k) * D + (i)] + red[(N + (k)) * D + (i)]) + (red[(2 * N + (k)) * D + (i)] + red[(3 * N + (k)) * D + (i)]))
+
 // partials P[wg][3][D] = {sum dout, sum dout*y, sum dy*n} over the workgroup's rows (one sample)
 // GATE: the gated-residual backward of the branch BELOW this norm (the attention branch under norm2) rides along: the updated residual
 // gradient is consumed while it is in registers -- dy = dx_new * gate[b] (rounded to T), dgate partials sum dx_new * y, bias-gradient
 // partials sum dy -- instead of being re-read by a separate gate_bwd pass (805 MB per block).  Same arithmetic, same partial layout
-// and same summation order as gate_bwd_kernel.
+// and same summation order as gate_bwd_kernel: both use GATE_BWD_TAIL and the WAVE_SETS_* flush above.
 // RECOMP (GATE only): `x` is the residual stream BEFORE the gated residual under this norm and the row that was normalised is rebuilt in
 // registers, gate_res4(x, gate[b], y) -- the very expression that formed it in the forward (res_rmsnorm_mod_fwd_kernel) -- from the y row and
 // the gate constants this kernel reads anyway: that row never has to be stored.  Only the source of the f32 row changes.
@@ -322,12 +281,7 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_bwd_kernel(const T* __restric
         const float4 d0 = (dn[i] - nv[i] * dot) * rs;
         const float4 gn = ga.dx_overwrite ? d0 : dold[i] + d0;
         *(float4*)(dx + ro + 256 * i) = gn;
-        if constexpr (GATE) {
-          a_g[i] = a_g[i] + gn * yv[i];
-          const float4 d = mul_rn(gn, *(const float4*)(cg + 4 * c));
-          store4<T>(gdy + ro + 256 * i, d);
-          a_b[i] = a_b[i] + make_float4(to_f<T>(from_f<T>(d.x)), to_f<T>(from_f<T>(d.y)), to_f<T>(from_f<T>(d.z)), to_f<T>(from_f<T>(d.w)));
-        }
+        if constexpr (GATE) GATE_BWD_TAIL(T, true, true, a_g[i], a_b[i], gn, yv[i], *(const float4*)(cg + 4 * c), gdy + ro + 256 * i);
       }
     }
   } else
@@ -379,39 +333,20 @@ __global__ __launch_bounds__(256) void rmsnorm_mod_bwd_kernel(const T* __restric
         const float4 d0 = ((dn[i] - nv[i] * dot) - f4(msum)) * rs;
         const float4 g = ga.dx_overwrite ? d0 : *(const float4*)p + d0;        // beta_x = 0: dx is written, not read (no memset by the caller)
         *(float4*)p = g;
-        if constexpr (GATE) {
-          a_g[i] = a_g[i] + g * load4<T>(gy + (size_t)m * D + 4 * c);
-          const float4 d = mul_rn(g, *(const float4*)(cg + 4 * c));
-          store4<T>(gdy + (size_t)m * D + 4 * c, d);
-          a_b[i] = a_b[i] + make_float4(to_f<T>(from_f<T>(d.x)), to_f<T>(from_f<T>(d.y)), to_f<T>(from_f<T>(d.z)), to_f<T>(from_f<T>(d.w)));
-        }
+        if constexpr (GATE)
+          GATE_BWD_TAIL(T, true, true, a_g[i], a_b[i], g, load4<T>(gy + (size_t)m * D + 4 * c), *(const float4*)(cg + 4 * c), gdy + (size_t)m * D + 4 * c);
       }
     }
   }
   if constexpr (GATE) __syncthreads();            // every wave is done with the constants: the region becomes reduction scratch
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      *(float4*)(red + (wave * 3 + 0) * D + 4 * c) = a_sh[i];
-      *(float4*)(red + (wave * 3 + 1) * D + 4 * c) = a_sc[i];
-      *(float4*)(red + (wave * 3 + 2) * D + 4 * c) = a_w[i];
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * D; i += 256)
-    P[(size_t)blockIdx.x * 3 * D + i] = (red[i] + red[3 * D + i]) + (red[6 * D + i] + red[9 * D + i]);
+  WAVE_SETS_TO_LDS(WAVE_SET(3, 0, a_sh) WAVE_SET(3, 1, a_sc) WAVE_SET(3, 2, a_w));
+  for (int i = threadIdx.x; i < 3 * D; i += 256) P[(size_t)blockIdx.x * 3 * D + i] = WAVE_SETS_SUM(3, 0, i);
   if constexpr (GATE) {
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) { *(float4*)(red + (wave * 2 + 0) * D + 4 * c) = a_g[i]; *(float4*)(red + (wave * 2 + 1) * D + 4 * c) = a_b[i]; }
-    }
-    __syncthreads();
+    WAVE_SETS_TO_LDS(WAVE_SET(2, 0, a_g) WAVE_SET(2, 1, a_b));
     for (int i = threadIdx.x; i < D; i += 256) {
-      ga.Pg[(size_t)blockIdx.x * D + i] = (red[i] + red[2 * D + i]) + (red[4 * D + i] + red[6 * D + i]);
-      ga.Pb[(size_t)blockIdx.x * D + i] = (red[D + i] + red[3 * D + i]) + (red[5 * D + i] + red[7 * D + i]);
+      ga.Pg[(size_t)blockIdx.x * D + i] = WAVE_SETS_SUM(2, 0, i);
+      ga.Pb[(size_t)blockIdx.x * D + i] = WAVE_SETS_SUM(2, 1, i);
     }
   }
 }
@@ -528,34 +463,42 @@ extern "C" long ldmae_rmsnorm_modulate_bwd_workspace_bytes(int M, int D, int row
 }
 
 
-static int rmsnorm_modulate_bwd_core(int dtype, const void* dout, const float* x, const float* w, const float* scale, int mod_ld,
-                                     const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, float* dw,
-                                     float beta_w, int M, int D, int rows_per_batch, float* workspace, const GateBwdArgs* gate,
-                                     float* dgate, int dgate_ld, float* dbias, void* stream, int center = 0) {
-  LDMAE_REQUIRE(dout && x && (w || center) && rstd && dx_accum && (dw || center) && workspace, "rmsnorm_modulate_bwd: null pointer");
+// What the five backward entries hand to rmsnorm_modulate_bwd_core, by name (w / dw null + center: the LayerNorm form; gated: ga.y / gate /
+// gate_ld / dy and dgate / dgate_ld / dbias are set, by norm_bwd_gate_args)
+struct NormBwdArgs {
+  int dtype; const void* dout; const float* x; const float* w; const float* scale; int mod_ld; const float* rstd;
+  float* dx_accum; float beta_x; float* dshift; float* dscale; int dmod_ld; float* dw; float beta_w;
+  int M, D, rows_per_batch; float* workspace; void* stream; int center;
+  bool gated; GateBwdArgs ga; float* dgate; int dgate_ld; float* dbias;
+};
+static int rmsnorm_modulate_bwd_core(const NormBwdArgs& a) {
+  const int dtype = a.dtype, M = a.M, D = a.D, rows_per_batch = a.rows_per_batch, center = a.center;
+  const bool gate = a.gated;
+  float* dw = a.dw;
+  LDMAE_REQUIRE(a.dout && a.x && (a.w || center) && a.rstd && a.dx_accum && (dw || center) && a.workspace, "rmsnorm_modulate_bwd: null pointer");
   LDMAE_REQUIRE(D % 4 == 0 && M > 0 && rows_per_batch > 0 && M % rows_per_batch == 0, "rmsnorm_modulate_bwd: bad shape M=%d D=%d rpb=%d", M, D, rows_per_batch);
   const int rw = pick_rows_per_wg(rows_per_batch);
   LDMAE_REQUIRE(rw > 0, "rmsnorm_modulate_bwd: rows_per_batch=%d must be a multiple of 4", rows_per_batch);
-  hipStream_t st = as_stream(stream);
+  hipStream_t st = as_stream(a.stream);
   const int G = M / rw, B = M / rows_per_batch, gps = rows_per_batch / rw;
-  float* P = workspace;
-  float* dwb = workspace + (size_t)G * 3 * D;
+  float* P = a.workspace;
+  float* dwb = a.workspace + (size_t)G * 3 * D;
   float* gws = dwb + (size_t)B * D;                     // gate partials (fused form): [G][D] dgate, [G][D] bias, colsum scratch
   const size_t lds = (size_t)4 * 3 * D * sizeof(float);
-  LDMAE_REQUIRE(beta_x == 0.f || beta_x == 1.f, "rmsnorm_modulate_bwd: beta_x must be 0 (write dx) or 1 (accumulate into dx)");
-  GateBwdArgs ga{nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0};
-  if (gate) { ga = *gate; ga.Pg = gws; ga.Pb = gws + (size_t)G * D; }
-  ga.dx_overwrite = beta_x == 0.f;
+  LDMAE_REQUIRE(a.beta_x == 0.f || a.beta_x == 1.f, "rmsnorm_modulate_bwd: beta_x must be 0 (write dx) or 1 (accumulate into dx)");
+  GateBwdArgs ga = a.ga;
+  if (gate) { ga.Pg = gws; ga.Pb = gws + (size_t)G * D; }
+  ga.dx_overwrite = a.beta_x == 0.f;
   ga.center = center;
   if (center && !dw) dw = P;             // LayerNorm without affine parameters: no weight gradient; the last reduce (stream-ordered behind the consumers of P) writes its [D] sums there
-  const bool recomp = gate && gate->recompute, full = D % 256 == 0 && !center;                 // both bf16 only
+  const bool recomp = gate && ga.recompute, full = D % 256 == 0 && !center;                 // both bf16 only
   LDMAE_REQUIRE(!recomp || (dtype == LDMAE_BF16 && !center), "rmsnorm_modulate_bwd_gate_recompute: bf16 activations and the RMSNorm form only");
   int rc = LDMAE_OK;
   auto go = [&](auto t) {
     using T = tag_t<decltype(t)>;
     rc = row_nch_dispatch(D, [&](auto nch) {
       constexpr int NCH = decltype(nch)::value;
-      auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(G), dim3(256), lds, st, (const T*)dout, x, w, scale, mod_ld, rstd, dx_accum, P, M, D, rows_per_batch, rw, ga); };
+      auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(G), dim3(256), lds, st, (const T*)a.dout, a.x, a.w, a.scale, a.mod_ld, a.rstd, a.dx_accum, P, M, D, rows_per_batch, rw, ga); };
       if constexpr (__is_same(T, bf16)) {
         if (recomp) { if (full) launch(rmsnorm_mod_bwd_kernel<NCH, bf16, true, true, true>); else launch(rmsnorm_mod_bwd_kernel<NCH, bf16, true, false, true>); return; }
         if (full) { if (gate) launch(rmsnorm_mod_bwd_kernel<NCH, bf16, true, true>); else launch(rmsnorm_mod_bwd_kernel<NCH, bf16, false, true>); return; }
@@ -568,23 +511,37 @@ static int rmsnorm_modulate_bwd_core(int dtype, const void* dout, const float* x
   LDMAE_CHECK_LAUNCH("rmsnorm_modulate_bwd");
   if (gate) {        // two launches: every per-sample sum, then dw and dbias over the samples together
     float* dbb = ga.Pb + (size_t)G * D;                 // [B][D], behind the gate partials (ldmae_gate_bwd_workspace_bytes reserves it)
-    hipLaunchKernelGGL(mod_partials_reduce_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, P, D, gps, dshift, dscale, dmod_ld, dwb,
-                       (const float*)ga.Pg, dgate, dgate_ld, (const float*)ga.Pb, dbb);
-    group_reduce(dwb, D, 1, D, B, dw, D, beta_w, st, dbb, dbias, 0.f);
+    hipLaunchKernelGGL(mod_partials_reduce_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, P, D, gps, a.dshift, a.dscale, a.dmod_ld, dwb,
+                       (const float*)ga.Pg, a.dgate, a.dgate_ld, (const float*)ga.Pb, dbb);
+    group_reduce(dwb, D, 1, D, B, dw, D, a.beta_w, st, dbb, a.dbias, 0.f);
     LDMAE_CHECK_LAUNCH("rmsnorm_modulate_bwd_gate reduce");
     return LDMAE_OK;
   }
-  hipLaunchKernelGGL(mod_partials_reduce_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, P, D, gps, dshift, dscale, dmod_ld, dwb);
-  group_reduce(dwb, D, 1, D, B, dw, D, beta_w, st);
+  hipLaunchKernelGGL(mod_partials_reduce_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, P, D, gps, a.dshift, a.dscale, a.dmod_ld, dwb);
+  group_reduce(dwb, D, 1, D, B, dw, D, a.beta_w, st);
   LDMAE_CHECK_LAUNCH("rmsnorm_modulate_bwd reduce");
+  return LDMAE_OK;
+}
+// the gate half of the three "_gate" entries: their two refusals, in the entry's name, then the fields
+static int norm_bwd_gate_args(NormBwdArgs& a, const char* entry, const void* y, const float* gate, int gate_ld, void* dy, float* dgate,
+                              int dgate_ld, float* dbias) {
+  LDMAE_REQUIRE(y && gate && dy && dgate && dbias, "%s: null pointer", entry);
+  LDMAE_REQUIRE(gate_ld % 4 == 0, "%s: gate_ld=%d must be a multiple of 4", entry, gate_ld);
+  a.gated = true;
+  a.ga.y = y; a.ga.gate = gate; a.ga.gate_ld = gate_ld; a.ga.dy = dy;
+  a.dgate = dgate; a.dgate_ld = dgate_ld; a.dbias = dbias;
   return LDMAE_OK;
 }
 
 extern "C" int ldmae_rmsnorm_modulate_bwd(int dtype, const void* dout, const float* x, const float* w, const float* scale, int mod_ld,
                                           const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, float* dw,
                                           float beta_w, int M, int D, int rows_per_batch, float* workspace, void* stream) {
-  return rmsnorm_modulate_bwd_core(dtype, dout, x, w, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, dw, beta_w, M, D, rows_per_batch,
-                                   workspace, nullptr, nullptr, 0, nullptr, stream);
+  NormBwdArgs a{};
+  a.dtype = dtype; a.dout = dout; a.x = x; a.scale = scale; a.mod_ld = mod_ld; a.rstd = rstd; a.dx_accum = dx_accum; a.beta_x = beta_x;
+  a.dshift = dshift; a.dscale = dscale; a.dmod_ld = dmod_ld; a.M = M; a.D = D; a.rows_per_batch = rows_per_batch;
+  a.workspace = workspace; a.stream = stream;
+  a.w = w; a.dw = dw; a.beta_w = beta_w;
+  return rmsnorm_modulate_bwd_core(a);
 }
 
 extern "C" long ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes(int M, int D, int rows_per_batch) {
@@ -597,11 +554,13 @@ extern "C" int ldmae_rmsnorm_modulate_bwd_gate(int dtype, const void* dout, cons
                                                const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, float* dw,
                                                float beta_w, const void* y, const float* gate, int gate_ld, void* dy, float* dgate,
                                                int dgate_ld, float* dbias, int M, int D, int rows_per_batch, float* workspace, void* stream) {
-  LDMAE_REQUIRE(y && gate && dy && dgate && dbias, "rmsnorm_modulate_bwd_gate: null pointer");
-  LDMAE_REQUIRE(gate_ld % 4 == 0, "rmsnorm_modulate_bwd_gate: gate_ld=%d must be a multiple of 4", gate_ld);
-  const GateBwdArgs ga{y, gate, gate_ld, dy, nullptr, nullptr, 0, 0};
-  return rmsnorm_modulate_bwd_core(dtype, dout, x, w, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, dw, beta_w, M, D, rows_per_batch,
-                                   workspace, &ga, dgate, dgate_ld, dbias, stream);
+  NormBwdArgs a{};
+  a.dtype = dtype; a.dout = dout; a.x = x; a.scale = scale; a.mod_ld = mod_ld; a.rstd = rstd; a.dx_accum = dx_accum; a.beta_x = beta_x;
+  a.dshift = dshift; a.dscale = dscale; a.dmod_ld = dmod_ld; a.M = M; a.D = D; a.rows_per_batch = rows_per_batch;
+  a.workspace = workspace; a.stream = stream;
+  a.w = w; a.dw = dw; a.beta_w = beta_w;
+  if (int rc = norm_bwd_gate_args(a, "rmsnorm_modulate_bwd_gate", y, gate, gate_ld, dy, dgate, dgate_ld, dbias)) return rc;
+  return rmsnorm_modulate_bwd_core(a);
 }
 // ldmae_rmsnorm_modulate_bwd_gate for a norm whose input row was never stored: `x` is the residual stream BEFORE the gated residual under
 // the norm and the kernel rebuilds the normalised row as x + gate[b] * y (RECOMP above).  Every output has the bits ldmae_rmsnorm_modulate_bwd_gate
@@ -610,29 +569,38 @@ extern "C" int ldmae_rmsnorm_modulate_bwd_gate_recompute(int dtype, const void* 
                                                          const float* rstd, float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld,
                                                          float* dw, float beta_w, const void* y, const float* gate, int gate_ld, void* dy, float* dgate,
                                                          int dgate_ld, float* dbias, int M, int D, int rows_per_batch, float* workspace, void* stream) {
-  LDMAE_REQUIRE(y && gate && dy && dgate && dbias, "rmsnorm_modulate_bwd_gate_recompute: null pointer");
-  LDMAE_REQUIRE(gate_ld % 4 == 0, "rmsnorm_modulate_bwd_gate_recompute: gate_ld=%d must be a multiple of 4", gate_ld);
-  const GateBwdArgs ga{y, gate, gate_ld, dy, nullptr, nullptr, 0, 0, 1};
-  return rmsnorm_modulate_bwd_core(dtype, dout, x, w, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, dw, beta_w, M, D, rows_per_batch,
-                                   workspace, &ga, dgate, dgate_ld, dbias, stream);
+  NormBwdArgs a{};
+  a.dtype = dtype; a.dout = dout; a.x = x; a.scale = scale; a.mod_ld = mod_ld; a.rstd = rstd; a.dx_accum = dx_accum; a.beta_x = beta_x;
+  a.dshift = dshift; a.dscale = dscale; a.dmod_ld = dmod_ld; a.M = M; a.D = D; a.rows_per_batch = rows_per_batch;
+  a.workspace = workspace; a.stream = stream;
+  a.w = w; a.dw = dw; a.beta_w = beta_w;
+  if (int rc = norm_bwd_gate_args(a, "rmsnorm_modulate_bwd_gate_recompute", y, gate, gate_ld, dy, dgate, dgate_ld, dbias)) return rc;
+  a.ga.recompute = 1;
+  return rmsnorm_modulate_bwd_core(a);
 }
 // The LayerNorm(elementwise_affine=False) forms of the two entry points above (use_rmsnorm=False blocks): same arguments without w / dw, same
 // workspaces (ldmae_rmsnorm_modulate_bwd(_gate)_workspace_bytes).
 extern "C" int ldmae_layernorm_modulate_bwd(int dtype, const void* dout, const float* x, const float* scale, int mod_ld, const float* rstd,
                                             float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, int M, int D, int rows_per_batch,
                                             float* workspace, void* stream) {
-  return rmsnorm_modulate_bwd_core(dtype, dout, x, nullptr, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, nullptr, 0.f, M, D, rows_per_batch,
-                                   workspace, nullptr, nullptr, 0, nullptr, stream, 1);
+  NormBwdArgs a{};
+  a.dtype = dtype; a.dout = dout; a.x = x; a.scale = scale; a.mod_ld = mod_ld; a.rstd = rstd; a.dx_accum = dx_accum; a.beta_x = beta_x;
+  a.dshift = dshift; a.dscale = dscale; a.dmod_ld = dmod_ld; a.M = M; a.D = D; a.rows_per_batch = rows_per_batch;
+  a.workspace = workspace; a.stream = stream;
+  a.center = 1;
+  return rmsnorm_modulate_bwd_core(a);
 }
 extern "C" int ldmae_layernorm_modulate_bwd_gate(int dtype, const void* dout, const float* x, const float* scale, int mod_ld, const float* rstd,
                                                  float* dx_accum, float beta_x, float* dshift, float* dscale, int dmod_ld, const void* y, const float* gate,
                                                  int gate_ld, void* dy, float* dgate, int dgate_ld, float* dbias, int M, int D, int rows_per_batch,
                                                  float* workspace, void* stream) {
-  LDMAE_REQUIRE(y && gate && dy && dgate && dbias, "layernorm_modulate_bwd_gate: null pointer");
-  LDMAE_REQUIRE(gate_ld % 4 == 0, "layernorm_modulate_bwd_gate: gate_ld=%d must be a multiple of 4", gate_ld);
-  const GateBwdArgs ga{y, gate, gate_ld, dy, nullptr, nullptr, 0, 1};
-  return rmsnorm_modulate_bwd_core(dtype, dout, x, nullptr, scale, mod_ld, rstd, dx_accum, beta_x, dshift, dscale, dmod_ld, nullptr, 0.f, M, D, rows_per_batch,
-                                   workspace, &ga, dgate, dgate_ld, dbias, stream, 1);
+  NormBwdArgs a{};
+  a.dtype = dtype; a.dout = dout; a.x = x; a.scale = scale; a.mod_ld = mod_ld; a.rstd = rstd; a.dx_accum = dx_accum; a.beta_x = beta_x;
+  a.dshift = dshift; a.dscale = dscale; a.dmod_ld = dmod_ld; a.M = M; a.D = D; a.rows_per_batch = rows_per_batch;
+  a.workspace = workspace; a.stream = stream;
+  a.center = 1;
+  if (int rc = norm_bwd_gate_args(a, "layernorm_modulate_bwd_gate", y, gate, gate_ld, dy, dgate, dgate_ld, dbias)) return rc;
+  return rmsnorm_modulate_bwd_core(a);
 }
 
 // ------------------------------------------------------------------ gated residual backward
@@ -658,27 +626,18 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
       const int c = lane + 64 * i;
       if (c < nch) {
         const float4 g = *(const float4*)(dxo + (size_t)m * D + 4 * c);
-        if (P) acc[i] = acc[i] + g * load4<T>(y + (size_t)m * D + 4 * c);
-        const float4 d = mul_rn(g, gv[i]);       // never contracted into the bias sum below: that sum is over the values AS STORED
-        store4<T>(dy + (size_t)m * D + 4 * c, d);
-        // bias gradient of the Linear that produced the branch = column sums of dy AS STORED (rounded to T: what the weight-
-        // gradient GEMM reads), formed here while the values are in registers instead of inside the TN GEMM
-        if (Pb) accb[i] = accb[i] + make_float4(to_f<T>(from_f<T>(d.x)), to_f<T>(from_f<T>(d.y)), to_f<T>(from_f<T>(d.z)), to_f<T>(from_f<T>(d.w)));
+        GATE_BWD_TAIL(T, P, Pb, acc[i], accb[i], g, load4<T>(y + (size_t)m * D + 4 * c), gv[i], dy + (size_t)m * D + 4 * c);
       }
     }
   }
   if (P) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) { const int c = lane + 64 * i; if (c < nch) *(float4*)(red + wave * D + 4 * c) = acc[i]; }
-    __syncthreads();
-    for (int i = threadIdx.x; i < D; i += 256) P[(size_t)blockIdx.x * D + i] = (red[i] + red[D + i]) + (red[2 * D + i] + red[3 * D + i]);
+    WAVE_SETS_TO_LDS(WAVE_SET(1, 0, acc));
+    for (int i = threadIdx.x; i < D; i += 256) P[(size_t)blockIdx.x * D + i] = WAVE_SETS_SUM(1, 0, i);
     __syncthreads();
   }
   if (Pb) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) { const int c = lane + 64 * i; if (c < nch) *(float4*)(red + wave * D + 4 * c) = accb[i]; }
-    __syncthreads();
-    for (int i = threadIdx.x; i < D; i += 256) Pb[(size_t)blockIdx.x * D + i] = (red[i] + red[D + i]) + (red[2 * D + i] + red[3 * D + i]);
+    WAVE_SETS_TO_LDS(WAVE_SET(1, 0, accb));
+    for (int i = threadIdx.x; i < D; i += 256) Pb[(size_t)blockIdx.x * D + i] = WAVE_SETS_SUM(1, 0, i);
   }
 }
 extern "C" long ldmae_gate_bwd_workspace_bytes(int M, int D, int rows_per_batch) {

@@ -117,85 +117,16 @@ __device__ __forceinline__ void mx8_norm_emit(float4 y, bool inr, int lane, uint
   }
 }
 
-// (the text of rmsnorm_mod_fwd_kernel, `center` path included: the compiler's contraction choices in the sum of squares depend on it)
+// (norm_mod_rows.inc is the body of rmsnorm_mod_fwd_kernel, `center` path included: the compiler's contraction choices in the sum of squares
+// depend on it.  Only what becomes of the modulated values differs: NORM_EMIT hands them, with their float4 chunk index, to the quantiser)
 template <int NCH, bool FULL = false>
 __global__ __launch_bounds__(256) void rmsnorm_mod_fwd_mx8_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ shift, const float* __restrict__ scale,
                                                               int mod_ld, uint8_t* __restrict__ q, uint8_t* __restrict__ sc, float* __restrict__ rstd, int M, int D,
                                                               int rpb, float eps, int center = 0) {
-  // center (guarded form only): LayerNorm WITHOUT affine parameters (the use_rmsnorm=False blocks, lightningdit.py:200-201) = the RMS norm of
-  // the centred row, w = NULL -> 1: y = (x - mean) * rsqrt(mean((x - mean)^2) + eps) * (1 + scale) + shift
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nch = D >> 2;
-  float4 wv[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) { const int c = lane + 64 * i; wv[i] = c < nch ? (w ? *(const float4*)(w + 4 * c) : f4(1.f)) : f4(0.f); }
-  if constexpr (FULL) {
-    const int m0 = (blockIdx.x * 4 + wave) * 4, b = m0 / rpb;
-    float4 sc1[NCH], sh[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      sc1[i] = scale ? f4(1.f) + *(const float4*)(scale + (size_t)b * mod_ld + 4 * lane + 256 * i) : f4(1.f);
-      sh[i] = shift ? *(const float4*)(shift + (size_t)b * mod_ld + 4 * lane + 256 * i) : f4(0.f);
-    }
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + r;
-      float4 xv[NCH];
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) xv[i] = *(const float4*)(x + (size_t)m * D + 4 * lane + 256 * i);
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) ss += hsum(xv[i] * xv[i]);
-      ss = wave_sum(ss);
-      const float rs = rsqrtf(ss / (float)D + eps);
-      if (lane == 0 && rstd) rstd[m] = rs;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        float4 y = (xv[i] * rs) * wv[i];
-        if (scale) y = y * sc1[i];
-        if (shift) y = y + sh[i];
-        mx8_norm_emit(y, true, lane, q + (size_t)m * D, sc + (size_t)m * (D >> 5), lane + 64 * i);
-      }
-    }
-    return;
-  }
-  for (int r = 0; r < 4; ++r) {
-    const int m = (blockIdx.x * 4 + wave) * 4 + r;
-    if (m >= M) return;
-    const int b = m / rpb;
-    float4 xv[NCH];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int c = lane + 64 * i;
-      xv[i] = c < nch ? *(const float4*)(x + (size_t)m * D + 4 * c) : f4(0.f);
-      ss += hsum(xv[i] * xv[i]);
-    }
-    if (center) {
-      float s1 = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) s1 += hsum(xv[i]);
-      const float mean = wave_sum(s1) / (float)D;
-      ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i) {
-        if (lane + 64 * i < nch) xv[i] = xv[i] - f4(mean);
-        ss += hsum(xv[i] * xv[i]);
-      }
-    }
-    ss = wave_sum(ss);
-    const float rs = rsqrtf(ss / (float)D + eps);
-    if (lane == 0 && rstd) rstd[m] = rs;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int c = lane + 64 * i;
-      if (c < nch) {
-        float4 y = (xv[i] * rs) * wv[i];
-        if (scale) y = y * (f4(1.f) + *(const float4*)(scale + (size_t)b * mod_ld + 4 * c));
-        if (shift) y = y + *(const float4*)(shift + (size_t)b * mod_ld + 4 * c);
-        mx8_norm_emit(y, true, lane, q + (size_t)m * D, sc + (size_t)m * (D >> 5), c);
-      }
-    }
-  }
+#define NORM_EMIT(m, a, b, y) mx8_norm_emit(y, true, lane, q + (size_t)(m) * D, sc + (size_t)(m) * (D >> 5), ((a) + (b)) >> 2)
+#include "norm_mod_rows.inc"
+#undef NORM_EMIT
 }
 
 extern "C" int ldmae_rmsnorm_modulate_fwd_mx8(const float* x, const float* w, const float* shift, const float* scale, int mod_ld, void* q,

@@ -113,6 +113,11 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def _mod_ld(a, b=None):
+    """Row stride of a modulation pair, (shift, scale) or (dshift, dscale) -- [B, D] views of one tensor: the first one given, 0 with neither."""
+    return a.stride(0) if a is not None else (b.stride(0) if b is not None else 0)
+
+
 def _pair(a, b, what):
     """The two operands of an NT product: same dtype, same K; both read as rows."""
     if b.dtype != a.dtype or a.dim() != 2 or b.dim() != 2 or b.shape[1] != a.shape[1]:
@@ -357,7 +362,7 @@ def rmsnorm_modulate_fwd_mx8(x, w, shift, scale, rows_per_batch, eps=1e-6):
     q = torch.empty(M, D, dtype=torch.uint8, device=x.device)
     sc = torch.empty(M, D // 32, dtype=torch.uint8, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    ld = shift.stride(0) if shift is not None else (scale.stride(0) if scale is not None else 0)
+    ld = _mod_ld(shift, scale)
     call("ldmae_rmsnorm_modulate_fwd_mx8", ptr(x), ptr(w), ptr(shift), ptr(scale), ld, ptr(q), ptr(sc), ptr(rstd), M, D, rows_per_batch, eps, stream())
     return q, sc, rstd
 
@@ -596,7 +601,7 @@ def rmsnorm_modulate_fwd(x, w, shift, scale, rows_per_batch, out_dtype, eps=1e-6
     M, D = x.shape
     out = torch.empty(M, D, dtype=out_dtype, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    ld = shift.stride(0) if shift is not None else (scale.stride(0) if scale is not None else 0)
+    ld = _mod_ld(shift, scale)
     if w is None:
         call("ldmae_layernorm_modulate_fwd", dt(out_dtype), ptr(x), ptr(shift), ptr(scale), ld, ptr(out), ptr(rstd), M, D, rows_per_batch, eps, stream())
         return out, rstd
@@ -630,53 +635,47 @@ def res_rmsnorm_modulate_fwd(x, ya, gate_a, yb=None, gate_b=None, w=None, shift=
     if want_norm:
         out = torch.empty(M, D, dtype=ya.dtype, device=x.device)
         rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        ld = shift.stride(0) if shift is not None else (scale.stride(0) if scale is not None else 0)
+        ld = _mod_ld(shift, scale)
     call("ldmae_res_rmsnorm_modulate_fwd", dt(ya.dtype), ptr(x), ptr(ya), ptr(gate_a), _ld(gate_a), ptr(yb), ptr(gate_b),
          _ld(gate_b) if gate_b is not None else 0, ptr(xout), ptr(w) if want_norm else None, ptr(shift) if want_norm else None,
          ptr(scale) if want_norm else None, ld, ptr(out), ptr(rstd), M, D, rows_per_batch, eps, stream())
     return xout, out, rstd
 
 
+def _norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate, dw):
+    """The leading arguments of the four ldmae_*norm_modulate_bwd* entries; the LayerNorm forms (w is None) take neither w nor dw / beta_w."""
+    head = [dt(dout.dtype), ptr(dout), ptr(x)] + ([] if w is None else [ptr(w)])
+    return head + [ptr(scale), _mod_ld(scale), ptr(rstd), ptr(dx_accum), 1.0 if accumulate else 0.0, ptr(dshift), ptr(dscale),
+                   _mod_ld(dshift, dscale)] + ([] if w is None else [ptr(dw), 0.0])
+
+
 def rmsnorm_modulate_bwd(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows_per_batch, accumulate=True):
     """dx_accum += dx (in place; accumulate=False: dx_accum = dx, the buffer may be uninitialised); writes dshift/dscale views ([B,D], any
-    row stride); returns dw [D]."""
+    row stride); returns dw [D] (None for w=None: LayerNorm without affine parameters, use_rmsnorm=False, has no weight gradient)."""
     M, D = x.shape
     ws = workspace(L.load().ldmae_rmsnorm_modulate_bwd_workspace_bytes(M, D, rows_per_batch), x.device)
-    dld = (dshift if dshift is not None else dscale).stride(0) if (dshift is not None or dscale is not None) else 0
-    if w is None:                      # LayerNorm without affine parameters (use_rmsnorm=False): no weight gradient
-        call("ldmae_layernorm_modulate_bwd", dt(dout.dtype), ptr(dout), ptr(x), ptr(scale), scale.stride(0) if scale is not None else 0, ptr(rstd), ptr(dx_accum),
-             1.0 if accumulate else 0.0, ptr(dshift), ptr(dscale), dld, M, D, rows_per_batch, ptr(ws), stream())
-        return None
-    dw = torch.empty(D, dtype=torch.float32, device=x.device)
-    call("ldmae_rmsnorm_modulate_bwd", dt(dout.dtype), ptr(dout), ptr(x), ptr(w), ptr(scale), scale.stride(0) if scale is not None else 0,
-         ptr(rstd), ptr(dx_accum), 1.0 if accumulate else 0.0, ptr(dshift), ptr(dscale), (dshift if dshift is not None else dscale).stride(0) if (dshift is not None or dscale is not None) else 0,
-         ptr(dw), 0.0, M, D, rows_per_batch, ptr(ws), stream())
+    dw = None if w is None else torch.empty(D, dtype=torch.float32, device=x.device)
+    call("ldmae_layernorm_modulate_bwd" if w is None else "ldmae_rmsnorm_modulate_bwd",
+         *_norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate, dw), M, D, rows_per_batch, ptr(ws), stream())
     return dw
 
 
 def rmsnorm_modulate_bwd_gate(dout, x, w, scale, rstd, dx_accum, dshift, dscale, y, gate, dgate, rows_per_batch, act_dtype, accumulate=True,
                               recompute=False):
     """rmsnorm_modulate_bwd followed by gate_bwd(dx_accum, y, gate, dgate, with_bias=True) in one pass over the rows.
-    Returns (dw [D], dy [M,D] act dtype, dbias [D]).  recompute: `x` is the residual stream BEFORE the gated residual under the norm (the
-    forward ran res_rmsnorm_modulate_fwd and never stored the normalised row); the kernel rebuilds that row as x + gate * y.  Bitwise the
-    plain form handed the row materialised; bf16, RMSNorm form."""
+    Returns (dw [D] or None as above, dy [M,D] act dtype, dbias [D]).  recompute: `x` is the residual stream BEFORE the gated residual under
+    the norm (the forward ran res_rmsnorm_modulate_fwd and never stored the normalised row); the kernel rebuilds that row as x + gate * y.
+    Bitwise the plain form handed the row materialised; bf16, RMSNorm form."""
     M, D = x.shape
     if recompute and (w is None or dout.dtype != torch.bfloat16):
         raise RuntimeError("rmsnorm_modulate_bwd_gate(recompute=True): the RMSNorm form with bfloat16 activations only")
     dy = torch.empty(M, D, dtype=act_dtype, device=x.device)
     dbias = torch.empty(D, dtype=torch.float32, device=x.device)
     ws = workspace(L.load().ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes(M, D, rows_per_batch), x.device)
-    if w is None:                      # LayerNorm without affine parameters (use_rmsnorm=False)
-        dld = (dshift if dshift is not None else dscale).stride(0) if (dshift is not None or dscale is not None) else 0
-        call("ldmae_layernorm_modulate_bwd_gate", dt(dout.dtype), ptr(dout), ptr(x), ptr(scale), scale.stride(0) if scale is not None else 0, ptr(rstd),
-             ptr(dx_accum), 1.0 if accumulate else 0.0, ptr(dshift), ptr(dscale), dld, ptr(y), ptr(gate), gate.stride(0), ptr(dy), ptr(dgate), dgate.stride(0),
-             ptr(dbias), M, D, rows_per_batch, ptr(ws), stream())
-        return None, dy, dbias
-    dw = torch.empty(D, dtype=torch.float32, device=x.device)
-    call("ldmae_rmsnorm_modulate_bwd_gate_recompute" if recompute else "ldmae_rmsnorm_modulate_bwd_gate", dt(dout.dtype), ptr(dout), ptr(x), ptr(w), ptr(scale),
-         scale.stride(0) if scale is not None else 0,
-         ptr(rstd), ptr(dx_accum), 1.0 if accumulate else 0.0, ptr(dshift), ptr(dscale), (dshift if dshift is not None else dscale).stride(0) if (dshift is not None or dscale is not None) else 0, ptr(dw), 0.0,
-         ptr(y), ptr(gate), gate.stride(0), ptr(dy), ptr(dgate), dgate.stride(0), ptr(dbias), M, D, rows_per_batch, ptr(ws), stream())
+    dw = None if w is None else torch.empty(D, dtype=torch.float32, device=x.device)
+    entry = "ldmae_layernorm_modulate_bwd_gate" if w is None else "ldmae_rmsnorm_modulate_bwd_gate" + ("_recompute" if recompute else "")
+    call(entry, *_norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate, dw), ptr(y), ptr(gate), gate.stride(0),
+         ptr(dy), ptr(dgate), dgate.stride(0), ptr(dbias), M, D, rows_per_batch, ptr(ws), stream())
     return dw, dy, dbias
 
 
