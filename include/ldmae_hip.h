@@ -275,6 +275,21 @@ int ldmae_label_embed_bwd(const float* dout, const long long* y, const unsigned 
 int ldmae_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long n, int step, double lr, double beta1,
                     double beta2, double eps, double weight_decay, double ema_decay, double grad_scale, void* stream);
 int ldmae_ema_only(float* ema, const float* p, long n, double ema_decay, void* stream);
+/* Power-function EMA tracks for post-hoc EMA reconstruction (Karras et al. 2024, section 3), in the AdamW pass.
+ * p, m, v and ema are written exactly as ldmae_adamw_ema writes them (same expressions, same order: bit for bit).
+ * Each of the ntracks (1..4) slabs t0..t3 then takes  e <- e + c (theta - e)  in f32, theta = the parameter after this
+ * step's update, c_k = 1 - beta_k(t) = -expm1((gamma_k + 1) log1p(-1/t)) computed by the caller in f64 and rounded to
+ * f32 here.  c_k == 1 (t = 1) stores theta and does NOT read the slab.  0 < c_k <= 1.  Any n; any base alignment (all
+ * slabs congruent modulo 16 bytes use 16-byte accesses between a scalar head and a scalar tail). */
+int ldmae_adamw_ema_tracks(float* p, const float* g, float* m, float* v, float* ema, long n, int step, double lr, double beta1,
+                           double beta2, double eps, double weight_decay, double ema_decay, double grad_scale, int ntracks,
+                           float* t0, float* t1, float* t2, float* t3, double c0, double c1, double c2, double c3, void* stream);
+/* the same track update alone, for parameters the optimizer does not touch (the frozen tail: pos_embed) */
+int ldmae_ema_tracks_only(const float* p, long n, int ntracks, float* t0, float* t1, float* t2, float* t3, double c0, double c1,
+                          double c2, double c3, void* stream);
+/* Combination of snapshots: acc[i] += coef * x[i] in f64 (coefficients of both signs), then out[i] = (float)acc[i]. */
+int ldmae_snapshot_accumulate(double* acc, const float* x, long n, double coef, void* stream);
+int ldmae_snapshot_finish(float* out, const double* acc, long n, void* stream);
 
 /* ---- VMAE masked-token encoder (tokenizer/models_mae.py) ------------------------------------- */
 /* random_masking (:472-497) on caller-supplied noise[N,L] f32: stable ascending argsort (ties -> lower

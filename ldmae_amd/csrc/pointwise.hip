@@ -520,3 +520,193 @@ extern "C" int ldmae_ema_only(float* ema, const float* p, long n, double ema_dec
   LDMAE_CHECK_LAUNCH("ema_only");
   return LDMAE_OK;
 }
+
+// ------------------------------------------------------------------ AdamW + EMA + power-function EMA tracks (post-hoc EMA)
+// Karras et al. 2024 ("Analyzing and Improving the Training Dynamics of Diffusion Models", section 3).  Step t counts optimizer steps from 1;
+// with exponent gamma:  beta(t) = (1 - 1/t)^(gamma+1),  e(t) = beta e(t-1) + (1 - beta) theta(t),  theta(t) = the parameter AFTER the AdamW
+// update of step t (what the classic EMA takes).  beta(1) = 0, so e(1) = theta(1) whatever the slab held.  The weight of theta(tau) in e(t) is
+// w_tau = (1 - beta(tau)) (tau/t)^(gamma+1); the weights sum to 1.
+// The kernel does no transcendental arithmetic: the caller passes c = 1 - beta(t), computed in f64 as -expm1((gamma+1) log1p(-1/t)), and the
+// update is the ONE-coefficient form  e <- e + c (theta - e)  in f32.  (beta e + (1-beta) theta with two separately rounded coefficients has
+// its fixed point for a constant parameter at theta (1-beta)_f32 / (1 - beta_f32): at t ~ 1e6, gamma ~ 17 that is off by ~3e-8 / 1.8e-5 =
+// 0.17 %.  The one-coefficient form has the exact fixed point.)  c == 1 (t = 1) stores theta and does not read the slab: a NaN in an
+// uninitialised slab would survive 1 * (theta - NaN).
+// p, m, v, ema: the operations of adamw_ema_kernel, in its order -- turning tracks on never perturbs training (tested bitwise).
+struct TrackArgs { float* e[4]; float c[4]; };
+// One element of adamw_ema_kernel.  Its expressions are compiled with floating-point contraction on, and which product of `x * a + b * y`
+// joins the addition is the compiler's choice: there it is always the first (read off the kernel's code: m = fma(w1, g - m, m), v = fma(v,
+// beta2, w2 * (g * g)), p = fma(p, decay_mul, neg_step * (m / denom)), ema = fma(ema, ema_d, ema_a * p)); in another loop shape it may be
+// the other one, and the result then differs in the last bit.  So the same operations are written out here with contraction off: the
+// 16-byte loop and the scalar loop below both give adamw_ema_kernel's bits (tested bitwise, also off 16-byte boundaries).
+__device__ __forceinline__ void adamw_ema_elem(float& p, float g, float& m, float& v, float& e, const AdamArgs& a) {
+#pragma clang fp contract(off)
+  const float gj = a.gscale == 1.f ? g : g * a.gscale;
+  m = __builtin_fmaf(a.w1, gj - m, m);                              // exp_avg.lerp_(grad, 1-beta1)
+  const float g2 = gj * gj;
+  v = __builtin_fmaf(v, a.beta2, a.w2 * g2);                        // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;                // (sqrt(v)/bc2_sqrt).add_(eps)
+  p = __builtin_fmaf(p, a.decay_mul, a.neg_step * (m / denom));     // p.mul_(1 - lr*wd); p.addcdiv_(m, denom, value=-step_size)
+  e = __builtin_fmaf(e, a.ema_d, a.ema_a * p);
+}
+// e + c (theta - e), as one subtraction and one fma in both loops: a track's bits do not depend on where its slab starts
+__device__ __forceinline__ float track_elem(float e, float c, float theta) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(c, theta - e, e);
+}
+// ADAM = false: the tracks alone (p is only read).  Elements [head, head + 4 nvec) go as 16-byte vectors; the scalar loop takes the head
+// (up to the first 16-byte boundary) and the tail -- or everything, when the slabs are not congruent modulo 16 bytes (head = n).
+template <int K, bool ADAM>
+__global__ void adamw_ema_tracks_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                        float* __restrict__ ema, long n, long head, AdamArgs a, TrackArgs t) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (long)gridDim.x * blockDim.x;
+  const long nvec = (n - head) / 4, tail0 = head + nvec * 4, nscalar = head + (n - tail0);
+  for (long q = tid; q < nvec; q += nthreads) {
+    const long i = head + q * 4;
+    const float4 pv = *(const float4*)(p + i);
+    float pa[4] = {pv.x, pv.y, pv.z, pv.w};
+    if (ADAM) {
+      float4 gv = *(const float4*)(g + i), mv = *(float4*)(m + i), vv = *(float4*)(v + i);
+      float ga[4] = {gv.x, gv.y, gv.z, gv.w}, ma[4] = {mv.x, mv.y, mv.z, mv.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
+      float ea[4] = {0, 0, 0, 0};
+      if (ema) { float4 e = *(float4*)(ema + i); ea[0] = e.x; ea[1] = e.y; ea[2] = e.z; ea[3] = e.w; }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) adamw_ema_elem(pa[j], ga[j], ma[j], va[j], ea[j], a);
+      *(float4*)(p + i) = make_float4(pa[0], pa[1], pa[2], pa[3]);
+      *(float4*)(m + i) = make_float4(ma[0], ma[1], ma[2], ma[3]);
+      *(float4*)(v + i) = make_float4(va[0], va[1], va[2], va[3]);
+      if (ema) *(float4*)(ema + i) = make_float4(ea[0], ea[1], ea[2], ea[3]);
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float4 o = make_float4(pa[0], pa[1], pa[2], pa[3]);
+      if (t.c[k] != 1.f) {
+        const float4 e = *(const float4*)(t.e[k] + i);
+        o.x = track_elem(e.x, t.c[k], pa[0]); o.y = track_elem(e.y, t.c[k], pa[1]);
+        o.z = track_elem(e.z, t.c[k], pa[2]); o.w = track_elem(e.w, t.c[k], pa[3]);
+      }
+      *(float4*)(t.e[k] + i) = o;
+    }
+  }
+  for (long s = tid; s < nscalar; s += nthreads) {
+    const long i = s < head ? s : tail0 + (s - head);
+    float ps = p[i];
+    if (ADAM) {
+      float ms = m[i], vs = v[i], es = ema ? ema[i] : 0.f;
+      adamw_ema_elem(ps, g[i], ms, vs, es, a);
+      p[i] = ps; m[i] = ms; v[i] = vs;
+      if (ema) ema[i] = es;
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      float o = ps;
+      if (t.c[k] != 1.f) o = track_elem(t.e[k][i], t.c[k], ps);
+      t.e[k][i] = o;
+    }
+  }
+}
+// head (in elements) of the scalar prologue: up to the first 16-byte boundary when every slab has the same address modulo 16, else n
+static long tracks_head(const void* const* ptrs, int count, long n) {
+  const unsigned long r = (unsigned long)ptrs[0] & 15ul;
+  for (int i = 1; i < count; ++i)
+    if (((unsigned long)ptrs[i] & 15ul) != r) return n;
+  const long h = (long)((16ul - r) & 15ul) / 4;
+  return h < n ? h : n;
+}
+template <bool ADAM>
+static int launch_tracks(float* p, const float* g, float* m, float* v, float* ema, long n, const AdamArgs& a, int ntracks, float* const* ts,
+                         const double* cs, void* stream, const char* name) {
+  LDMAE_REQUIRE(ntracks >= 1 && ntracks <= 4, "%s: %d tracks (1..4)", name, ntracks);
+  TrackArgs t;
+  const void* ptrs[9];
+  int np = 0;
+  ptrs[np++] = p;
+  if (ADAM) { ptrs[np++] = g; ptrs[np++] = m; ptrs[np++] = v; if (ema) ptrs[np++] = ema; }
+  for (int k = 0; k < 4; ++k) { t.e[k] = nullptr; t.c[k] = 0.f; }
+  for (int k = 0; k < ntracks; ++k) {
+    LDMAE_REQUIRE(ts[k] != nullptr, "%s: track %d has no slab", name, k);
+    LDMAE_REQUIRE(cs[k] > 0.0 && cs[k] <= 1.0, "%s: track %d coefficient %g is not 1 - beta(t) in (0, 1]", name, k, cs[k]);
+    t.e[k] = ts[k];
+    t.c[k] = (float)cs[k];
+    LDMAE_REQUIRE(t.c[k] > 0.f, "%s: track %d coefficient %g rounds to 0 in f32", name, k, cs[k]);
+    ptrs[np++] = ts[k];
+  }
+  for (int i = 0; i < np; ++i) LDMAE_REQUIRE(((unsigned long)ptrs[i] & 3ul) == 0, "%s: a slab is not 4-byte aligned", name);
+  const long head = tracks_head(ptrs, np, n), nvec = (n - head) / 4, nscalar = n - nvec * 4;
+  const dim3 grid(ew_grid(nvec > nscalar ? nvec : nscalar)), block(256);
+  hipStream_t st = as_stream(stream);
+  switch (ntracks) {
+    case 1: hipLaunchKernelGGL((adamw_ema_tracks_kernel<1, ADAM>), grid, block, 0, st, p, g, m, v, ema, n, head, a, t); break;
+    case 2: hipLaunchKernelGGL((adamw_ema_tracks_kernel<2, ADAM>), grid, block, 0, st, p, g, m, v, ema, n, head, a, t); break;
+    case 3: hipLaunchKernelGGL((adamw_ema_tracks_kernel<3, ADAM>), grid, block, 0, st, p, g, m, v, ema, n, head, a, t); break;
+    default: hipLaunchKernelGGL((adamw_ema_tracks_kernel<4, ADAM>), grid, block, 0, st, p, g, m, v, ema, n, head, a, t); break;
+  }
+  LDMAE_CHECK_LAUNCH(name);
+  return LDMAE_OK;
+}
+extern "C" int ldmae_adamw_ema_tracks(float* p, const float* g, float* m, float* v, float* ema, long n, int step, double lr, double beta1,
+                                      double beta2, double eps, double weight_decay, double ema_decay, double grad_scale, int ntracks,
+                                      float* t0, float* t1, float* t2, float* t3, double c0, double c1, double c2, double c3, void* stream) {
+  LDMAE_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw_ema_tracks: bad arguments");
+  const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
+  AdamArgs a;                                    // as ldmae_adamw_ema prepares them
+  a.decay_mul = (float)(1.0 - lr * weight_decay);
+  a.w1 = (float)(1.0 - beta1);
+  a.beta2 = (float)beta2;
+  a.w2 = (float)(1.0 - beta2);
+  a.bc2_sqrt = (float)sqrt(bc2);
+  a.eps = (float)eps;
+  a.neg_step = (float)(-(lr / bc1));
+  a.ema_d = (float)ema_decay;
+  a.ema_a = (float)(1.0 - ema_decay);
+  a.gscale = (float)grad_scale;
+  float* const ts[4] = {t0, t1, t2, t3};
+  const double cs[4] = {c0, c1, c2, c3};
+  return launch_tracks<true>(p, g, m, v, ema, n, a, ntracks, ts, cs, stream, "adamw_ema_tracks");
+}
+extern "C" int ldmae_ema_tracks_only(const float* p, long n, int ntracks, float* t0, float* t1, float* t2, float* t3, double c0, double c1,
+                                     double c2, double c3, void* stream) {
+  LDMAE_REQUIRE(p && n > 0, "ema_tracks_only: bad arguments");
+  float* const ts[4] = {t0, t1, t2, t3};
+  const double cs[4] = {c0, c1, c2, c3};
+  AdamArgs a = {};
+  return launch_tracks<false>(const_cast<float*>(p), nullptr, nullptr, nullptr, nullptr, n, a, ntracks, ts, cs, stream, "ema_tracks_only");
+}
+
+// ------------------------------------------------------------------ combination of snapshots: sum_i x_i snapshot_i
+// The least-squares coefficients have mixed signs and run to ~3.7 in magnitude for narrow targets, so the sum is kept in f64 and rounded
+// to f32 once, at the end.  16-byte accesses where both buffers allow them, a scalar tail (or everything) otherwise.
+__global__ void snapshot_accumulate_kernel(double* __restrict__ acc, const float* __restrict__ x, long n, long nvec, double coef) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (long)gridDim.x * blockDim.x;
+  for (long q = tid; q < nvec; q += nthreads) {
+    const float4 xv = *(const float4*)(x + q * 4);
+    double2 a0 = *(double2*)(acc + q * 4), a1 = *(double2*)(acc + q * 4 + 2);
+    a0.x += coef * (double)xv.x; a0.y += coef * (double)xv.y; a1.x += coef * (double)xv.z; a1.y += coef * (double)xv.w;
+    *(double2*)(acc + q * 4) = a0; *(double2*)(acc + q * 4 + 2) = a1;
+  }
+  for (long i = nvec * 4 + tid; i < n; i += nthreads) acc[i] += coef * (double)x[i];
+}
+__global__ void snapshot_finish_kernel(float* __restrict__ out, const double* __restrict__ acc, long n, long nvec) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (long)gridDim.x * blockDim.x;
+  for (long q = tid; q < nvec; q += nthreads) {
+    const double2 a0 = *(const double2*)(acc + q * 4), a1 = *(const double2*)(acc + q * 4 + 2);
+    *(float4*)(out + q * 4) = make_float4((float)a0.x, (float)a0.y, (float)a1.x, (float)a1.y);
+  }
+  for (long i = nvec * 4 + tid; i < n; i += nthreads) out[i] = (float)acc[i];
+}
+extern "C" int ldmae_snapshot_accumulate(double* acc, const float* x, long n, double coef, void* stream) {
+  LDMAE_REQUIRE(acc && x && n > 0, "snapshot_accumulate: bad arguments");
+  LDMAE_REQUIRE(((unsigned long)acc & 7ul) == 0 && ((unsigned long)x & 3ul) == 0, "snapshot_accumulate: misaligned buffer");
+  LDMAE_REQUIRE(coef == coef && coef - coef == 0.0, "snapshot_accumulate: coefficient %g is not finite", coef);
+  const long nvec = (((unsigned long)acc | (unsigned long)x) & 15ul) == 0 ? n / 4 : 0;
+  hipLaunchKernelGGL(snapshot_accumulate_kernel, dim3(ew_grid(nvec ? nvec : n)), dim3(256), 0, as_stream(stream), acc, x, n, nvec, coef);
+  LDMAE_CHECK_LAUNCH("snapshot_accumulate");
+  return LDMAE_OK;
+}
+extern "C" int ldmae_snapshot_finish(float* out, const double* acc, long n, void* stream) {
+  LDMAE_REQUIRE(out && acc && n > 0, "snapshot_finish: bad arguments");
+  LDMAE_REQUIRE(((unsigned long)acc & 7ul) == 0 && ((unsigned long)out & 3ul) == 0, "snapshot_finish: misaligned buffer");
+  const long nvec = (((unsigned long)acc | (unsigned long)out) & 15ul) == 0 ? n / 4 : 0;
+  hipLaunchKernelGGL(snapshot_finish_kernel, dim3(ew_grid(nvec ? nvec : n)), dim3(256), 0, as_stream(stream), out, acc, n, nvec);
+  LDMAE_CHECK_LAUNCH("snapshot_finish");
+  return LDMAE_OK;
+}

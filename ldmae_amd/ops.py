@@ -979,6 +979,55 @@ def ema_only(ema, p, ema_decay):
     call("ldmae_ema_only", ptr(ema), ptr(p), p.numel(), float(ema_decay), stream())
 
 
+def _track_args(op, tracks, coefs, p):
+    """The (count, 4 slab pointers, 4 coefficients) tail of the two track entries: 1..4 f32 slabs of p's length on p's device, written in
+    place (out=True: never copied), one c_k = 1 - beta_k(t) each."""
+    tracks, coefs = list(tracks), [float(c) for c in coefs]
+    if not 1 <= len(tracks) <= 4 or len(coefs) != len(tracks):
+        raise RuntimeError(f"{op}: {len(tracks)} track slabs with {len(coefs)} coefficients (need 1..4 of each, one coefficient per slab)")
+    for k, t in enumerate(tracks):
+        _arg(t, f"{op} track {k}", dtype=torch.float32, numel=p.numel(), like=p, out=True)
+    pad = 4 - len(tracks)
+    return (len(tracks), *[ptr(t) for t in tracks], *([None] * pad), *coefs, *([0.0] * pad))
+
+
+def adamw_ema_tracks(p, g, m, v, ema, tracks, coefs, step, lr, beta1, beta2, eps, weight_decay, ema_decay, grad_scale=1.0):
+    """`adamw_ema` plus the power-function EMA tracks of the post-hoc EMA in the same pass: p, m, v, ema come out bit for bit as `adamw_ema`
+    writes them; tracks[k] <- tracks[k] + coefs[k] (p_new - tracks[k]) (coefs[k] == 1: p_new is stored, the slab is not read)."""
+    global WEIGHT_EPOCH
+    op = "adamw_ema_tracks"
+    _arg(p, op + " p", dtype=torch.float32, out=True)
+    for name, t in (("g", g), ("m", m), ("v", v), ("ema", ema)):
+        _arg(t, f"{op} {name}", dtype=torch.float32, numel=p.numel(), like=p, out=True)
+    tail = _track_args(op, tracks, coefs, p)
+    WEIGHT_EPOCH += 1
+    call("ldmae_adamw_ema_tracks", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), int(step), float(lr), float(beta1), float(beta2),
+         float(eps), float(weight_decay), float(ema_decay), float(grad_scale), *tail, stream())
+
+
+def ema_tracks_only(p, tracks, coefs):
+    """The track update alone, for parameters the optimizer does not touch (the frozen tail)."""
+    op = "ema_tracks_only"
+    _arg(p, op + " p", dtype=torch.float32, copy=False)
+    call("ldmae_ema_tracks_only", ptr(p), p.numel(), *_track_args(op, tracks, coefs, p), stream())
+
+
+def snapshot_accumulate(acc, x, coef):
+    """acc (f64) += coef * x (f32), element by element; coef is a python float (f64)."""
+    _arg(acc, "snapshot_accumulate acc", dtype=torch.float64, out=True)
+    _arg(x, "snapshot_accumulate x", dtype=torch.float32, numel=acc.numel(), like=acc, copy=False)
+    call("ldmae_snapshot_accumulate", ptr(acc), ptr(x), acc.numel(), float(coef), stream())
+
+
+def snapshot_finish(acc, out=None):
+    """The f64 accumulator rounded to f32 (into `out`, or a new tensor of acc's shape)."""
+    _arg(acc, "snapshot_finish acc", dtype=torch.float64, copy=False)
+    out = torch.empty(acc.shape, dtype=torch.float32, device=acc.device) if out is None else out
+    _arg(out, "snapshot_finish out", dtype=torch.float32, numel=acc.numel(), like=acc, out=True)
+    call("ldmae_snapshot_finish", ptr(out), ptr(acc), acc.numel(), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- VMAE
 def random_masking(noise, keep):
     N, Lq = noise.shape

@@ -8,11 +8,13 @@ alone.  The same contiguous gradient buffer is what the data-parallel reducer al
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 
 import torch
 
 from . import ops
+from . import posthoc_ema as ph
 
 _ALIGN = 64   # elements (256 B): keeps every parameter view 16-B aligned for the GEMM operand loads
 
@@ -79,8 +81,11 @@ class AdamWEMA:
     reference's EMA includes the frozen ``pos_embed``, train_accum.py:343-347)."""
 
     def __init__(self, module, lr=2e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.0, ema_decay=0.9999, flat: FlatParams = None,
-                 group_weight_decay=None, front_fn=None):
-        """group_weight_decay: {group id: weight decay} for a ``FlatParams(module, group_fn)`` layout (default: `weight_decay` everywhere)."""
+                 group_weight_decay=None, front_fn=None, posthoc_sigma_rels=None):
+        """group_weight_decay: {group id: weight decay} for a ``FlatParams(module, group_fn)`` layout (default: `weight_decay` everywhere).
+        posthoc_sigma_rels: up to 4 relative widths; one power-function EMA track over ALL parameters is kept per width, updated in the
+        AdamW pass (``posthoc_ema``: any EMA width can then be reconstructed after training from snapshots of the tracks).  Absent: no slab
+        is allocated and `step` makes exactly the calls it made before."""
         self.module = module
         self.flat = flat or FlatParams(module, front_fn=front_fn)
         self.lr, self.betas, self.eps, self.weight_decay, self.ema_decay = lr, betas, eps, weight_decay, ema_decay
@@ -90,6 +95,13 @@ class AdamWEMA:
         self.v = torch.zeros_like(f.grads)
         self.ema = f.params.clone()          # == update_ema(ema, model, decay=0) at start (train_accum.py:166)
         self.step_count = 0
+        self.sigma_rels = tuple(ph.check_sigma_rel(s) for s in (posthoc_sigma_rels or ()))
+        if len(self.sigma_rels) > ph.MAX_TRACKS:
+            raise ValueError(f"AdamWEMA: {len(self.sigma_rels)} posthoc_sigma_rels; the fused pass carries at most {ph.MAX_TRACKS} tracks")
+        self.gammas = tuple(ph.sigma_rel_to_gamma(s) for s in self.sigma_rels)
+        # step 1 stores the parameters without reading the slab (beta(1) = 0), so the slabs need no initial value
+        self.tracks = [torch.empty_like(f.params) for _ in self.sigma_rels]
+        self.track_step = 0          # t of the power-function profiles: optimizer steps since the START of training (restored on resume)
 
     def zero_grad(self):
         self.flat.grads.zero_()
@@ -103,11 +115,21 @@ class AdamWEMA:
         n = f.n_trainable
         spans = [(0, n, self.weight_decay)] if not self.group_weight_decay else \
             [(lo, hi, self.group_weight_decay.get(g, self.weight_decay)) for g, (lo, hi) in sorted(f.groups.items())]
+        if self.tracks:
+            self.track_step += 1
+            coefs = [ph.track_coef(g, self.track_step) for g in self.gammas]         # c_k = 1 - beta_k(t), f64 on the host
         for lo, hi, wd in spans:
-            ops.adamw_ema(f.params[lo:hi], f.grads[lo:hi], self.m[lo:hi], self.v[lo:hi], self.ema[lo:hi], self.step_count, self.lr,
-                          self.betas[0], self.betas[1], self.eps, wd, self.ema_decay, grad_scale)
+            if self.tracks:
+                ops.adamw_ema_tracks(f.params[lo:hi], f.grads[lo:hi], self.m[lo:hi], self.v[lo:hi], self.ema[lo:hi],
+                                     [t[lo:hi] for t in self.tracks], coefs, self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, wd,
+                                     self.ema_decay, grad_scale)
+            else:
+                ops.adamw_ema(f.params[lo:hi], f.grads[lo:hi], self.m[lo:hi], self.v[lo:hi], self.ema[lo:hi], self.step_count, self.lr,
+                              self.betas[0], self.betas[1], self.eps, wd, self.ema_decay, grad_scale)
         if f.total > n:
             ops.ema_only(self.ema[n:], f.params[n:], self.ema_decay)
+            if self.tracks:          # the tracks cover the frozen tail too (pos_embed): a reconstructed state dict has the reference's key set
+                ops.ema_tracks_only(f.params[n:], [t[n:] for t in self.tracks], coefs)
 
     def ema_state_dict(self):
         """EMA weights under the module's parameter names (+ buffers copied as-is), loadable by
@@ -117,6 +139,62 @@ class AdamWEMA:
         for k, v in self.module.state_dict().items():
             sd[k] = self.flat.view(self.ema, k, params[k].shape).clone() if k in params else v.clone()
         return sd
+
+    # ------------------------------------------------------------------ post-hoc EMA tracks
+    def _need_tracks(self, what):
+        if not self.tracks:
+            raise RuntimeError(f"AdamWEMA.{what}: this optimizer keeps no post-hoc EMA tracks (posthoc_sigma_rels was not given)")
+
+    def snapshot_layout(self):
+        """(name, offset, shape) of every parameter in slab order: what a snapshot index records."""
+        shapes = {n: tuple(p.shape) for n, p in self.module.named_parameters()}
+        return [(n, int(o), shapes[n]) for n, (o, _) in self.flat.offsets.items()]
+
+    def track_state_dict(self):
+        """The tracks and their step, for a checkpoint (the slabs themselves, like `state_dict`)."""
+        self._need_tracks("track_state_dict")
+        return {"step": self.track_step, "sigma_rels": list(self.sigma_rels), "gammas": list(self.gammas), "tracks": list(self.tracks),
+                "layout": self.layout()}
+
+    @torch.no_grad()
+    def load_track_state(self, sd):
+        """Restores the tracks and their step.  Validated before anything is touched: other widths or other parameters are refused; another
+        slab order of the same parameters is re-ordered by name."""
+        self._need_tracks("load_track_state")
+        if any(k not in sd for k in ("step", "sigma_rels", "tracks", "layout")):
+            raise RuntimeError("AdamWEMA.load_track_state: the saved state lacks step / sigma_rels / tracks / layout")
+        if [float(s) for s in sd["sigma_rels"]] != list(self.sigma_rels) or len(sd["tracks"]) != len(self.tracks):
+            raise RuntimeError(f"AdamWEMA.load_track_state: the saved tracks have sigma_rels {list(sd['sigma_rels'])}, this optimizer {list(self.sigma_rels)}")
+        mine, lay = self.flat.offsets, [tuple(x) for x in sd["layout"]]
+        if {n for n, _, _ in lay} != set(mine) or any(mine[n][1] != k for n, _, k in lay):
+            raise RuntimeError("AdamWEMA.load_track_state: the saved tracks belong to a different set of parameters")
+        if any(t.dtype != torch.float32 or t.numel() < max(o + k for _, o, k in lay) for t in sd["tracks"]):
+            raise RuntimeError("AdamWEMA.load_track_state: the saved slabs are not float32 slabs of the recorded layout")
+        for dst, src in zip(self.tracks, sd["tracks"]):
+            if lay == self.layout() and src.numel() == dst.numel():
+                dst.copy_(src)
+            else:
+                for n, o, k in lay:
+                    d = mine[n][0]
+                    dst[d:d + k].copy_(src[o:o + k])
+        self.track_step = int(sd["step"])
+
+    @torch.no_grad()
+    def write_snapshot(self, directory, step=None):
+        """One raw f32 file per track for this step into `directory` (created; its snapshots.json is rewritten atomically afterwards).  `step`,
+        when given, must be the tracks' step: the profile a snapshot stands for is (step, gamma)."""
+        self._need_tracks("write_snapshot")
+        step = self.track_step if step is None else int(step)
+        if step != self.track_step or step < 1:
+            raise RuntimeError(f"AdamWEMA.write_snapshot: step {step}, but the tracks are at step {self.track_step}")
+        os.makedirs(directory, exist_ok=True)
+        if os.path.exists(os.path.join(directory, ph.INDEX)):
+            index = ph.read_index(directory, verify=False)
+            if not ph.same_run(index, self.snapshot_layout(), self.flat.total, self.sigma_rels):
+                raise RuntimeError(f"AdamWEMA.write_snapshot: {directory} holds snapshots of another layout or other sigma_rels (mismatched layout)")
+        else:
+            index = ph.new_index(self.snapshot_layout(), self.flat.total, self.sigma_rels)
+        ph.write_snapshot_files(directory, index, step, [t.cpu().numpy() for t in self.tracks])
 
     def layout(self):
         """(name, offset, numel) of every parameter in slab order: m / v / ema are raw slabs, and the order depends on `front_fn` / `group_fn`."""

@@ -80,6 +80,25 @@ def load_weights_with_shape_check(model, checkpoint, rank=0):
     return model
 
 
+def posthoc_ema_config(tr_cfg, ckpt_dir):
+    """The optional ``train.posthoc_ema: {sigma_rels: [0.05, 0.10], snapshot_every: N, dir: <path>}`` (not a reference key) as
+    (sigma_rels, snapshot_every, dir), or None when the key is absent.  `dir` defaults to <ckpt_dir>/ema_snapshots."""
+    ph_cfg = tr_cfg.get('posthoc_ema')
+    if ph_cfg is None:
+        return None
+    from ldmae_amd.posthoc_ema import MAX_TRACKS, check_sigma_rel
+    unknown = set(ph_cfg) - {'sigma_rels', 'snapshot_every', 'dir'} if isinstance(ph_cfg, dict) else None
+    if unknown is None or unknown or 'sigma_rels' not in ph_cfg or 'snapshot_every' not in ph_cfg:
+        raise ValueError(f"train.posthoc_ema must be a mapping with sigma_rels and snapshot_every (and optionally dir); got {ph_cfg!r}")
+    sig = ph_cfg['sigma_rels']
+    if not isinstance(sig, (list, tuple)) or not 1 <= len(sig) <= MAX_TRACKS:
+        raise ValueError(f"train.posthoc_ema.sigma_rels must list 1..{MAX_TRACKS} widths; got {sig!r}")
+    every = ph_cfg['snapshot_every']
+    if not isinstance(every, int) or isinstance(every, bool) or every < 1:
+        raise ValueError(f"train.posthoc_ema.snapshot_every must be a positive integer; got {every!r}")
+    return tuple(check_sigma_rel(s) for s in sig), every, str(ph_cfg.get('dir') or f"{ckpt_dir}/ema_snapshots")
+
+
 def make_loader(cfg, per_gpu, rank, world, synthetic):
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
@@ -138,7 +157,9 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
     # weights sit at the FRONT of the gradient slab (optim.adaln_first): the reducer cuts its buckets from the end backwards, the front ones
     # are the last to be all-reduced anyway, and every other bucket still starts under backward.  The data-parallel step is then the same
     # program as the single-GPU one (round 3 switched the batched form off for world > 1).
-    opt = AdamWEMA(model, lr=o['lr'], betas=(0.9, o['beta2']), weight_decay=0.0, ema_decay=0.9999, front_fn=adaln_first)
+    posthoc = posthoc_ema_config(tr_cfg, ckpt_dir)
+    opt = AdamWEMA(model, lr=o['lr'], betas=(0.9, o['beta2']), weight_decay=0.0, ema_decay=0.9999, front_fn=adaln_first,
+                   posthoc_sigma_rels=posthoc[0] if posthoc else None)
     reducer = GradBucketReducer(opt.flat)
     # world > 1: those front buckets (170 MB for B/1, 890 MB for XL/1) are all-reduced fully exposed, which can cost more than the ~0.125 ms per
     # block that batching saves -- chosen by size until a multi-rank run has measured it (distributed.batched_adaln_pays; the exposed time is
@@ -166,6 +187,14 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
                 if k in opt.flat.offsets:
                     opt.flat.view(opt.ema, k, v.shape).copy_(v)
             train_steps = int(os.path.basename(files[-1]).split('.')[0])
+            if posthoc:
+                # the tracks average the whole trajectory theta(1..t): their slabs and step come back, and AdamW continues with its moments
+                # and step (the checkpoint's "opt"), so the parameters the tracks see are those of the uninterrupted run
+                if 'ema_tracks' not in ck:
+                    raise RuntimeError(f"train.posthoc_ema is set, but {files[-1]} has no 'ema_tracks' entry: the tracks cannot be continued "
+                                       f"from a checkpoint written without them")
+                opt.load_state_dict(ck['opt'])
+                opt.load_track_state(ck['ema_tracks'])
             logger.info(f"Resuming training from checkpoint: {files[-1]}")
     per_gpu = int(np.round(tr_cfg['global_batch_size'] / world))
     accum = int(tr_cfg['gradient_accumulation_steps'])
@@ -225,10 +254,16 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
                 logger.info(f"(step={train_steps:07d}) Train Loss: {avg.item() / world:.4f}, Train Steps/Sec: {log_steps / (time() - start):.2f}{comm}")
                 running.zero_()
                 log_steps, start = 0, time()
-            if train_steps % tr_cfg['ckpt_every'] == 0 and train_steps > 0:
+            at_ckpt = train_steps % tr_cfg['ckpt_every'] == 0 and train_steps > 0
+            if posthoc and rank == 0 and (at_ckpt or opt.track_step % posthoc[1] == 0):
+                opt.write_snapshot(posthoc[2])
+            if at_ckpt:
                 if rank == 0:
                     path = f"{ckpt_dir}/{train_steps:07d}.pt"
-                    torch.save({"model": model.state_dict(), "ema": opt.ema_state_dict(), "opt": opt.torch_adamw_state_dict(), "config": cfg}, path)   # train_accum.py:275-280: "opt" = AdamW.state_dict()
+                    ck = {"model": model.state_dict(), "ema": opt.ema_state_dict(), "opt": opt.torch_adamw_state_dict(), "config": cfg}   # train_accum.py:275-280: "opt" = AdamW.state_dict()
+                    if posthoc:
+                        ck["ema_tracks"] = opt.track_state_dict()
+                    torch.save(ck, path)
                     logger.info(f"Saved checkpoint to {path}")
                 if world > 1:
                     dist.barrier()
