@@ -720,6 +720,27 @@ int ldmae_topk_merge(const float* sims, int ld, int M, int Nc, int col0, float* 
 int ldmae_knn_vote(const float* vals, const int* idx, int M, int k, const long long* bank_labels, int nbank, const long long* qlabels, int C,
                    float temperature, int* rank, float* scores, void* stream);
 
+/* ---- Held-out validation of the flow-matching objective (csrc/fm_valid.hip, ldmae_amd/validate.py) ----
+ * f32, 16-byte accesses, no atomics, every sum in one fixed order.
+ * fm_valid_plan: the model input xt and the regression target ut [B, C, HW] of a validation batch in one launch.  stored: [B, 2C, HW]
+ *   (mean | logvar halves) when sample = 1, else the plain latents [B, C, HW]; idx [B] int64: the GLOBAL index of each sample; t [B]: its time;
+ *   lat_mean / lat_std [C] or both NULL.  With n = C HW, z = the n values ldmae_normal_f32(., n, seed, 2 idx[b]) writes and x0 = those of
+ *   counter 2 idx[b] + 1 (counters taken mod 2^64; z is drawn only when sample = 1):
+ *     x1 = ldmae_latent_prologue's expression on (stored, z): ((mean + exp(0.5 clamp(logvar, -30, 20)) z) - lat_mean) / lat_std * multiplier
+ *     xt = t x1 + (1 - t) x0: 1 - t rounded, each product rounded, then the sum rounded (no fma: ICPlan.plan operation by operation)
+ *     ut = x1 - x0
+ *   so the rows of sample i depend on (stored, seed, i, t) alone, whatever batch, position or rank they are computed in.  Neither draw is
+ *   stored.  HW % 4 == 0; stored, xt, ut 16-byte aligned; xt and ut must not overlap.
+ * row_mse: loss[b] = (sum_j (float(a[b, j]) - u[b, j])^2) / m for B dense rows of m elements, a f32 or bf16 (a_dtype), u f32: the difference
+ *   rounded once, one fma chain per thread over its elements of a 4096-element chunk, the block sum of ldmae_rowdot_f32, partial[b ceil(m / 4096)
+ *   + c], one block per row folds its chunks and divides by m (a true division).  4-element loads (16 bytes of f32, 8 of bf16) when every row
+ *   start of a and u is aligned for them, element loads otherwise (another, equally fixed, order).  partial: ldmae_row_mse_partials(B, m)
+ *   floats. */
+int ldmae_fm_valid_plan_f32(const float* stored, const long long* idx, const float* t, const float* lat_mean, const float* lat_std,
+                            float multiplier, int sample, unsigned long long seed, float* xt, float* ut, int B, int C, int HW, void* stream);
+long ldmae_row_mse_partials(int B, long m);
+int ldmae_row_mse(int a_dtype, const void* a, const float* u, float* loss, int B, long m, float* partial, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1065,6 +1065,47 @@ def latent_prologue(moments, noise=None, lat_mean=None, lat_std=None, multiplier
     return out
 
 
+# ----------------------------------------------------------------------------- held-out validation (csrc/fm_valid.hip), f32
+def fm_valid_plan(stored, idx, t, lat_mean=None, lat_std=None, multiplier=1.0, sample=True, seed=0):
+    """Model input and regression target of a validation batch in one launch: stored [B, 2C, H, W] f32 (mean | logvar, sample) or [B, C, H, W];
+    idx [B] int64, the GLOBAL index of each sample; t [B] f32.  With z = normal(seed, 2 idx[b]) and x0 = normal(seed, 2 idx[b] + 1) (the named
+    draws of `normal`, C H W values each, never stored): x1 = latent_prologue(stored, z, ...), xt = t x1 + (1 - t) x0 and ut = x1 - x0 with the
+    roundings of ICPlan.plan.  Returns (xt, ut) [B, C, H, W] f32: the rows of sample i depend on (stored[i], seed, i, t[i]) alone."""
+    if stored.dim() != 4 or (sample and stored.shape[1] % 2):
+        raise RuntimeError(f"fm_valid_plan stored: shape {tuple(stored.shape)}, expected [B, {'2C' if sample else 'C'}, H, W]")
+    B, C2, H, W = stored.shape
+    C = C2 // 2 if sample else C2
+    stored = _arg(stored, "fm_valid_plan stored", torch.float32, align=16)
+    idx = _arg(idx, "fm_valid_plan idx", torch.int64, (B,), like=stored)
+    t = _arg(t, "fm_valid_plan t", torch.float32, (B,), like=stored)
+    if (lat_mean is None) != (lat_std is None):
+        raise RuntimeError("fm_valid_plan: give both lat_mean and lat_std, or neither")
+    mu, sd = (_arg(s.reshape(-1) if s is not None else None, f"fm_valid_plan {w}", torch.float32, (C,), like=stored)
+              for s, w in ((lat_mean, "lat_mean"), (lat_std, "lat_std")))
+    xt = torch.empty(B, C, H, W, dtype=torch.float32, device=stored.device)
+    ut = torch.empty_like(xt)
+    call("ldmae_fm_valid_plan_f32", ptr(stored), ptr(idx), ptr(t), ptr(mu), ptr(sd), float(multiplier), 1 if sample else 0,
+         int(seed) & (2 ** 64 - 1), ptr(xt), ptr(ut), B, C, H * W, stream())
+    return xt, ut
+
+
+def row_mse(a, u, out=None):
+    """out[b] = mean over everything but dim 0 of (float(a[b]) - u[b])^2: mean_flat((a - u) ** 2) with a f32 or bf16 and u f32, in f32, as a
+    two-stage fixed-order sum (bitwise reproducible).  A tensor of another layout is copied first (the DiT returns a permuted view)."""
+    a = _arg(a, "row_mse a", (torch.float32, torch.bfloat16))
+    u = _arg(u, "row_mse u", torch.float32, a.shape, like=a)
+    if a.dim() < 1 or a.numel() == 0:
+        raise RuntimeError(f"row_mse: two non-empty tensors of at least one dimension expected, got {tuple(a.shape)}")
+    B, m = a.shape[0], a.numel() // a.shape[0]
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=a.device)
+    else:
+        _arg(out, "row_mse out", torch.float32, numel=B, out=True, like=a)
+    partial = torch.empty(int(L.load().ldmae_row_mse_partials(B, m)), dtype=torch.float32, device=a.device)
+    call("ldmae_row_mse", dt(a.dtype), ptr(a), ptr(u), ptr(out), B, m, ptr(partial), stream())
+    return out
+
+
 def check_crop_table(offsets, geom, blob_bytes):
     """The range checks ldmae_crop_resize_flip_u8 leaves to its caller, on the HOST copy of the tables: offsets [B] i64, geom [B, 8] i32 =
     (h, w, top, left, ch, cw, flip, 0).  Raises ValueError naming the first bad sample."""

@@ -203,10 +203,13 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
     if getattr(dataset, "raw", False):
         from ldmae_amd.datasets.img_latent_dataset import LatentPrologue
         prologue = LatentPrologue(dataset).to(device)
-    if 'valid_path' in cfg['data']:
-        # train_accum.py:148-163,288-297 builds a validation loader and calls an `evaluate` that the reference never defines (NameError at the
-        # first checkpoint step); no shipped config sets the key.  Said once instead of dying after ckpt_every steps.
-        logger.info(f"data.valid_path={cfg['data']['valid_path']!r} is ignored: the reference's validation pass calls an undefined evaluate()")
+    # train.valid (opt-in, not a reference key): held-out validation at fixed steps (validate.TrainValidator).  data.valid_path alone is the
+    # reference's state: it builds a validation loader and calls an `evaluate` it never defines, so the key is reported as ignored.
+    from ldmae_amd import validate
+    valid, line = validate.training_plan(cfg, per_gpu)
+    if line:
+        logger.info(line)
+    validator = validate.TrainValidator(cfg, valid, exp_dir, precision, rank, world, device, transport.use_lognorm) if valid else None
     logger.info(f"LightningDiT Parameters: {sum(p.numel() for p in model.parameters()) / 1e6:.2f}M; {len(dataset):,} samples; "
                 f"batch {per_gpu}/gpu x {world} gpus x {accum} accumulation; precision {precision}")
     max_steps = max_steps or tr_cfg['max_steps']
@@ -255,6 +258,8 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
                 running.zero_()
                 log_steps, start = 0, time()
             at_ckpt = train_steps % tr_cfg['ckpt_every'] == 0 and train_steps > 0
+            if validator is not None and validator.due(train_steps):
+                validator.run(model, opt, train_steps, logger)
             if posthoc and rank == 0 and (at_ckpt or opt.track_step % posthoc[1] == 0):
                 opt.write_snapshot(posthoc[2])
             if at_ckpt:
