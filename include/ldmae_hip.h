@@ -741,6 +741,34 @@ int ldmae_fm_valid_plan_f32(const float* stored, const long long* idx, const flo
 long ldmae_row_mse_partials(int B, long m);
 int ldmae_row_mse(int a_dtype, const void* a, const float* u, float* loss, int B, long m, float* partial, void* stream);
 
+/* ---- Guidance rules of the sampler (csrc/guidance.hip, ldmae_amd/guidance.py) ----
+ * Time convention: x_t = t x1 + (1 - t) x0, the model predicts v = x1 - x0, the data prediction is x_t + (1 - t) v.
+ * guidance_combine: pos (the main / conditional output p), neg (the null-class or guide-model output q) [B, C, HW] f32 or bf16 (in_dtype),
+ *   out [B, C, HW] f32, one launch.  The first k channels (1 <= k <= C) of each sample, n_g = k HW contiguous elements, are guided; the sums
+ *   below run over those n_g elements of ONE sample.  f32 arithmetic with every rounding as written (fma = one rounding), except the sums
+ *   and the scalars derived from them, which are f64.  s = scale.
+ *   LDMAE_GUIDE_CFG      g = fma(s, p - q, q).
+ *   LDMAE_GUIDE_RESCALE  g0 = fma(s, p - q, q) (f32); std = the unbiased sample standard deviation (torch.std) of the f32 values p and g0, from
+ *                        the f64 sums of (v - v_0) and (v - v_0)^2, v_0 the sample's first value (equal values: exactly 0); ratio = std(p) /
+ *                        std(g0), or 1 when std(g0) == 0; f = (float)(1 + phi (ratio - 1)) [= phi ratio + 1 - phi]; g = g0 * f.  phi in [0, 1],
+ *                        n_g >= 2.
+ *   LDMAE_GUIDE_APG      omt = 1 - t[b]; d = p - q, then d = fma(momentum, m_prev, d) when momentum != 0 (m_prev = mom[b, i]); u = fma(omt, p, x);
+ *                        <d, d>, <d, u>, <u, u> in f64; gamma = min(1, r / (omt sqrt<d, d>)) when r = norm_threshold > 0 and the denominator
+ *                        is > 0, else 1; c = <d, u> / <u, u>, or 0 when <u, u> == 0; a = (float)((s - 1) gamma), b = (float)((1 - eta) c);
+ *                        g = fma(a, fma(-b, u, d), p) [= p + (s - 1) gamma (d - (1 - eta) par), par = c u]; mom[b, i] = d when mom is given.
+ *                        x [B, C, HW] f32 (the state), t [B] f32; mom NULL or [B, n_g] f32, updated in place; momentum != 0 needs it.
+ *                        With eta = 1, r = 0, momentum = 0 it is cfg up to rounding.  x, t, mom are ignored by the other rules.
+ *   Channels k .. C-1 of out are pos widened to f32, bit for bit.  out may be pos itself when pos is f32; it overlaps nothing else.
+ *   Order: thread t of the sample's 1024 adds its 4-element groups t, t + 1024, ... in order, a wave joins its lanes in the xor butterfly
+ *   32 .. 1, the 16 wave sums are added as a chain.  It depends on n_g alone: the rows of sample b depend on that sample's inputs only (alone
+ *   or in a batch: same bits), two runs give the same bits, and so do the two access paths: 16-byte accesses (8 bytes of bf16) when
+ *   HW % 4 == 0 and every pointer is 16-byte (bf16: 8-byte) aligned, element accesses otherwise.  No atomics, no workspace. */
+#define LDMAE_GUIDE_CFG 0
+#define LDMAE_GUIDE_RESCALE 1
+#define LDMAE_GUIDE_APG 2
+int ldmae_guidance_combine(int rule, int in_dtype, const void* pos, const void* neg, const float* x, const float* t, float* mom, float* out,
+                           int B, int C, int HW, int k, float scale, float phi, float eta, float norm_threshold, float momentum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

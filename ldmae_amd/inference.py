@@ -15,6 +15,7 @@ for p in (_HERE, os.path.dirname(_HERE)):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from ldmae_amd.guidance import Guidance                      # noqa: E402
 from ldmae_amd.models.lightningdit import _act_dtype        # noqa: E402
 from ldmae_amd.tokenizer import models_mae                  # noqa: E402
 from ldmae_amd.train_accum import build_model               # noqa: E402
@@ -65,10 +66,15 @@ def build_sde_sampler(cfg, tr):
 
 @torch.no_grad()
 def sample_latents(model, sample_fn, n, cfg_scale, cfg_interval_start, device, num_classes=1000, generator=None, truncation=None,
-                   labels=None, cfg_interval=True):
+                   labels=None, cfg_interval=True, guidance=None):
     """inference.py:264-292: z ~ N(0,I); CFG on a doubled batch with the null class; Euler; drop the null half.
     `truncation`: the resampling loop of :266-272 (|z| > bound redrawn, at most 100 rounds).  `labels` / `cfg_interval=False`: the demo
-    branch (:219-232), fixed classes and guidance on every step."""
+    branch (:219-232), fixed classes and guidance on every step.
+    `guidance`: a function of ldmae_amd.guidance.Guidance.model_fn (the YAML key sample.guidance).  It replaces the cfg_scale branch: the state
+    is NOT doubled (the function runs the negative forward itself, inside its interval), so dopri5's error norm runs over the n kept samples --
+    a stated departure from the reference's doubled-batch norm.  cfg_scale / cfg_interval_start / cfg_interval are not read then."""
+    if guidance is not None:
+        guidance.guidance.check_sampler(sample_fn)          # a momentum under a solver with several evaluations per step: refused before the draw
     latent = model.x_embedder.img_size[0]
     z = torch.randn(n, model.in_channels, latent, latent, device=device, generator=generator)
     if truncation is not None:
@@ -81,7 +87,10 @@ def sample_latents(model, sample_fn, n, cfg_scale, cfg_interval_start, device, n
         y = torch.randint(0, num_classes, (n,), device=device, generator=generator)
     else:
         y = torch.as_tensor(labels, device=device, dtype=torch.long)
-    if cfg_scale > 1.0:
+    if guidance is not None:
+        guidance.reset()                     # the APG momentum belongs to one trajectory
+        out = sample_fn(z, guidance, y=y)[-1]
+    elif cfg_scale > 1.0:
         z = torch.cat([z, z], 0)
         y = torch.cat([y, torch.full((n,), num_classes, device=device)], 0)
         # dopri5's error norm runs over the whole doubled batch, as the reference's does: it gets forward_with_cfg at every evaluation
@@ -151,13 +160,16 @@ DEMO_LABELS = [975, 3, 207, 387, 388, 88, 979, 279]          # inference.py:223
 
 
 def sample_folder_name(cfg, ckpt_path, cfg_scale=None):
-    """The directory name rule of inference.py:45-52 (the FID tooling downstream finds the PNGs by it)."""
+    """The directory name rule of inference.py:45-52 (the FID tooling downstream finds the PNGs by it).  With the key sample.guidance the name
+    gains Guidance.folder_suffix(): the rule, the source, k and every parameter, so two settings never share a folder."""
     s = cfg['sample']
     method = ("sde-" if s.get('mode') == "SDE" else "") + s['sampling_method']          # the SDE's euler is not the ODE's: its own folder
     name = f"{cfg['model']['model_type'].replace('/', '-')}-ckpt-{ckpt_path.split('/')[-1].split('.')[0]}-{method}-{s['num_sampling_steps']}".lower()
     cfg_scale = s['cfg_scale'] if cfg_scale is None else cfg_scale
     if cfg_scale > 1.0:
         name += f"-interval{s.get('cfg_interval_start', 0):.2f}" + f"-cfg{cfg_scale:.2f}" + f"-shift{s.get('timestep_shift', 0):.2f}"
+    if s.get('guidance') is not None:
+        name += Guidance.from_config(cfg).folder_suffix()
     return name
 
 
@@ -206,12 +218,42 @@ def resolve_gemm_precision(cfg, flag=None):
     return mode
 
 
+GUIDANCE_NOTICE = "sample.guidance: the effect of the guidance rules (all-channel CFG, rescale, APG, autoguidance) on FID has not been measured"
+
+
+def build_guidance(cfg, model, device, gemm_precision=None):
+    """The guided model function of sample.guidance for `model`.  source auto: the guide is built from the same YAML with
+    guidance.guide_model_type, loaded from guidance.guide_ckpt as the main model is (guide_weights ema: the checkpoint's "ema" entry, or the
+    file itself when it is a bare state dict such as a post-hoc EMA reconstruction; model: its "model" entry), at the same gemm_precision."""
+    g = Guidance.from_config(cfg)
+    guide = None
+    if g.source == "auto":
+        gcfg = dict(cfg, model=dict(cfg['model'], model_type=g.guide_model_type))
+        guide = build_model(gcfg, learn_sigma=cfg['model'].get('learn_sigma', False))
+        ck = torch.load(g.guide_ckpt, map_location='cpu')
+        if g.guide_weights == "model":
+            if "model" not in ck:
+                raise KeyError(f"sample.guidance.guide_weights model: {g.guide_ckpt} has no 'model' entry")
+            ck = {k.replace('module.', ''): v for k, v in ck["model"].items()}
+        elif "ema" in ck:
+            ck = ck["ema"]
+        guide.load_state_dict(ck)
+        guide = guide.to(device).eval()
+        if gemm_precision is not None:
+            guide.set_gemm_precision(gemm_precision)
+    return g.model_fn(model, guide)
+
+
 def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", cfg_scale=None, demo=False, gemm_precision=None):
     """inference.py:40-300.  `out_dir=None` -> <train.output_dir>/<train.exp_name>/<sample_folder_name> as the reference; a folder that already
     holds more than `fid_num` PNGs is left alone (:69-77).  `demo=True`: the eight fixed classes, guidance on every step, unshifted grid, one
     2 x 4 sheet under ./demo_images (:54-57, :219-262) written by rank 0; returns None as the reference does."""
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     s = cfg['sample']
+    if s.get('guidance') is not None:                        # every refusal of the key happens here, before anything is loaded
+        if demo:
+            raise NotImplementedError("sample.guidance with --demo: the demo sheet is the reference's CFG; remove the key or --demo")
+        Guidance.from_config(cfg)
     cfg_scale = s['cfg_scale'] if cfg_scale is None else cfg_scale
     if out_dir is None:
         out_dir = os.path.join(cfg['train']['output_dir'], cfg['train']['exp_name'], sample_folder_name(cfg, ckpt_path, cfg_scale))
@@ -233,6 +275,11 @@ def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", 
         model.set_gemm_precision(gemm_precision)
         if rank == 0:
             print(MX8_NOTICE)
+    guided = None
+    if s.get('guidance') is not None:                        # opt-in: absent, nothing below differs from before the key existed
+        guided = build_guidance(cfg, model, device, gemm_precision)
+        if rank == 0:
+            print(GUIDANCE_NOTICE)
     if demo:                                                  # :54-57 -- the demo sheet is drawn with guidance on every step of the unshifted grid
         cfg = dict(cfg, sample=dict(s, cfg_interval_start=0, timestep_shift=0))
         s = cfg['sample']
@@ -278,7 +325,8 @@ def do_sample(cfg, ckpt_path, out_dir=None, num_samples=None, precision="bf16", 
     try:
         for it in range(total // (n * world)):
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=precision == "bf16"):
-                lat, _ = sample_latents(model, sample_fn, n, cfg_scale, s.get('cfg_interval_start', 0), device, cfg['data']['num_classes'], truncation=trunc)
+                lat, _ = sample_latents(model, sample_fn, n, cfg_scale, s.get('cfg_interval_start', 0), device, cfg['data']['num_classes'], truncation=trunc,
+                                        **({} if guided is None else {"guidance": guided}))
             solver = getattr(sample_fn, "__self__", None)
             if it == 0 and rank == 0 and getattr(solver, "sampler_type", None) == "dopri5":
                 print(f"dopri5 (atol {solver.atol:g}, rtol {solver.rtol:g}): nfe {solver.nfe}, accepted {solver.accepted}, rejected {solver.rejected}")
@@ -300,10 +348,28 @@ def build_parser():
     ap.add_argument('--out', type=str, default=None, help="default: <output_dir>/<exp_name>/<the reference's folder name>")
     ap.add_argument('--gemm_precision', type=str, default=None, choices=['mxfp8', 'none'],
                     help="block-GEMM arithmetic of the DiT (overrides the YAML key sample.gemm_precision); mxfp8: MX block-scaled fp8, forward-only bf16")
+    ap.add_argument('--guidance_rule', type=str, default=None, choices=['cfg', 'rescale', 'apg'], help="overrides the YAML key sample.guidance.rule")
+    ap.add_argument('--guidance_source', type=str, default=None, choices=['null_class', 'auto'], help="overrides sample.guidance.source")
+    ap.add_argument('--guidance_channels', type=str, default=None, help="overrides sample.guidance.channels: 'all' or an integer")
+    ap.add_argument('--guide_ckpt', type=str, default=None, help="overrides sample.guidance.guide_ckpt (the guiding model of source auto)")
     ap.add_argument('--mode', type=str, default=None, choices=['ODE', 'SDE'],
                     help="overrides the YAML key sample.mode; SDE: Euler-Maruyama / Heun with the optional keys sample.diffusion_form (default "
                          "sigma), diffusion_norm, last_step, last_step_size")
     return ap
+
+
+def apply_guidance_flags(c, a):
+    """The --guidance_* / --guide_ckpt flags over the YAML's sample.guidance, the way --mode overrides sample.mode; no flag: c itself."""
+    over = {k: v for k, v in (("rule", a.guidance_rule), ("source", a.guidance_source), ("channels", a.guidance_channels),
+                              ("guide_ckpt", a.guide_ckpt)) if v is not None}
+    if not over:
+        return c
+    if "channels" in over and over["channels"] != "all":
+        try:
+            over["channels"] = int(over["channels"])
+        except ValueError:
+            raise SystemExit(f"--guidance_channels {over['channels']!r}: 'all' or an integer")
+    return dict(c, sample=dict(c['sample'], guidance=dict(c['sample'].get('guidance') or {}, **over)))
 
 
 def main(argv=None):
@@ -311,6 +377,7 @@ def main(argv=None):
     c = yaml.safe_load(open(a.config))
     if a.mode is not None:
         c = dict(c, sample=dict(c['sample'], mode=a.mode))
+    c = apply_guidance_flags(c, a)
     if a.ckpt is None:
         assert 'ckpt_path' in c, "ckpt_path must be specified in config"
     # run_inference.sh passes --mixed_precision $PRECISION (default bf16) to the launcher, which exports ACCELERATE_MIXED_PRECISION; the

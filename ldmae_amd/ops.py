@@ -1106,6 +1106,56 @@ def row_mse(a, u, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- guidance rules of the sampler (csrc/guidance.hip)
+GUIDANCE_RULES = {"cfg": 0, "rescale": 1, "apg": 2}
+
+
+def guidance_combine(rule, pos, neg, scale, k=None, x=None, t=None, phi=0.7, eta=0.0, norm_threshold=0.0, momentum=0.0, mom=None, out=None):
+    """The guided velocity of `rule` ('cfg' / 'rescale' / 'apg': the contract of ldmae_guidance_combine) in one launch.  pos (main / conditional
+    output), neg (null-class / guide output) [B, C, H, W] f32 or bf16, same type; the first k channels (default: all C) are guided, the rest of
+    out is pos.  apg also takes the state x [B, C, H, W] f32, the times t [B] f32 and optionally the momentum buffer mom [B, k H W] f32, updated
+    in place (momentum != 0 needs it).  out: f32 [B, C, H, W], may be pos itself when pos is f32.  A tensor of another layout is copied first (the
+    DiT returns a permuted view)."""
+    if rule not in GUIDANCE_RULES:
+        raise RuntimeError(f"guidance_combine rule: {rule!r}, expected one of {sorted(GUIDANCE_RULES)}")
+    if pos.dim() != 4 or pos.numel() == 0:
+        raise RuntimeError(f"guidance_combine pos: shape {tuple(pos.shape)}, expected a non-empty [B, C, H, W]")
+    B, C, H, W = pos.shape
+    if neg.dim() == 4 and neg.shape[0] == B and neg.shape[2:] == pos.shape[2:] and neg.shape[1] != C:
+        raise RuntimeError(f"guidance_combine neg: {neg.shape[1]} channels against the {C} of pos: learn_sigma outputs (out_channels != in_channels) are not "
+                           "guided here; pass the velocity channels only")
+    k = C if k is None else k
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= C:
+        raise RuntimeError(f"guidance_combine k: {k!r} guided channels, expected an integer in 1 .. C = {C}")
+    aliased = out is pos
+    pos = _arg(pos, "guidance_combine pos", (torch.float32, torch.bfloat16), copy=not aliased)
+    neg = _arg(neg, "guidance_combine neg", pos.dtype, pos.shape, like=pos)
+    if rule == "rescale" and not 0.0 <= float(phi) <= 1.0:
+        raise RuntimeError(f"guidance_combine phi: {phi!r}, expected a value in [0, 1]")
+    if rule == "apg":
+        if float(norm_threshold) < 0.0:
+            raise RuntimeError(f"guidance_combine norm_threshold: {norm_threshold!r} must not be negative (0 = off)")
+        if x is None or t is None:
+            raise RuntimeError("guidance_combine: rule 'apg' needs the state x and the times t")
+        if x.dim() == 4 and x.shape[0] == B and x.shape[2:] == pos.shape[2:] and x.shape[1] != C:
+            raise RuntimeError(f"guidance_combine x: {x.shape[1]} channels against the {C} of pos: learn_sigma shapes (out_channels != in_channels) are "
+                               "not guided here")
+        x = _arg(x, "guidance_combine x", torch.float32, pos.shape, like=pos)
+        t = _arg(t, "guidance_combine t", torch.float32, (B,), like=pos)
+        if mom is None and float(momentum) != 0.0:
+            raise RuntimeError(f"guidance_combine mom: momentum = {momentum!r} needs the momentum buffer [B, k*H*W] = [{B}, {k * H * W}]")
+        _arg(mom, "guidance_combine mom", torch.float32, (B, k * H * W), out=True, like=pos)
+    else:
+        x = t = mom = None
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=pos.device)
+    else:
+        _arg(out, "guidance_combine out", torch.float32, pos.shape, out=True, like=pos)
+    call("ldmae_guidance_combine", GUIDANCE_RULES[rule], dt(pos.dtype), ptr(pos), ptr(neg), ptr(x), ptr(t), ptr(mom), ptr(out), B, C, H * W, k,
+         float(scale), float(phi), float(eta), float(norm_threshold), float(momentum), stream())
+    return out
+
+
 def check_crop_table(offsets, geom, blob_bytes):
     """The range checks ldmae_crop_resize_flip_u8 leaves to its caller, on the HOST copy of the tables: offsets [B] i64, geom [B, 8] i32 =
     (h, w, top, left, ch, cw, flip, 0).  Raises ValueError naming the first bad sample."""
