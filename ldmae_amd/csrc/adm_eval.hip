@@ -76,8 +76,7 @@ __global__ __launch_bounds__(256) void row_sqnorms_kernel(const float* __restric
     const double v = (double)p[d];
     s = fma(v, v, s);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   if (lane == 0) out[row] = (float)s;
 }
 
@@ -274,14 +273,9 @@ __global__ __launch_bounds__(PW_NT) void pairwise_kernel(typename PairArgsOf<MOD
             }
           }
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-      double* red = (double*)smem;                                         // the staging buffers are free: the K loop ended on a barrier
-      if (lane == 0) red[wave] = t;
-      __syncthreads();
+      t = block_sum(t, (double*)smem);      // the staging buffers are free: the K loop ended on a barrier; free again for the next tile on return
       const size_t row_tiles = gridDim.x / a.nsplit;
-      if (tid == 0) a.part[((size_t)blockIdx.y * row_tiles + rt) * col_tiles + ct] = (red[0] + red[1]) + (red[2] + red[3]);
-      __syncthreads();                                                     // red is read before the next tile's staging
+      if (tid == 0) a.part[((size_t)blockIdx.y * row_tiles + rt) * col_tiles + ct] = t;
     } else {
       // distances of the tile into LDS (the staging buffers are free: the K loop ended on a barrier); padding is +inf
 #pragma unroll
@@ -508,24 +502,6 @@ extern "C" int ldmae_kid_sums(const float* a, int Na, const float* b, int Nb, in
 // give NaN there); S[s, c] = sum over the rows of split s of p[i, c] in f64, summed over fixed 128-row chunks and then over the chunks in
 // order: bitwise reproducible, no atomics.
 constexpr int IS_CHUNK = 128;
-
-__device__ __forceinline__ float block_max(float v, float* red) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float r = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return r;
-}
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const T r = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return r;
-}
 
 __global__ __launch_bounds__(256) void is_softmax_kernel(const float* __restrict__ logits, int C, float* __restrict__ probs, double* __restrict__ h) {
   __shared__ float redf[4];

@@ -127,15 +127,21 @@ template <> struct Vec8<f16> {
   }
 };
 
-// four adjacent channels as floats from an f32 (16 B) or fp16 (8 B) tensor: the LPIPS heads and pool backward read either
+// four adjacent elements as floats from an f32 (16 B), fp16 or bf16 (8 B) tensor: the LPIPS heads and pool backward, the row reductions
 __device__ __forceinline__ float4 load4f(const float* p) { return *(const float4*)p; }
 __device__ __forceinline__ float4 load4f(const f16* p) {
   const f16x4 v = *(const f16x4*)p;
   return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
+__device__ __forceinline__ float4 load4f(const bf16* p) {
+  const bf16x4 v = *(const bf16x4*)p;
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
 
 // ---------------------------------------------------------------- wave / block reductions (wave = 64 lanes)
-__device__ __forceinline__ float wave_sum(float v) {
+// THE fixed-order sums of the library.  wave_sum: the xor butterfly 32, 16, 8, 4, 2, 1 over the 64 lanes, the result in
+// every lane; V is float, double, int or unsigned long long.
+template <typename V> __device__ __forceinline__ V wave_sum(V v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -160,6 +166,27 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+// block_sum / block_max: a block of exactly 256 threads, all of which call it; `slot` is 4 elements of LDS.  wave_sum, then the four wave
+// sums as (s0 + s1) + (s2 + s3); the result in every thread.  The second barrier stands AFTER the read: when the call returns no thread
+// reads the slot any more, so the next call on the same slot, or whatever else the memory is used for next, may write it at once.  (A
+// barrier before the write would serve two calls in a row as well, but not the caller whose slot is a buffer it fills again afterwards.)
+// The caller owes only that nothing else reads or writes the slot when the call begins.  Adds only: nothing here can be contracted.
+template <typename V> __device__ __forceinline__ V block_sum(V v, V* slot) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const V r = (slot[0] + slot[1]) + (slot[2] + slot[3]);
+  __syncthreads();
+  return r;
+}
+__device__ __forceinline__ float block_max(float v, float* slot) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float r = fmaxf(fmaxf(slot[0], slot[1]), fmaxf(slot[2], slot[3]));
+  __syncthreads();
+  return r;
 }
 // sum over a power-of-two sub-group of lanes (width <= 64)
 template <int W> __device__ __forceinline__ float group_sum(float v) {
@@ -210,6 +237,19 @@ void ldmae_prof_end(long idx, hipStream_t st);
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+// host predicates of the entry points: an address on a multiple of `bytes` (a power of two); two byte ranges that share nothing; two
+// ranges of n floats that are the same range or share nothing (in place is allowed, a partial overlap is not)
+static inline bool is_aligned(const void* p, uintptr_t bytes = 16) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+static inline bool disjoint(const void* a, size_t na, const void* b, size_t nb) {
+  return (const char*)a + na <= (const char*)b || (const char*)b + nb <= (const char*)a;
+}
+static inline bool same_or_disjoint(const float* a, const float* b, long n) { return a == b || a + n <= b || b + n <= a; }
+// (seed, counter) of a named Philox draw as the generator's two key and first two counter words (philox_normal.h)
+struct PhiloxWords {
+  unsigned k0, k1, c0, c1;
+  PhiloxWords(unsigned long long seed, unsigned long long counter)
+      : k0((unsigned)(seed & 0xffffffffu)), k1((unsigned)(seed >> 32)), c0((unsigned)(counter & 0xffffffffu)), c1((unsigned)(counter >> 32)) {}
+};
 // an int as a type: f(IC<hd>{}) hands a generic lambda a compile-time constant (the attention and GEMM launch dispatchers)
 template <int I> struct IC { static constexpr int value = I; };
 // a type as a value, and the LDMAE_* code of an element type

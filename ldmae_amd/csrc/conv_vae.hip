@@ -23,16 +23,7 @@ __device__ __forceinline__ float gn_act(float x, float mu, float rs, float ga, f
 // One block of 256 threads per (image, group); a group is HW pixels x cpg adjacent channels.  Two passes over the group (the second one hits
 // the L2): mean first, then the biased variance as the mean of (x - mean)^2, so no cancellation of large sums.  Summation order of either
 // pass (blocked, never one serial chain over the group): the cpg channels of a pixel are added first; a thread adds the pixel sums of pixels
-// tid, tid + 256, ... serially (at most HW / 256 terms); the 64 lanes of a wave are joined by a butterfly tree, the four waves pairwise.
-__device__ __forceinline__ float block_sum_256(float v, float* sh) {
-  v = wave_sum(v);
-  const int tid = threadIdx.x;
-  __syncthreads();                                         // sh may still be read from the previous reduction
-  if ((tid & 63) == 0) sh[tid >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
+// tid, tid + 256, ... serially (at most HW / 256 terms); the block is joined by block_sum of common.h (butterfly, then the four waves pairwise).
 template <bool VEC>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ mean, float* __restrict__ rstd, int HW, int C,
                                                        int G, float eps) {
@@ -51,7 +42,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     }
     s += t;
   }
-  const float mu = block_sum_256(s, sh) * inv_n;
+  const float mu = block_sum(s, sh) * inv_n;
   float q = 0.f;
   for (int p = tid; p < HW; p += 256) {
     const float* px = xb + (size_t)p * C;
@@ -67,7 +58,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     }
     q += t;
   }
-  const float var = block_sum_256(q, sh) * inv_n;
+  const float var = block_sum(q, sh) * inv_n;
   if (tid == 0) {
     mean[blockIdx.x] = mu;
     rstd[blockIdx.x] = 1.f / sqrtf(var + eps);
@@ -480,17 +471,14 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ s
   const int tid = threadIdx.x;
   float mx = -INFINITY;
   for (int j = tid; j < cols; j += 256) mx = fmaxf(mx, row[j] * scale);
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) sh[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  mx = block_max(mx, sh);
   float sum = 0.f;
   for (int j = tid; j < cols; j += 256) {
     const float e = expf(row[j] * scale - mx);
     row[j] = e;
     sum += e;
   }
-  sum = block_sum_256(sum, sh);
+  sum = block_sum(sum, sh);
   for (int j = tid; j < ld; j += 256) row[j] = j < cols ? row[j] / sum : 0.f;
 }
 

@@ -18,8 +18,6 @@ namespace {
 constexpr int GD_THREADS = 1024;
 constexpr int GD_WAVES = GD_THREADS / 64;
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 template <typename T, bool VEC> __device__ __forceinline__ void load_group(const T* p, int nv, float (&v)[4]) {
   if constexpr (VEC) {
     if constexpr (sizeof(T) == 4) {
@@ -46,17 +44,12 @@ template <bool VEC> __device__ __forceinline__ void store_group(float* p, int nv
   }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// s[j] <- the block's sum of s[j], the same value in every thread: butterfly, then the chain w0 + w1 + ... + w15
+// s[j] <- the block's sum of s[j], the same value in every thread: wave_sum, then the chain w0 + w1 + ... + w15 (1024 threads: this kernel's
+// own join, not the 256-thread block_sum of common.h)
 template <int N> __device__ __forceinline__ void block_sums_f64(double (&s)[N], double* red) {
 #pragma unroll
   for (int j = 0; j < N; ++j) {
-    s[j] = wave_sum_f64(s[j]);
+    s[j] = wave_sum(s[j]);
     if ((threadIdx.x & 63) == 0) red[j * GD_WAVES + (threadIdx.x >> 6)] = s[j];
   }
   __syncthreads();
@@ -216,10 +209,6 @@ __global__ __launch_bounds__(GD_THREADS) void guidance_kernel(GuideArgs a) {
   }
 }
 
-inline bool disjoint(const void* a, size_t na, const void* b, size_t nb) {
-  return (const char*)a + na <= (const char*)b || (const char*)b + nb <= (const char*)a;
-}
-
 }  // namespace
 
 extern "C" int ldmae_guidance_combine(int rule, int in_dtype, const void* pos, const void* neg, const float* x, const float* t, float* mom,
@@ -232,7 +221,7 @@ extern "C" int ldmae_guidance_combine(int rule, int in_dtype, const void* pos, c
   LDMAE_REQUIRE(k >= 1 && k <= C, "guidance_combine: k = %d guided channels, expected 1 .. C = %d", k, C);
   const long n = (long)C * HW, ng = (long)k * HW;
   const size_t esize = in_dtype == LDMAE_BF16 ? 2 : 4;
-  LDMAE_REQUIRE(aligned(pos, esize) && aligned(neg, esize) && aligned(out, 4), "guidance_combine: pos, neg and out must be aligned to their element size");
+  LDMAE_REQUIRE(is_aligned(pos, esize) && is_aligned(neg, esize) && is_aligned(out, 4), "guidance_combine: pos, neg and out must be aligned to their element size");
   const size_t in_bytes = (size_t)B * n * esize, out_bytes = (size_t)B * n * 4;
   const bool alias = (const void*)out == pos;
   LDMAE_REQUIRE(alias ? in_dtype == LDMAE_F32 : disjoint(out, out_bytes, pos, in_bytes), "guidance_combine: out may be pos itself (f32) but must not overlap it otherwise");
@@ -243,7 +232,7 @@ extern "C" int ldmae_guidance_combine(int rule, int in_dtype, const void* pos, c
   }
   if (rule == LDMAE_GUIDE_APG) {
     LDMAE_REQUIRE(x && t, "guidance_combine: apg needs the state x and the times t");
-    LDMAE_REQUIRE(aligned(x, 4) && aligned(t, 4) && (!mom || aligned(mom, 4)), "guidance_combine: x, t and the momentum buffer must be 4-byte aligned");
+    LDMAE_REQUIRE(is_aligned(x, 4) && is_aligned(t, 4) && (!mom || is_aligned(mom, 4)), "guidance_combine: x, t and the momentum buffer must be 4-byte aligned");
     LDMAE_REQUIRE(norm_threshold >= 0.f, "guidance_combine: norm_threshold = %g must not be negative", (double)norm_threshold);
     LDMAE_REQUIRE(mom || momentum == 0.f, "guidance_combine: momentum = %g needs the momentum buffer", (double)momentum);
     LDMAE_REQUIRE(disjoint(out, out_bytes, x, out_bytes), "guidance_combine: out overlaps x");
@@ -256,8 +245,8 @@ extern "C" int ldmae_guidance_combine(int rule, int in_dtype, const void* pos, c
     x = nullptr; t = nullptr; mom = nullptr;
   }
   // 4-element accesses: every sample (and its guided part) starts on a multiple of 4 elements of 16-byte (bf16: 8-byte) aligned storage
-  const bool vec = HW % 4 == 0 && aligned(pos, 4 * esize) && aligned(neg, 4 * esize) && aligned(out, 16) && (!x || aligned(x, 16)) &&
-                   (!mom || aligned(mom, 16));
+  const bool vec = HW % 4 == 0 && is_aligned(pos, 4 * esize) && is_aligned(neg, 4 * esize) && is_aligned(out, 16) && (!x || is_aligned(x, 16)) &&
+                   (!mom || is_aligned(mom, 16));
   GuideArgs a{pos, neg, x, t, mom, out, n, ng, scale, phi, eta, norm_threshold, momentum, alias ? 0 : 1};
   hipStream_t st = as_stream(stream);
   auto go = [&](auto tag) {

@@ -7,24 +7,6 @@
 
 namespace {
 
-// four per-wave values of a 256-thread block joined in one fixed order; every thread gets the result.  `slot` is 4 elements of LDS.
-template <typename V> __device__ __forceinline__ V block_join4(V v, V* slot) {
-  __syncthreads();                                  // the slot may still be read from the previous join
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (slot[0] + slot[1]) + (slot[2] + slot[3]);
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---------------------------------------------------------------- token_mean: out[b, d] = (1 / N) sum_n x[b, n, col0 + d]
 // A block owns 16 columns of one sample; 16 row groups of 16 lanes each add rows g, g + 16, ... in ascending order, thread g = 0 adds the 16
 // group sums in ascending order and divides once.
@@ -139,11 +121,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     m = fmaxf(m, xv);
     cnt += (c < C && (xv > ly || (xv == ly && c < (int)y))) ? 1 : 0;
   }
-  m = wave_max(m);
-  __syncthreads();
-  if ((tid & 63) == 0) redf[tid >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
+  m = block_max(m, redf);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < iters; ++i) {
@@ -153,8 +131,8 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     if (REG) v[REG ? i : 0] = e;
     s += e;
   }
-  s = block_join4(wave_sum(s), redf);
-  cnt = block_join4(wave_sum_i(cnt), redi);
+  s = block_sum(s, redf);
+  cnt = block_sum(cnt, redi);
   if (tid == 0) {
     loss[row] = (m + logf(s)) - ly;
     rank[row] = cnt;
@@ -189,16 +167,16 @@ __global__ __launch_bounds__(256) void lars_norms1_kernel(const float* __restric
       sd += (double)dp * (double)dp;
     }
   }
-  sp = block_join4(wave_sum_d(sp), red);
-  sd = block_join4(wave_sum_d(sd), red);
+  sp = block_sum(sp, red);
+  sd = block_sum(sd, red);
   if (threadIdx.x == 0) { part[2 * (long)blockIdx.x] = sp; part[2 * (long)blockIdx.x + 1] = sd; }
 }
 __global__ __launch_bounds__(256) void lars_norms2_kernel(const double* __restrict__ part, int nblk, float* __restrict__ norms) {
   __shared__ double red[4];
   double sp = 0.0, sd = 0.0;
   for (int j = threadIdx.x; j < nblk; j += 256) { sp += part[2 * (long)j]; sd += part[2 * (long)j + 1]; }
-  sp = block_join4(wave_sum_d(sp), red);
-  sd = block_join4(wave_sum_d(sd), red);
+  sp = block_sum(sp, red);
+  sd = block_sum(sd, red);
   if (threadIdx.x == 0) { norms[0] = (float)sqrt(sp); norms[1] = (float)sqrt(sd); }
 }
 // norms != NULL: a tensor of more than one dimension (weight decay and the trust ratio apply); NULL: a bias (neither does)
@@ -339,7 +317,7 @@ __global__ __launch_bounds__(256) void knn_vote_kernel(const float* __restrict__
     const float sc = scores[c];
     cnt += (sc > sy || (sc == sy && c < (int)y)) ? 1 : 0;
   }
-  cnt = block_join4(wave_sum_i(cnt), redi);
+  cnt = block_sum(cnt, redi);
   if (t == 0) rank[q] = cnt;
 }
 

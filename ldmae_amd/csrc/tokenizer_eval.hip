@@ -63,6 +63,21 @@ extern "C" int ldmae_lpips_prep(const float* input, const float* target, float* 
 // grid (chunks, B): block (k, b) walks pixels k * PPB + j * chunks * PPB of image b and writes its sum of d to part[b * chunks + k].
 constexpr int LP_NT = 256, LP_MAX_CHUNKS = 128;
 
+// *dst = the sum of acc over a 256-thread block, for the two f32 sums of this file (the LPIPS head, the SSIM tile): wave_sum, then thread 0
+// adds the four wave sums as the CHAIN ((w0 + w1) + w2) + w3.  Not block_sum of common.h, whose join is (w0 + w1) + (w2 + w3): another
+// rounding, and these kernels' results are recorded with this one.  One call per kernel: `red` (4 floats of LDS) is not reused.
+__device__ __forceinline__ void block_chain_sum(float acc, float* red, float* dst) {
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s += red[i];
+    *dst = s;
+  }
+}
+
 template <int C, typename T>
 __global__ __launch_bounds__(LP_NT) void lpips_layer_kernel(const T* __restrict__ f, const float* __restrict__ lw, float* __restrict__ part,
                                                             int B, int HW, int chunks) {
@@ -99,17 +114,7 @@ __global__ __launch_bounds__(LP_NT) void lpips_layer_kernel(const T* __restrict_
     }
     acc += lane_group_sum<L>(d) * (gl == 0 ? 1.f : 0.f);       // one lane per group counts the pixel
   }
-  // fixed-order block sum: wave butterfly, then the four wave sums in order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < LP_NT / 64; ++i) s += red[i];
-    part[(size_t)b * chunks + blockIdx.x] = s;
-  }
+  block_chain_sum(acc, red, part + (size_t)b * chunks + blockIdx.x);
 }
 
 // out[b] += (sum over k of part[b, k], in order, f64) / HW
@@ -224,16 +229,7 @@ __global__ __launch_bounds__(SS_NT) void ssim_tile_kernel(const float* __restric
     const float mx = m[0] + shx, my = m[1] + shy;
     acc += ((2.f * (mx * my) + a.c1) * (2.f * cxy + a.c2)) / ((mx * mx + my * my + a.c1) * (vx + vy + a.c2));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < SS_NT / 64; ++i) s += red[i];
-    part[(size_t)plane * tiles + tile] = s;
-  }
+  block_chain_sum(acc, red, part + (size_t)plane * tiles + tile);
 }
 
 // out[b] = sum over the C * tiles partials of image b (in order, f64) / (C (H - 10) (W - 10))
@@ -295,20 +291,6 @@ __device__ __forceinline__ int png_quantize(float x) {
 
 constexpr int QZ_NT = 256, QZ_MAX_BLOCKS = 256;
 
-__device__ __forceinline__ void block_sum_u64(unsigned long long acc, unsigned long long* red, unsigned long long* dst) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned long long s = 0;
-#pragma unroll
-    for (int i = 0; i < QZ_NT / 64; ++i) s += red[i];
-    *dst = s;
-  }
-}
-
 __global__ __launch_bounds__(QZ_NT) void recon_quantize_kernel(const float* __restrict__ dec, const float* __restrict__ ref, uint8_t* __restrict__ dec8,
                                                                uint8_t* __restrict__ ref8, unsigned long long* __restrict__ part, long HW, int blocks) {
   __shared__ unsigned long long red[QZ_NT / 64];
@@ -329,7 +311,8 @@ __global__ __launch_bounds__(QZ_NT) void recon_quantize_kernel(const float* __re
     }
     acc += s;
   }
-  block_sum_u64(acc, red, part + (size_t)b * blocks + blockIdx.x);
+  acc = block_sum(acc, red);                                // integers: no order to keep
+  if (threadIdx.x == 0) part[(size_t)b * blocks + blockIdx.x] = acc;
 }
 
 __global__ __launch_bounds__(QZ_NT) void sse_u8_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b8, unsigned long long* __restrict__ part,
@@ -343,7 +326,8 @@ __global__ __launch_bounds__(QZ_NT) void sse_u8_kernel(const uint8_t* __restrict
     const int d = (int)ap[i] - (int)bp[i];
     acc += (unsigned)(d * d);
   }
-  block_sum_u64(acc, red, part + (size_t)b * blocks + blockIdx.x);
+  acc = block_sum(acc, red);
+  if (threadIdx.x == 0) part[(size_t)b * blocks + blockIdx.x] = acc;
 }
 
 __global__ __launch_bounds__(64) void sse_finish_kernel(const unsigned long long* __restrict__ part, long long* __restrict__ sse, int B, int blocks) {

@@ -564,7 +564,7 @@ extern "C" int ldmae_conv3x3(const float* x, const float* w, const float* b, flo
 // coefficients read from the device (upstream gradient / (elements per patch * patch count): no host round trip).
 __global__ __launch_bounds__(256) void mae_loss_fwd_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
                                                            float* __restrict__ P, long n4, int C, int Hh, int Ww, int p) {
-  __shared__ float red[4][2];
+  __shared__ float red[2][4];
   const int W4 = Ww >> 2, gw = Ww / p;
   float am = 0.f, av = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
@@ -576,10 +576,9 @@ __global__ __launch_bounds__(256) void mae_loss_fwd_kernel(const float* __restri
     const float ss = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
     am += m * ss; av += (1.f - m) * ss;
   }
-  am = wave_sum(am); av = wave_sum(av);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = am; red[threadIdx.x >> 6][1] = av; }
-  __syncthreads();
-  if (threadIdx.x < 2) P[(size_t)blockIdx.x * 2 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  am = block_sum(am, red[0]);
+  av = block_sum(av, red[1]);
+  if (threadIdx.x == 0) { P[(size_t)blockIdx.x * 2] = am; P[(size_t)blockIdx.x * 2 + 1] = av; }
 }
 __global__ __launch_bounds__(256) void mae_loss_bwd_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
                                                            const float* __restrict__ coef, float* __restrict__ dx, long n4, int C, int Hh, int Ww, int p) {
@@ -682,10 +681,8 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_reduce_kernel(const float* __
   const int a = blockIdx.x;
   float s = 0.f;
   for (int g = threadIdx.x; g < G; g += 256) s += P[(size_t)g * NA + a];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { const float v = (red[0] + red[1]) + (red[2] + red[3]); if (a < NW) dw[a] = v; else db[a - NW] = v; }
+  const float v = block_sum(s, red);
+  if (threadIdx.x == 0) { if (a < NW) dw[a] = v; else db[a - NW] = v; }
 }
 constexpr int CONV_BWD_G = 1024;
 extern "C" long ldmae_conv3x3_bwd_workspace_bytes(int C) { return (long)CONV_BWD_G * (C * C * 9 + C) * 4; }

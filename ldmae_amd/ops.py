@@ -1089,19 +1089,26 @@ def fm_valid_plan(stored, idx, t, lat_mean=None, lat_std=None, multiplier=1.0, s
     return xt, ut
 
 
+def _row_reduce_out(op, partials, a, out):
+    """What rowdot and row_mse share once their two operands [B, ...] are checked: B and the row length m, the result out [B] (checked, or made
+    here) and the workspace of partial sums that `partials` (the entry's own ldmae_*_partials) sizes -> (B, m, out, partial).  No string is
+    built unless something is wrong: the two run once per model evaluation."""
+    if a.dim() < 1 or a.numel() == 0:
+        raise RuntimeError(f"{op}: two non-empty tensors of at least one dimension expected, got {tuple(a.shape)}")
+    B, m = a.shape[0], a.numel() // a.shape[0]
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=a.device)
+    else:
+        _arg(out, op + " out", torch.float32, numel=B, out=True, like=a)
+    return B, m, out, torch.empty(int(partials(B, m)), dtype=torch.float32, device=a.device)
+
+
 def row_mse(a, u, out=None):
     """out[b] = mean over everything but dim 0 of (float(a[b]) - u[b])^2: mean_flat((a - u) ** 2) with a f32 or bf16 and u f32, in f32, as a
     two-stage fixed-order sum (bitwise reproducible).  A tensor of another layout is copied first (the DiT returns a permuted view)."""
     a = _arg(a, "row_mse a", (torch.float32, torch.bfloat16))
     u = _arg(u, "row_mse u", torch.float32, a.shape, like=a)
-    if a.dim() < 1 or a.numel() == 0:
-        raise RuntimeError(f"row_mse: two non-empty tensors of at least one dimension expected, got {tuple(a.shape)}")
-    B, m = a.shape[0], a.numel() // a.shape[0]
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=a.device)
-    else:
-        _arg(out, "row_mse out", torch.float32, numel=B, out=True, like=a)
-    partial = torch.empty(int(L.load().ldmae_row_mse_partials(B, m)), dtype=torch.float32, device=a.device)
+    B, m, out, partial = _row_reduce_out("row_mse", L.load().ldmae_row_mse_partials, a, out)
     call("ldmae_row_mse", dt(a.dtype), ptr(a), ptr(u), ptr(out), B, m, ptr(partial), stream())
     return out
 
@@ -2259,14 +2266,7 @@ def rowdot(a, b=None, out=None):
     b = a if b is None else b
     _arg(a, "rowdot a", torch.float32, copy=False)
     _arg(b, "rowdot b", torch.float32, a.shape, copy=False, like=a)
-    if a.dim() < 1 or a.numel() == 0:
-        raise RuntimeError(f"rowdot: two non-empty tensors of at least one dimension expected, got {tuple(a.shape)}")
-    B, m = a.shape[0], a.numel() // a.shape[0]
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=a.device)
-    else:
-        _arg(out, "rowdot out", torch.float32, numel=B, out=True, like=a)
-    partial = torch.empty(int(L.load().ldmae_rowdot_partials(B, m)), dtype=torch.float32, device=a.device)
+    B, m, out, partial = _row_reduce_out("rowdot", L.load().ldmae_rowdot_partials, a, out)
     call("ldmae_rowdot_f32", ptr(a), ptr(b), ptr(out), B, m, ptr(partial), stream())
     return out
 
