@@ -7,6 +7,7 @@ PyTorch: if the library is missing, or a tensor is on the CPU, they raise.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import weakref
 
@@ -14,7 +15,7 @@ import torch
 
 from . import _lib as L
 from ._lib import (BF16, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_POS, EPI_F16_INF, EPI_GATE_RES, EPI_GELU_BWD, EPI_HALF_LINES, EPI_SWIGLU, EPI_SWIGLU_BWD, EPI_TILE_LAUNCH, F32, call, dt,
-                   ptr, stream)
+                   ptr)
 
 mx8_launch_counts = L.mx8_launch_counts      # the MXFP8 sampling mode's own counters (quantise, norm + quantise, GEMM)
 launch_counts = L.launch_counts      # launch counts by kernel family (which arithmetic type, which GEMM form the calls were dispatched to)
@@ -22,11 +23,29 @@ launch_counts = L.launch_counts      # launch counts by kernel family (which ari
 _ws = {}
 
 
+def stream(device=None):
+    """The handle of torch's current stream on `device` (default: the current device) -- torch.cuda.current_stream(device).cuda_stream, as
+    _lib.stream() returns it, without the torch.cuda.Stream object that call builds for every wrapper call.  It and _ws_bytes below pay for the
+    argument checks: with the checks alone every wrapper of the train steps costs about 2 to 7 us of host time more than before it had them, far out
+    of the run-to-run spread; this saves 2.2 to 2.5 us per call, _ws_bytes about 2 us per backward wrapper (profiles/ops_args_host.txt)."""
+    if device is not None and not isinstance(device, torch.device):
+        device = torch.device(device)
+    idx = None if device is None else device.index
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device() if idx is None else idx)
+
+
+@functools.lru_cache(maxsize=1024)
+def _ws_bytes(entry, *dims):
+    """The scratch size an entry point asks for (every ldmae_*_workspace_bytes query of this file): a pure function of the extents, asked of
+    the library once per shape instead of once per call."""
+    return getattr(L.load(), entry)(*dims)
+
+
 def workspace(nbytes: int, device, slot: str = "main") -> torch.Tensor:
     """Grow-only f32 scratch buffer per (device, slot, STREAM): the library's entry points take their scratch from the caller and use it only inside
     the launches they enqueue, so two calls may share a buffer exactly when they are ordered on one stream -- work enqueued on different streams
     (the weight-gradient side stream, a data-parallel reducer, two modules driven from two host threads) gets buffers of its own."""
-    key = (device, slot, torch.cuda.current_stream(device).cuda_stream)
+    key = (device, slot, stream(device))
     n = max(1, (int(nbytes) + 3) // 4)
     t = _ws.get(key)
     if t is None or t.numel() < n:
@@ -35,8 +54,10 @@ def workspace(nbytes: int, device, slot: str = "main") -> torch.Tensor:
     return t
 
 
-def _c(t):
-    return t if t is None or t.is_contiguous() else t.contiguous()
+_F32_BF16 = (torch.float32, torch.bfloat16)                       # the dtype sets the entry points dispatch on (include/ldmae_hip.h: the dtype codes)
+_B16 = (torch.bfloat16, torch.float16)
+_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
+_FLAGS = (torch.uint8, torch.bool)                                # one byte per element
 
 
 def _arg(t, what, dtype=None, shape=None, rows=False, out=False, numel=None, like=None, align=0, at_least=0, copy=True):
@@ -57,7 +78,8 @@ def _arg(t, what, dtype=None, shape=None, rows=False, out=False, numel=None, lik
             or at_least and t.numel() < at_least or like is not None and t.device != like.device or align and t.data_ptr() % align):
         raise _refusal(t, what, dtype, shape, rows, out, numel, like, align, at_least, copy)
     if rows:
-        ok = t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+        st, sh = t.stride(), t.shape
+        ok = len(st) == 2 and (st[1] == 1 or sh[1] <= 1) and (st[0] >= sh[1] or sh[0] <= 1)
     else:
         ok = t.is_contiguous()
     if ok:
@@ -101,7 +123,12 @@ def _refusal(t, what, dtype, shape, rows, out, numel, like, align, at_least, cop
 
 def _shape_fits(got, want):
     """Slow path of _arg's shape check: `want` has wildcard entries (anything that is no int), or is no tuple."""
-    return len(got) == len(want) and all(not isinstance(w, int) or w == g for g, w in zip(got, want))
+    if len(got) != len(want):
+        return False
+    for g, w in zip(got, want):                      # (a plain loop: the anchors of the training path come here on every call)
+        if w != g and isinstance(w, int):
+            return False
+    return True
 
 
 def _shape_text(shape):
@@ -116,6 +143,23 @@ def _ld(t):
 def _mod_ld(a, b=None):
     """Row stride of a modulation pair, (shift, scale) or (dshift, dscale) -- [B, D] views of one tensor: the first one given, 0 with neither."""
     return a.stride(0) if a is not None else (b.stride(0) if b is not None else 0)
+
+
+def _mod_views(a, b, what_a, what_b, B, D, like, out=False):
+    """A modulation pair -- (shift, scale) or (dshift, dscale); either may be None -- as the row kernels address it: two [B, D] f32 views read
+    in place (copy=False) at ONE row stride, which is returned (_mod_ld)."""
+    a = _arg(a, what_a, torch.float32, (B, D), rows=True, out=out, like=like, copy=False)
+    b = _arg(b, what_b, torch.float32, (B, D), rows=True, out=out, like=like, copy=False)
+    if a is not None and b is not None and B > 1 and a.stride(0) != b.stride(0):
+        raise RuntimeError(f"{what_b}: row stride {b.stride(0)} against {a.stride(0)} of its partner (need two views at one row stride)")
+    return _mod_ld(a, b)
+
+
+def _batches(op, M, rows_per_batch):
+    """B of M = B * rows_per_batch token rows (the rows of the modulation and gate views)."""
+    if rows_per_batch <= 0 or M % rows_per_batch:
+        raise RuntimeError(f"{op}: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
+    return M // rows_per_batch
 
 
 def _pair(a, b, what):
@@ -220,7 +264,7 @@ def gemm_nt(a, b, bias=None, out_dtype=None, out=None, beta=0.0, grad=False):
     if out is None:
         out = torch.empty(M, N, dtype=out_dtype or a.dtype, device=a.device)
     else:
-        _arg(out, "gemm_nt out", out_dtype, (M, N), rows=True, out=True)
+        _arg(out, "gemm_nt out", out_dtype or (a.dtype, torch.float32), (M, N), rows=True, out=True)
     call("ldmae_gemm_nt", dt(a.dtype), dt(out.dtype), EPI_BIAS | _launch_flag() | _grad_flag(out.dtype, grad), ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), _ld(out),
          M, N, K, ptr(bias), float(beta), None, None, None, 0, 0, stream())
     return out
@@ -233,11 +277,10 @@ def gemm_nt_gate_res(a, b, bias, xin, gate, rows_per_batch, save_y=True, xout=No
     a, b = _pair(a, b, "gemm_nt_gate_res")
     M, K = a.shape
     N = b.shape[0]
-    if rows_per_batch <= 0 or M % rows_per_batch:
-        raise RuntimeError(f"gemm_nt_gate_res: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
+    nb = _batches("gemm_nt_gate_res", M, rows_per_batch)
     bias = _arg(bias, "gemm_nt_gate_res bias", torch.float32, (N,))
     xin = _arg(xin, "gemm_nt_gate_res xin", torch.float32, numel=M * N)
-    gate = _arg(gate, "gemm_nt_gate_res gate", torch.float32, (M // rows_per_batch, N), rows=True)
+    gate = _arg(gate, "gemm_nt_gate_res gate", torch.float32, (nb, N), rows=True)
     y_dtype = y_dtype or a.dtype
     y = torch.empty(M, N, dtype=y_dtype, device=a.device) if save_y else None
     if xout is None:
@@ -328,7 +371,11 @@ def gemm_nt_qkv_rope(a, w, bias, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, store_
     what qknorm_rope_fwd makes of the stored q / k.  wq = wk = None: RoPE only.  Call gemm_nt_qkv_rope_ok first."""
     a, w = _pair(a, w, "gemm_nt_qkv_rope")
     M, K = a.shape
-    bias = _arg(bias, "gemm_nt_qkv_rope bias", torch.float32, (3 * H * hd,))
+    if M != B * N or w.shape[0] != 3 * H * hd:
+        raise RuntimeError(f"gemm_nt_qkv_rope: operands {tuple(a.shape)} and {tuple(w.shape)} must be [B*N, K] and [3*H*hd, K] = [{B * N}, K] and [{3 * H * hd}, K]")
+    bias = _arg(bias, "gemm_nt_qkv_rope bias", torch.float32, (3 * H * hd,), like=a)
+    wq, wk = _arg(wq, "gemm_nt_qkv_rope wq", torch.float32, (hd,), like=a), _arg(wk, "gemm_nt_qkv_rope wk", torch.float32, (hd,), like=a)
+    cos, sin = _arg(cos, "gemm_nt_qkv_rope cos", torch.float32, (N, hd), like=a), _arg(sin, "gemm_nt_qkv_rope sin", torch.float32, (N, hd), like=a)
     qkv = torch.empty(M, 3 * H * hd, dtype=a.dtype, device=a.device)
     q2 = torch.empty(B, H, N, hd, dtype=a.dtype, device=a.device)
     k2 = torch.empty_like(q2)
@@ -354,15 +401,18 @@ def mx8_quantize(x):
 
 def rmsnorm_modulate_fwd_mx8(x, w, shift, scale, rows_per_batch, eps=1e-6):
     """(q, scales, rstd): rmsnorm_modulate_fwd(..., torch.bfloat16) and mx8_quantize of its output in one kernel, bitwise the pair."""
+    x = _arg(x, "rmsnorm_modulate_fwd_mx8 x", torch.float32, ("M", "D"))
     M, D = x.shape
     if w is None:
         raise RuntimeError("rmsnorm_modulate_fwd_mx8: needs the RMSNorm weight (the LayerNorm form is not built in this mode)")
     if D % 128:
         raise RuntimeError(f"rmsnorm_modulate_fwd_mx8: D={D} is not a multiple of 128")
+    B = _batches("rmsnorm_modulate_fwd_mx8", M, rows_per_batch)
+    w = _arg(w, "rmsnorm_modulate_fwd_mx8 w", torch.float32, (D,), like=x)
+    ld = _mod_views(shift, scale, "rmsnorm_modulate_fwd_mx8 shift", "rmsnorm_modulate_fwd_mx8 scale", B, D, x)
     q = torch.empty(M, D, dtype=torch.uint8, device=x.device)
     sc = torch.empty(M, D // 32, dtype=torch.uint8, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    ld = _mod_ld(shift, scale)
     call("ldmae_rmsnorm_modulate_fwd_mx8", ptr(x), ptr(w), ptr(shift), ptr(scale), ld, ptr(q), ptr(sc), ptr(rstd), M, D, rows_per_batch, eps, stream())
     return q, sc, rstd
 
@@ -401,11 +451,10 @@ def gemm_nt_gate_res_mx8(aq, asc, wq, wsc, bias, xin, gate, rows_per_batch, save
     aq, asc, wq, wsc = _mx8_pair(aq, asc, wq, wsc, "gemm_nt_gate_res_mx8")
     M, K = aq.shape
     N = wq.shape[0]
-    if rows_per_batch <= 0 or M % rows_per_batch:
-        raise RuntimeError(f"gemm_nt_gate_res_mx8: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
+    nb = _batches("gemm_nt_gate_res_mx8", M, rows_per_batch)
     bias = _arg(bias, "gemm_nt_gate_res_mx8 bias", torch.float32, (N,))
     xin = _arg(xin, "gemm_nt_gate_res_mx8 xin", torch.float32, numel=M * N)
-    gate = _arg(gate, "gemm_nt_gate_res_mx8 gate", torch.float32, (M // rows_per_batch, N), rows=True)
+    gate = _arg(gate, "gemm_nt_gate_res_mx8 gate", torch.float32, (nb, N), rows=True)
     y = torch.empty(M, N, dtype=y_dtype, device=aq.device) if save_y else None
     if xout is None:
         xout = torch.empty(M, N, dtype=torch.float32, device=aq.device)
@@ -445,7 +494,11 @@ def gemm_nt_qkv_rope_mx8(aq, asc, wq, wsc, bias, nwq, nwk, cos, sin, B, N, H, hd
     gemm_nt_qkv_rope_mx8_ok first."""
     aq, asc, wq, wsc = _mx8_pair(aq, asc, wq, wsc, "gemm_nt_qkv_rope_mx8")
     M, K = aq.shape
-    bias = _arg(bias, "gemm_nt_qkv_rope_mx8 bias", torch.float32, (3 * H * hd,))
+    if M != B * N or wq.shape[0] != 3 * H * hd:
+        raise RuntimeError(f"gemm_nt_qkv_rope_mx8: operands {tuple(aq.shape)} and {tuple(wq.shape)} must be [B*N, K] and [3*H*hd, K] = [{B * N}, K] and [{3 * H * hd}, K]")
+    bias = _arg(bias, "gemm_nt_qkv_rope_mx8 bias", torch.float32, (3 * H * hd,), like=aq)
+    nwq, nwk = _arg(nwq, "gemm_nt_qkv_rope_mx8 nwq", torch.float32, (hd,), like=aq), _arg(nwk, "gemm_nt_qkv_rope_mx8 nwk", torch.float32, (hd,), like=aq)
+    cos, sin = _arg(cos, "gemm_nt_qkv_rope_mx8 cos", torch.float32, (N, hd), like=aq), _arg(sin, "gemm_nt_qkv_rope_mx8 sin", torch.float32, (N, hd), like=aq)
     qkv = torch.empty(M, 3 * H * hd, dtype=torch.bfloat16, device=aq.device)
     q2 = torch.empty(B, H, N, hd, dtype=torch.bfloat16, device=aq.device)
     k2 = torch.empty_like(q2)
@@ -495,7 +548,7 @@ def gemm_tn(a, b, out=None, beta=0.0, with_bias=False, ws_slot="tn", dbias_out=N
         # the C entry applies ONE beta to C and to dbias: a fresh bias-gradient buffer must be zero when the caller accumulates into `out`
         dbias = (torch.zeros if beta != 0.0 else torch.empty)(N, dtype=torch.float32, device=a.device) if with_bias else None
     d = dt(a.dtype)
-    nb = max(L.load().ldmae_gemm_tn_workspace_bytes(d, M, N, K), L.load().ldmae_colsum_workspace_bytes(M, N) if with_bias else 0)
+    nb = max(_ws_bytes("ldmae_gemm_tn_workspace_bytes", d, M, N, K), _ws_bytes("ldmae_colsum_workspace_bytes", M, N) if with_bias else 0)
     ws = workspace(nb, a.device, ws_slot)
     call("ldmae_gemm_tn", d, ptr(a), _ld(a), ptr(b), _ld(b), ptr(out), ptr(dbias), M, N, K, float(beta), ptr(ws), ws.numel() * 4,
          stream())
@@ -503,21 +556,21 @@ def gemm_tn(a, b, out=None, beta=0.0, with_bias=False, ws_slot="tn", dbias_out=N
 
 
 def colsum(x, out=None, beta=0.0):
-    x = _arg(x, "colsum x", rows=True)
+    x = _arg(x, "colsum x", _FLOATS, ("M", "N"), rows=True)
     M, N = x.shape
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=x.device)
         beta = 0.0
     else:
         _arg(out, "colsum out", torch.float32, (N,), out=True)
-    ws = workspace(L.load().ldmae_colsum_workspace_bytes(M, N), x.device, "colsum")
+    ws = workspace(_ws_bytes("ldmae_colsum_workspace_bytes", M, N), x.device, "colsum")
     call("ldmae_colsum", dt(x.dtype), ptr(x), _ld(x), M, N, ptr(out), float(beta), ptr(ws), stream())
     return out
 
 
 def cast_weight(w, dtype, transposed=True, straight=True):
     """f32 master weight [R,C] -> (copy in `dtype` or None, [C,R] transposed copy or None)."""
-    w = _arg(w, "cast_weight w", torch.float32)
+    w = _arg(w, "cast_weight w", torch.float32, ("R", "C"))
     R, C = w.shape
     dst = torch.empty(R, C, dtype=dtype, device=w.device) if straight else None
     dstT = torch.empty(C, R, dtype=dtype, device=w.device) if transposed else None
@@ -528,8 +581,9 @@ def cast_weight(w, dtype, transposed=True, straight=True):
 def cast(x, dtype):
     if x.dtype == dtype:
         return x
+    x = _arg(x, "cast x", _FLOATS)
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
-    call("ldmae_cast", dt(x.dtype), dt(dtype), ptr(_c(x)), ptr(out), x.numel(), stream())
+    call("ldmae_cast", dt(x.dtype), dt(dtype), ptr(x), ptr(out), x.numel(), stream())
     return out
 
 
@@ -543,11 +597,12 @@ def thin_ok(N, K):
 
 def thin_nt(t, w, bias=None, pos=None, rows_per_batch=0, out_dtype=torch.float32):
     """out[M,N] = t[M,K] @ w[N,K]^T + bias (+ pos[row % rows_per_batch]) for K = 16 / 32, f32 inputs; one streaming pass."""
+    t = _arg(t, "thin_nt t", torch.float32, ("M", "K"))
     M, K = t.shape
+    w = _arg(w, "thin_nt w", torch.float32, ("N", K), like=t)
     N = w.shape[0]
-    t, w = _arg(t, "thin_nt t", torch.float32), _arg(w, "thin_nt w", torch.float32, (N, K))
-    bias = _arg(bias, "thin_nt bias", torch.float32, (N,))
-    pos = _arg(pos, "thin_nt pos", torch.float32, numel=rows_per_batch * N)
+    bias = _arg(bias, "thin_nt bias", torch.float32, (N,), like=t)
+    pos = _arg(pos, "thin_nt pos", torch.float32, numel=rows_per_batch * N, like=t)
     out = torch.empty(M, N, dtype=out_dtype, device=t.device)
     call("ldmae_thin_nt", dt(out_dtype), ptr(t), ptr(w), ptr(bias), ptr(pos), ptr(out), M, N, K,
          int(rows_per_batch), stream())
@@ -556,24 +611,25 @@ def thin_nt(t, w, bias=None, pos=None, rows_per_batch=0, out_dtype=torch.float32
 
 def thin_tn(g, t, with_bias=True):
     """(dW[N,K] = g[M,N]^T @ t[M,K], column sums of g or None) for K = 16 / 32, f32; one pass over g."""
+    g = _arg(g, "thin_tn g", torch.float32, ("M", "N"))
     M, N = g.shape
+    t = _arg(t, "thin_tn t", torch.float32, (M, "K"), like=g)
     K = t.shape[1]
-    g, t = _arg(g, "thin_tn g", torch.float32), _arg(t, "thin_tn t", torch.float32, (M, K))
     dW = torch.empty(N, K, dtype=torch.float32, device=g.device)
     db = torch.empty(N, dtype=torch.float32, device=g.device) if with_bias else None
-    ws = workspace(L.load().ldmae_thin_tn_workspace_bytes(M, N, K), g.device)
+    ws = workspace(_ws_bytes("ldmae_thin_tn_workspace_bytes", M, N, K), g.device)
     call("ldmae_thin_tn", ptr(g), ptr(t), ptr(dW), ptr(db), M, N, K, 0.0, ptr(ws), ws.numel() * 4, stream())
     return dW, db
 
 
 def multi_add_(dsts, srcs):
     """dsts[i] += srcs[i] (contiguous f32 tensors of equal sizes pairwise), one launch."""
-    import ctypes
     k = len(dsts)
-    srcs = [_c(s_) for s_ in srcs]
-    for d_, s_ in zip(dsts, srcs):
-        if d_.dtype != torch.float32 or s_.dtype != torch.float32 or d_.numel() != s_.numel() or not d_.is_contiguous():
-            raise RuntimeError("multi_add_: contiguous f32 pairs of equal size expected")
+    if len(srcs) != k:
+        raise RuntimeError(f"multi_add_: {k} destinations with {len(srcs)} sources")
+    for d_ in dsts:
+        _arg(d_, "multi_add_ dst (contiguous f32 pairs of equal size)", torch.float32, out=True, like=dsts[0])
+    srcs = [_arg(s_, "multi_add_ src (contiguous f32 pairs of equal size)", torch.float32, numel=d_.numel(), like=d_) for d_, s_ in zip(dsts, srcs)]
     da = (ctypes.c_void_p * k)(*[d_.data_ptr() for d_ in dsts])
     sa = (ctypes.c_void_p * k)(*[s_.data_ptr() for s_ in srcs])
     na = (ctypes.c_long * k)(*[d_.numel() for d_ in dsts])
@@ -582,13 +638,12 @@ def multi_add_(dsts, srcs):
 
 def cast_stack(tensors, dtype):
     """Equally shaped contiguous f32 tensors -> one stacked [len * rows, cols] tensor in `dtype`, one launch."""
-    import ctypes
     t0 = tensors[0]
     n_each = t0.numel()
+    srcs = [_arg(t, "cast_stack source (f32 tensors of one size)", torch.float32, numel=n_each, like=t0) for t in tensors]
+    if t0.dim() < 1:
+        raise RuntimeError("cast_stack source (f32 tensors of one size): at least one dimension expected")
     out = torch.empty((len(tensors) * t0.shape[0],) + tuple(t0.shape[1:]), dtype=dtype, device=t0.device)
-    srcs = [_c(t) for t in tensors]
-    if any(t.dtype != torch.float32 or t.numel() != n_each for t in srcs):
-        raise RuntimeError("cast_stack: f32 tensors of one size expected")
     arr = (ctypes.c_void_p * len(srcs))(*[t.data_ptr() for t in srcs])
     call("ldmae_cast_stack", dt(dtype), arr, len(srcs), n_each, ptr(out), stream())
     return out
@@ -598,10 +653,13 @@ def cast_stack(tensors, dtype):
 def rmsnorm_modulate_fwd(x, w, shift, scale, rows_per_batch, out_dtype, eps=1e-6):
     """modulate(norm(x), shift, scale) (lightningdit.py:26-30,248-249).  w: the RMSNorm weight; w=None: nn.LayerNorm(elementwise_affine=False)
     -- the blocks built with use_rmsnorm=False (:200-201) -- on the same kernels (the norm of the centred row)."""
+    x = _arg(x, "rmsnorm_modulate_fwd x", torch.float32, ("M", "D"))
     M, D = x.shape
+    B = _batches("rmsnorm_modulate_fwd", M, rows_per_batch)
+    w = _arg(w, "rmsnorm_modulate_fwd w", torch.float32, (D,), like=x)
+    ld = _mod_views(shift, scale, "rmsnorm_modulate_fwd shift", "rmsnorm_modulate_fwd scale", B, D, x)
     out = torch.empty(M, D, dtype=out_dtype, device=x.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    ld = _mod_ld(shift, scale)
     if w is None:
         call("ldmae_layernorm_modulate_fwd", dt(out_dtype), ptr(x), ptr(shift), ptr(scale), ld, ptr(out), ptr(rstd), M, D, rows_per_batch, eps, stream())
         return out, rstd
@@ -616,30 +674,47 @@ def res_rmsnorm_modulate_fwd(x, ya, gate_a, yb=None, gate_b=None, w=None, shift=
     -> (xout or None, xm or None, rstd or None) with xout = r (f32) and (xm, rstd) = rmsnorm_modulate_fwd(r, w, shift, scale) in ya's
     type.  ya / yb: the Linear outputs as stored (bf16 / fp16); gates [B, D] f32 views (any row stride).  Bitwise gemm_nt_gate_res's
     residual followed by rmsnorm_modulate_fwd."""
+    x = _arg(x, "res_rmsnorm_modulate_fwd x", torch.float32, ("M", "D"))
     M, D = x.shape
-    if ya.dtype not in (torch.bfloat16, torch.float16) or (yb is not None and yb.dtype != ya.dtype):
-        raise RuntimeError("res_rmsnorm_modulate_fwd: bfloat16 or float16 branch outputs of one type expected")
     if not (want_xout or want_norm):
         raise RuntimeError("res_rmsnorm_modulate_fwd: nothing requested (want_xout / want_norm)")
-    if rows_per_batch <= 0 or M % rows_per_batch:
-        raise RuntimeError(f"res_rmsnorm_modulate_fwd: M={M} is not a multiple of rows_per_batch={rows_per_batch}")
-    B = M // rows_per_batch
-    x = _arg(x, "res_rmsnorm_modulate_fwd x", torch.float32, (M, D))
-    ya = _arg(ya, "res_rmsnorm_modulate_fwd ya", None, (M, D))
-    yb = _arg(yb, "res_rmsnorm_modulate_fwd yb", None, (M, D))
-    gate_a = _arg(gate_a, "res_rmsnorm_modulate_fwd gate_a", torch.float32, (B, D), rows=True)
-    gate_b = _arg(gate_b, "res_rmsnorm_modulate_fwd gate_b", torch.float32, (B, D), rows=True)
+    B = _batches("res_rmsnorm_modulate_fwd", M, rows_per_batch)
+    ya = _arg(ya, "res_rmsnorm_modulate_fwd ya (bfloat16 or float16 branch outputs of one type)", _B16, (M, D), like=x)
+    yb = _arg(yb, "res_rmsnorm_modulate_fwd yb (bfloat16 or float16 branch outputs of one type)", ya.dtype, (M, D), like=x)
+    gate_a = _arg(gate_a, "res_rmsnorm_modulate_fwd gate_a", torch.float32, (B, D), rows=True, like=x)
+    gate_b = _arg(gate_b, "res_rmsnorm_modulate_fwd gate_b", torch.float32, (B, D), rows=True, like=x)
     xout = torch.empty(M, D, dtype=torch.float32, device=x.device) if want_xout else None
     out = rstd = None
     ld = 0
     if want_norm:
+        w = _arg(w, "res_rmsnorm_modulate_fwd w", torch.float32, (D,), like=x)
+        ld = _mod_views(shift, scale, "res_rmsnorm_modulate_fwd shift", "res_rmsnorm_modulate_fwd scale", B, D, x)
         out = torch.empty(M, D, dtype=ya.dtype, device=x.device)
         rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        ld = _mod_ld(shift, scale)
+    else:
+        w = shift = scale = None
     call("ldmae_res_rmsnorm_modulate_fwd", dt(ya.dtype), ptr(x), ptr(ya), ptr(gate_a), _ld(gate_a), ptr(yb), ptr(gate_b),
-         _ld(gate_b) if gate_b is not None else 0, ptr(xout), ptr(w) if want_norm else None, ptr(shift) if want_norm else None,
-         ptr(scale) if want_norm else None, ld, ptr(out), ptr(rstd), M, D, rows_per_batch, eps, stream())
+         _ld(gate_b) if gate_b is not None else 0, ptr(xout), ptr(w), ptr(shift), ptr(scale), ld, ptr(out), ptr(rstd), M, D, rows_per_batch, eps,
+         stream())
     return xout, out, rstd
+
+
+def _norm_bwd_checked(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows_per_batch, y=None, gate=None, dgate=None):
+    """The checks of the five norm + modulate backward forms, once (RMSNorm / LayerNorm, alone or with the gate backward and its recompute
+    form: y, gate, dgate) -> (M, D, and what the kernel reads densely, copied where it must be: dout, x, w, rstd, y)."""
+    x = _arg(x, "rmsnorm_modulate_bwd x", torch.float32, ("M", "D"))
+    M, D = x.shape
+    B = _batches("rmsnorm_modulate_bwd", M, rows_per_batch)
+    dout = _arg(dout, "rmsnorm_modulate_bwd dout", _F32_BF16, (M, D), like=x)
+    w = _arg(w, "rmsnorm_modulate_bwd w", torch.float32, (D,), like=x)
+    _mod_views(scale, None, "rmsnorm_modulate_bwd scale", None, B, D, x)
+    rstd = _arg(rstd, "rmsnorm_modulate_bwd rstd", torch.float32, (M,), like=x)
+    _arg(dx_accum, "rmsnorm_modulate_bwd dx_accum", torch.float32, (M, D), out=True, like=x)
+    _mod_views(dshift, dscale, "rmsnorm_modulate_bwd dshift", "rmsnorm_modulate_bwd dscale", B, D, x, out=True)
+    y = _arg(y, "rmsnorm_modulate_bwd y", dout.dtype, (M, D), like=x)
+    _arg(gate, "rmsnorm_modulate_bwd gate", torch.float32, (B, D), rows=True, like=x, copy=False)
+    _arg(dgate, "rmsnorm_modulate_bwd dgate", torch.float32, (B, D), rows=True, out=True, like=x)
+    return M, D, dout, x, w, rstd, y
 
 
 def _norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate, dw):
@@ -652,8 +727,8 @@ def _norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate
 def rmsnorm_modulate_bwd(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows_per_batch, accumulate=True):
     """dx_accum += dx (in place; accumulate=False: dx_accum = dx, the buffer may be uninitialised); writes dshift/dscale views ([B,D], any
     row stride); returns dw [D] (None for w=None: LayerNorm without affine parameters, use_rmsnorm=False, has no weight gradient)."""
-    M, D = x.shape
-    ws = workspace(L.load().ldmae_rmsnorm_modulate_bwd_workspace_bytes(M, D, rows_per_batch), x.device)
+    M, D, dout, x, w, rstd, _ = _norm_bwd_checked(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows_per_batch)
+    ws = workspace(_ws_bytes("ldmae_rmsnorm_modulate_bwd_workspace_bytes", M, D, rows_per_batch), x.device)
     dw = None if w is None else torch.empty(D, dtype=torch.float32, device=x.device)
     call("ldmae_layernorm_modulate_bwd" if w is None else "ldmae_rmsnorm_modulate_bwd",
          *_norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate, dw), M, D, rows_per_batch, ptr(ws), stream())
@@ -666,12 +741,14 @@ def rmsnorm_modulate_bwd_gate(dout, x, w, scale, rstd, dx_accum, dshift, dscale,
     Returns (dw [D] or None as above, dy [M,D] act dtype, dbias [D]).  recompute: `x` is the residual stream BEFORE the gated residual under
     the norm (the forward ran res_rmsnorm_modulate_fwd and never stored the normalised row); the kernel rebuilds that row as x + gate * y.
     Bitwise the plain form handed the row materialised; bf16, RMSNorm form."""
-    M, D = x.shape
     if recompute and (w is None or dout.dtype != torch.bfloat16):
         raise RuntimeError("rmsnorm_modulate_bwd_gate(recompute=True): the RMSNorm form with bfloat16 activations only")
+    if y is None or gate is None or dgate is None or act_dtype != dout.dtype:
+        raise RuntimeError(f"rmsnorm_modulate_bwd_gate: needs y, gate and dgate, and act_dtype {act_dtype} = dout's {dout.dtype} (y is read, dy written in it)")
+    M, D, dout, x, w, rstd, y = _norm_bwd_checked(dout, x, w, scale, rstd, dx_accum, dshift, dscale, rows_per_batch, y, gate, dgate)
     dy = torch.empty(M, D, dtype=act_dtype, device=x.device)
     dbias = torch.empty(D, dtype=torch.float32, device=x.device)
-    ws = workspace(L.load().ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes(M, D, rows_per_batch), x.device)
+    ws = workspace(_ws_bytes("ldmae_rmsnorm_modulate_bwd_gate_workspace_bytes", M, D, rows_per_batch), x.device)
     dw = None if w is None else torch.empty(D, dtype=torch.float32, device=x.device)
     entry = "ldmae_layernorm_modulate_bwd_gate" if w is None else "ldmae_rmsnorm_modulate_bwd_gate" + ("_recompute" if recompute else "")
     call(entry, *_norm_bwd_args(dout, x, w, scale, rstd, dx_accum, dshift, dscale, accumulate, dw), ptr(y), ptr(gate), gate.stride(0),
@@ -682,6 +759,9 @@ def rmsnorm_modulate_bwd_gate(dout, x, w, scale, rstd, dx_accum, dshift, dscale,
 def qknorm_rope_fwd(qkv, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, copy_v=True):
     """copy_v=False: v gets no head-major copy (returned as None); attention then reads it from the packed qkv (attention_fwd_pv).
     wq = wk = None: RoPE only (the block built with use_qknorm=False: q_norm = k_norm = nn.Identity, lightningdit.py:60-61)."""
+    qkv = _arg(qkv, "qknorm_rope_fwd qkv", _F32_BF16, numel=B * N * 3 * H * hd)
+    wq, wk = _arg(wq, "qknorm_rope_fwd wq", torch.float32, (hd,), like=qkv), _arg(wk, "qknorm_rope_fwd wk", torch.float32, (hd,), like=qkv)
+    cos, sin = _arg(cos, "qknorm_rope_fwd cos", torch.float32, (N, hd), like=qkv), _arg(sin, "qknorm_rope_fwd sin", torch.float32, (N, hd), like=qkv)
     q = torch.empty(B, H, N, hd, dtype=qkv.dtype, device=qkv.device)
     k = torch.empty_like(q)
     v = torch.empty_like(q) if copy_v else None
@@ -693,11 +773,19 @@ def qknorm_rope_bwd(dq, dk, dv, qkv, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, wi
     """Backward of qknorm_rope_fwd: (dqkv [B,N,3,H,hd], dwq, dwk[, dbias [3*H*hd]]).  with_bias: the bias gradient of the qkv Linear
     (column sums of dqkv as stored), formed in the same pass.  dv=None with dqkv given: dv already sits in the v slot of dqkv
     (attention_bwd_pv) and is left there."""
-    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    qkv = _arg(qkv, "qknorm_rope_bwd qkv", _F32_BF16, numel=B * N * 3 * H * hd)
+    dq, dk = _arg(dq, "qknorm_rope_bwd dq", qkv.dtype, (B, H, N, hd), like=qkv), _arg(dk, "qknorm_rope_bwd dk", qkv.dtype, (B, H, N, hd), like=qkv)
+    dv = _arg(dv, "qknorm_rope_bwd dv", qkv.dtype, (B, H, N, hd), like=qkv)
+    wq, wk = _arg(wq, "qknorm_rope_bwd wq", torch.float32, (hd,), like=qkv), _arg(wk, "qknorm_rope_bwd wk", torch.float32, (hd,), like=qkv)
+    cos, sin = _arg(cos, "qknorm_rope_bwd cos", torch.float32, (N, hd), like=qkv), _arg(sin, "qknorm_rope_bwd sin", torch.float32, (N, hd), like=qkv)
+    if dqkv is None:
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+    else:
+        _arg(dqkv, "qknorm_rope_bwd dqkv", qkv.dtype, numel=qkv.numel(), out=True, like=qkv)
     dwq = torch.empty(hd, dtype=torch.float32, device=qkv.device) if wq is not None else None      # wq = wk = None: RoPE adjoint only
     dwk = torch.empty_like(dwq) if wq is not None else None
     db = torch.empty(H, 3, hd, dtype=torch.float32, device=qkv.device) if with_bias else None
-    ws = workspace(L.load().ldmae_qknorm_rope_bwd_workspace_bytes(B, N, H, hd), qkv.device)
+    ws = workspace(_ws_bytes("ldmae_qknorm_rope_bwd_workspace_bytes", B, N, H, hd), qkv.device)
     call("ldmae_qknorm_rope_bwd", dt(qkv.dtype), ptr(dq), ptr(dk), ptr(dv), ptr(qkv), ptr(wq), ptr(wk), ptr(cos), ptr(sin), ptr(dqkv),
          ptr(dwq), ptr(dwk), 0.0, ptr(db), B, N, H, hd, eps, ptr(ws), stream())
     if with_bias:
@@ -708,11 +796,11 @@ def qknorm_rope_bwd(dq, dk, dv, qkv, wq, wk, cos, sin, B, N, H, hd, eps=1e-6, wi
 def rope(t, cos, sin, transposed=False):
     """t [..., N, hd] (f32 or bf16, contiguous) -> t*cos + rotate_half(t)*sin with cos/sin [N, hd] f32 (VisionRotaryEmbeddingFast.forward);
     transposed: the adjoint (backward)."""
+    cos = _arg(cos, "rope cos", torch.float32, ("N", "hd"))
     N, hd = cos.shape
-    if t.shape[-2:] != (N, hd):
-        raise RuntimeError(f"rope: the last two dims of t {tuple(t.shape)} must be (N, head_dim) = {(N, hd)}")
-    t = _c(t)
-    out = torch.empty_like(t)
+    sin = _arg(sin, "rope sin", torch.float32, (N, hd), like=cos)
+    t = _arg(t, "rope t", _F32_BF16, (*t.shape[:-2], N, hd), like=cos)
+    out = torch.empty(t.shape, dtype=t.dtype, device=t.device)
     call("ldmae_rope", dt(t.dtype), ptr(t), ptr(cos), ptr(sin), ptr(out), t.numel() // hd, N, hd, 1 if transposed else 0, stream())
     return out
 
@@ -732,10 +820,22 @@ def _attn_pad(hd: int, dtype=None) -> int:
     raise RuntimeError(f"ldmae_amd attention: head_dim {hd} is above the largest instantiated kernel (128)")
 
 
+def _attn_out(B, H, N, hd, like):
+    """(o [B, N, H*hd] of like's type, lse [B, H, N] f32) as every attention forward writes them."""
+    return torch.empty(B, N, H * hd, dtype=like.dtype, device=like.device), torch.empty(B, H, N, dtype=torch.float32, device=like.device)
+
+
+def _attn_delta(B, H, N, like):
+    """The [2][B, H, NP] f32 scratch of the attention backwards: rows padded to whole 64-row tiles."""
+    return torch.empty(2, B, H, (N + 63) // 64 * 64, dtype=torch.float32, device=like.device)
+
+
 def attention_fwd(q, k, v, scale):
     """softmax(q k^T * scale) v.  q, k, v: [B,H,N,hd]; returns (o [B,N,H*hd], lse [B,H,N] f32).
     bf16 head dims that are not a multiple of 32 (LightningDiT-XL: 72, VMAE: 16) are zero-padded to the next multiple of 32
     INSIDE the kernels (LDS images and register fragments); HBM tensors keep the true head dim."""
+    q = _arg(q, "attention_fwd q", _FLOATS, ("B", "H", "N", "hd"))
+    k, v = _arg(k, "attention_fwd k", q.dtype, q.shape, like=q), _arg(v, "attention_fwd v", q.dtype, q.shape, like=q)
     B, H, N, hd = q.shape
     if hd not in _attn_hds(q.dtype):
         # Head dims outside the instantiated set (16, 32, 64, 72, 128) -- e.g. 24 (mae_for_ldmae_f8d16_prev_large), 80 (mae_vit_huge), 8: zero
@@ -745,22 +845,25 @@ def attention_fwd(q, k, v, scale):
         pad = lambda t: torch.nn.functional.pad(t, (0, P - hd))      # noqa: E731
         o, lse = attention_fwd(pad(q), pad(k), pad(v), scale)
         return o.view(B, N, H, P)[..., :hd].reshape(B, N, H * hd), lse
-    o = torch.empty(B, N, H * hd, dtype=q.dtype, device=q.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=q.device)
+    o, lse = _attn_out(B, H, N, hd, q)
     call("ldmae_attention_fwd", dt(q.dtype), ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), B, H, N, hd, float(scale), stream())
     return o, lse
 
 
 def attention_bwd(q, k, v, o, do, lse, scale):
+    q = _arg(q, "attention_bwd q", _FLOATS, ("B", "H", "N", "hd"))
+    k, v = _arg(k, "attention_bwd k", q.dtype, q.shape, like=q), _arg(v, "attention_bwd v", q.dtype, q.shape, like=q)
     B, H, N, hd = q.shape
+    o, do = _arg(o, "attention_bwd o", q.dtype, numel=q.numel(), like=q), _arg(do, "attention_bwd do", q.dtype, numel=q.numel(), like=q)
+    lse = _arg(lse, "attention_bwd lse", torch.float32, (B, H, N), like=q)
     if hd not in _attn_hds(q.dtype):                          # head dims the kernels are not instantiated for: zero-padded (see attention_fwd)
         P = _attn_pad(hd, q.dtype)
         pad, padt = (lambda t: torch.nn.functional.pad(t, (0, P - hd))), (lambda t: torch.nn.functional.pad(t.reshape(B, N, H, hd), (0, P - hd)).reshape(B, N, H * P))
-        dq, dk, dv = attention_bwd(pad(q), pad(k), pad(v), padt(o), padt(_c(do)), lse, scale)
+        dq, dk, dv = attention_bwd(pad(q), pad(k), pad(v), padt(o), padt(do), lse, scale)
         return dq[..., :hd].contiguous(), dk[..., :hd].contiguous(), dv[..., :hd].contiguous()
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-    delta = torch.empty(2, B, H, (N + 63) // 64 * 64, dtype=torch.float32, device=q.device)      # rows padded to whole 64-row tiles
-    call("ldmae_attention_bwd", dt(q.dtype), ptr(q), ptr(k), ptr(v), ptr(o), ptr(_c(do)), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta),
+    dq, dk, dv = (torch.empty(q.shape, dtype=q.dtype, device=q.device) for _ in range(3))
+    delta = _attn_delta(B, H, N, q)
+    call("ldmae_attention_bwd", dt(q.dtype), ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(dq), ptr(dk), ptr(dv), ptr(delta),
          B, H, N, hd, float(scale), stream())
     return dq, dk, dv
 
@@ -768,6 +871,8 @@ def attention_bwd(q, k, v, o, do, lse, scale):
 def qk_score_bound(wq, wk, hd, scale):
     """One float on the device: hd * max|wq| * max|wk| * scale * log2(e) * 1.02, an upper bound of every attention score (in the kernels'
     log2 units) of heads that went through QK-RMSNorm with these weights and RoPE -- for attention_fwd_pv(bound=...)."""
+    wq = _arg(wq, "qk_score_bound wq", torch.float32, (hd,))
+    wk = _arg(wk, "qk_score_bound wk", torch.float32, (hd,), like=wq)
     out = torch.empty(1, dtype=torch.float32, device=wq.device)
     call("ldmae_qk_score_bound", ptr(wq), ptr(wk), hd, float(scale), ptr(out), stream())
     return out
@@ -776,9 +881,12 @@ def qk_score_bound(wq, wk, hd, scale):
 def attention_fwd_pv(q, k, qkv, scale, bound=None):
     """q, k head-major [B,H,N,hd]; v read from the packed qkv [B*N, 3*H*hd] (bf16).  bound: a proven upper bound of the scores
     (qk_score_bound): the softmax then runs with a static shift instead of a running maximum (same result, fewer vector instructions)."""
+    q = _arg(q, "attention_fwd_pv q", torch.bfloat16, ("B", "H", "N", "hd"))
+    k = _arg(k, "attention_fwd_pv k", torch.bfloat16, q.shape, like=q)
+    qkv = _arg(qkv, "attention_fwd_pv qkv", torch.bfloat16, numel=3 * q.numel(), like=q)
+    bound = _arg(bound, "attention_fwd_pv bound", torch.float32, numel=1, like=q)
     B, H, N, hd = q.shape
-    o = torch.empty(B, N, H * hd, dtype=q.dtype, device=q.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=q.device)
+    o, lse = _attn_out(B, H, N, hd, q)
     if bound is not None:
         call("ldmae_attention_fwd_pv_bounded", dt(q.dtype), ptr(q), ptr(k), ptr(qkv), ptr(o), ptr(lse), ptr(bound), B, H, N, hd, float(scale), stream())
     else:
@@ -788,11 +896,16 @@ def attention_fwd_pv(q, k, qkv, scale, bound=None):
 
 def attention_bwd_pv(q, k, qkv, o, do, lse, scale):
     """-> (dq, dk head-major, dqkv with ONLY its v slot written: dv in the packed layout)."""
+    q = _arg(q, "attention_bwd_pv q", torch.bfloat16, ("B", "H", "N", "hd"))
+    k = _arg(k, "attention_bwd_pv k", torch.bfloat16, q.shape, like=q)
+    qkv = _arg(qkv, "attention_bwd_pv qkv", torch.bfloat16, numel=3 * q.numel(), like=q)
+    o, do = _arg(o, "attention_bwd_pv o", torch.bfloat16, numel=q.numel(), like=q), _arg(do, "attention_bwd_pv do", torch.bfloat16, numel=q.numel(), like=q)
     B, H, N, hd = q.shape
-    dq, dk = torch.empty_like(q), torch.empty_like(q)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(2, B, H, (N + 63) // 64 * 64, dtype=torch.float32, device=q.device)
-    call("ldmae_attention_bwd_pv", dt(q.dtype), ptr(q), ptr(k), ptr(qkv), ptr(o), ptr(_c(do)), ptr(lse), ptr(dq), ptr(dk), ptr(dqkv), ptr(delta),
+    lse = _arg(lse, "attention_bwd_pv lse", torch.float32, (B, H, N), like=q)
+    dq, dk = torch.empty(q.shape, dtype=q.dtype, device=q.device), torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    dqkv = torch.empty(qkv.shape, dtype=q.dtype, device=q.device)
+    delta = _attn_delta(B, H, N, q)
+    call("ldmae_attention_bwd_pv", dt(q.dtype), ptr(q), ptr(k), ptr(qkv), ptr(o), ptr(do), ptr(lse), ptr(dq), ptr(dk), ptr(dqkv), ptr(delta),
          B, H, N, hd, float(scale), stream())
     return dq, dk, dqkv
 
@@ -800,16 +913,25 @@ def attention_bwd_pv(q, k, qkv, o, do, lse, scale):
 def attention_bwd_pv_qknorm(q, k, qkv, o, do, lse, scale, wq, wk, cos, sin, eps=1e-6):
     """attention_bwd_pv + qknorm_rope_bwd(with_bias=True) in one (bf16, head_dim 64 / 128): -> (dqkv [B,N,3,H,hd] complete, dwq, dwk,
     dbias [3*H*hd])."""
+    q = _arg(q, "attention_bwd_pv_qknorm q", torch.bfloat16, ("B", "H", "N", "hd"))
+    k = _arg(k, "attention_bwd_pv_qknorm k", torch.bfloat16, q.shape, like=q)
+    qkv = _arg(qkv, "attention_bwd_pv_qknorm qkv", torch.bfloat16, numel=3 * q.numel(), like=q)
+    o = _arg(o, "attention_bwd_pv_qknorm o", torch.bfloat16, numel=q.numel(), like=q)
+    do = _arg(do, "attention_bwd_pv_qknorm do", torch.bfloat16, numel=q.numel(), like=q)
     B, H, N, hd = q.shape
-    dqkv = torch.empty_like(qkv)
+    lse = _arg(lse, "attention_bwd_pv_qknorm lse", torch.float32, (B, H, N), like=q)
+    wq, wk = _arg(wq, "attention_bwd_pv_qknorm wq", torch.float32, (hd,), like=q), _arg(wk, "attention_bwd_pv_qknorm wk", torch.float32, (hd,), like=q)
+    cos = _arg(cos, "attention_bwd_pv_qknorm cos", torch.float32, (N, hd), like=q)
+    sin = _arg(sin, "attention_bwd_pv_qknorm sin", torch.float32, (N, hd), like=q)
+    dqkv = torch.empty(qkv.shape, dtype=q.dtype, device=q.device)
     if wq is not None:
         dw2 = torch.empty(2 * hd, dtype=torch.float32, device=q.device)      # dwq | dwk adjacent: the library reduces straight into them
         dwq, dwk = dw2[:hd], dw2[hd:]
     else:
         dwq = dwk = None                                                      # RoPE adjoint only (use_qknorm=False)
     db = torch.empty(3 * H * hd, dtype=torch.float32, device=q.device)
-    ws = workspace(L.load().ldmae_attention_bwd_pv_qknorm_workspace_bytes(B, H, N, hd), q.device)
-    call("ldmae_attention_bwd_pv_qknorm", dt(q.dtype), ptr(q), ptr(k), ptr(qkv), ptr(o), ptr(_c(do)), ptr(lse), ptr(wq), ptr(wk), ptr(cos),
+    ws = workspace(_ws_bytes("ldmae_attention_bwd_pv_qknorm_workspace_bytes", B, H, N, hd), q.device)
+    call("ldmae_attention_bwd_pv_qknorm", dt(q.dtype), ptr(q), ptr(k), ptr(qkv), ptr(o), ptr(do), ptr(lse), ptr(wq), ptr(wk), ptr(cos),
          ptr(sin), float(eps), ptr(dqkv), ptr(dwq), ptr(dwk), ptr(db), ptr(ws), B, H, N, hd, float(scale), stream())
     return dqkv, dwq, dwk, db
 
@@ -823,10 +945,10 @@ def attention_fwd_qkv(qkv, B, N, H, hd, scale):
     Long sequences of small heads (the 1024-token VMAE decoder: the kernel is bound by vector issue) first take one pass over the k slots
     for max |k|^2 per (image, head): with each query's own norm it bounds the scores, and the softmax runs with that static shift instead of
     a running maximum (same result; ldmae_k_norm_max + ldmae_attention_fwd_qkv_bounded)."""
+    qkv = _arg(qkv, "attention_fwd_qkv qkv", _FLOATS, numel=B * N * 3 * H * hd)
     if hd not in _attn_hds(qkv.dtype):                        # (see attention_fwd: head-major zero-padded copies)
         return attention_fwd(*heads_split(qkv, B, N, H, hd), scale)
-    o = torch.empty(B, N, H * hd, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
+    o, lse = _attn_out(B, H, N, hd, qkv)
     if qkv.dtype == torch.bfloat16 and hd <= 32 and N >= 512 and B * H * N * N >= BOUNDED_ATTENTION_MIN_SCORES:
         kmax = torch.empty(B * H, 2, dtype=torch.float32, device=qkv.device)
         call("ldmae_k_norm_max", ptr(qkv), ptr(kmax), B, N, H, hd, stream())
@@ -838,16 +960,21 @@ def attention_fwd_qkv(qkv, B, N, H, hd, scale):
 
 def attention_bwd_qkv(qkv, o, do, lse, B, N, H, hd, scale):
     """-> dqkv [B*N, 3*H*hd] (dq / dk / dv written in the packed layout)."""
+    qkv = _arg(qkv, "attention_bwd_qkv qkv", _FLOATS, numel=B * N * 3 * H * hd)
+    o = _arg(o, "attention_bwd_qkv o", qkv.dtype, numel=B * N * H * hd, like=qkv)
+    do = _arg(do, "attention_bwd_qkv do", qkv.dtype, numel=B * N * H * hd, like=qkv)
+    lse = _arg(lse, "attention_bwd_qkv lse", torch.float32, (B, H, N), like=qkv)
     if hd not in _attn_hds(qkv.dtype):                        # (see attention_fwd: head-major zero-padded copies)
         q, k, v = heads_split(qkv, B, N, H, hd)
         return heads_merge(*attention_bwd(q, k, v, o, do, lse, scale), B, N, H, hd)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(2, B, H, (N + 63) // 64 * 64, dtype=torch.float32, device=qkv.device)
-    call("ldmae_attention_bwd_qkv", dt(qkv.dtype), ptr(qkv), ptr(o), ptr(_c(do)), ptr(lse), ptr(dqkv), ptr(delta), B, H, N, hd, float(scale), stream())
+    dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+    delta = _attn_delta(B, H, N, qkv)
+    call("ldmae_attention_bwd_qkv", dt(qkv.dtype), ptr(qkv), ptr(o), ptr(do), ptr(lse), ptr(dqkv), ptr(delta), B, H, N, hd, float(scale), stream())
     return dqkv
 
 
 def swiglu_fwd(h12):
+    h12 = _arg(h12, "swiglu_fwd h12", _F32_BF16, ("M", "2*Hs"))
     M, H2 = h12.shape
     hid = torch.empty(M, H2 // 2, dtype=h12.dtype, device=h12.device)
     call("ldmae_swiglu_fwd", dt(h12.dtype), ptr(h12), ptr(hid), M, H2 // 2, stream())
@@ -855,8 +982,10 @@ def swiglu_fwd(h12):
 
 
 def swiglu_bwd(dhid, h12):
+    h12 = _arg(h12, "swiglu_bwd h12", _F32_BF16, ("M", "2*Hs"))
     M, H2 = h12.shape
-    dh12 = torch.empty_like(h12)
+    dhid = _arg(dhid, "swiglu_bwd dhid", h12.dtype, (M, H2 // 2), like=h12)
+    dh12 = torch.empty(M, H2, dtype=h12.dtype, device=h12.device)
     call("ldmae_swiglu_bwd", dt(h12.dtype), ptr(dhid), ptr(h12), ptr(dh12), M, H2 // 2, stream())
     return dh12
 
@@ -864,44 +993,61 @@ def swiglu_bwd(dhid, h12):
 def gate_bwd(dxout, y, gate, dgate, rows_per_batch, act_dtype, with_bias=False):
     """dy = dxout * gate[b] (act dtype);  dgate view [B,D] <- sum_n dxout*y (skipped when dgate is None).
     with_bias: also return the column sums of dy (the bias gradient of the Linear that produced the branch)."""
+    dxout = _arg(dxout, "gate_bwd dxout", torch.float32, ("M", "D"))
     M, D = dxout.shape
+    B = _batches("gate_bwd", M, rows_per_batch)
+    y = _arg(y, "gate_bwd y", act_dtype, (M, D), like=dxout)
+    _arg(gate, "gate_bwd gate", torch.float32, (B, D), rows=True, like=dxout, copy=False)
+    _arg(dgate, "gate_bwd dgate", torch.float32, (B, D), rows=True, out=True, like=dxout)
     dy = torch.empty(M, D, dtype=act_dtype, device=dxout.device)
     dbias = torch.empty(D, dtype=torch.float32, device=dxout.device) if with_bias else None
     need_ws = dgate is not None or with_bias
-    ws = workspace(L.load().ldmae_gate_bwd_workspace_bytes(M, D, rows_per_batch), dxout.device) if need_ws else None
+    ws = workspace(_ws_bytes("ldmae_gate_bwd_workspace_bytes", M, D, rows_per_batch), dxout.device) if need_ws else None
     call("ldmae_gate_bwd", dt(act_dtype), ptr(dxout), ptr(y), ptr(gate), gate.stride(0) if gate is not None else 0, ptr(dy), ptr(dgate),
          dgate.stride(0) if dgate is not None else 0, ptr(dbias), M, D, rows_per_batch, ptr(ws), stream())
     return (dy, dbias) if with_bias else dy
 
 
 def timestep_embedding(t, dim=256, max_period=10000.0):
+    """t [B] of any real type (converted to f32, as the reference's t.float()) -> the [B, dim] sinusoidal embedding."""
+    t = _arg(t.float(), "timestep_embedding t", torch.float32, ("B",))
     out = torch.empty(t.shape[0], dim, dtype=torch.float32, device=t.device)
-    call("ldmae_timestep_embedding", ptr(_c(t.float())), ptr(out), t.shape[0], dim, float(max_period), stream())
+    call("ldmae_timestep_embedding", ptr(t), ptr(out), t.shape[0], dim, float(max_period), stream())
     return out
 
 
 def silu_fwd(x, out_dtype=torch.float32):
+    x = _arg(x, "silu_fwd x", torch.float32)
     out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     call("ldmae_silu_fwd", dt(out_dtype), ptr(x), ptr(out), x.numel(), stream())
     return out
 
 
 def silu_bwd(dy, x):
-    dx = torch.empty_like(x)
-    call("ldmae_silu_bwd", ptr(_c(dy)), ptr(x), ptr(dx), x.numel(), stream())
+    x = _arg(x, "silu_bwd x", torch.float32)
+    dy = _arg(dy, "silu_bwd dy", torch.float32, x.shape, like=x)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    call("ldmae_silu_bwd", ptr(dy), ptr(x), ptr(dx), x.numel(), stream())
     return dx
 
 
 def label_embed_fwd(table, y, drop, num_classes):
+    table = _arg(table, "label_embed_fwd table", torch.float32, ("rows", "D"))
+    y = _arg(y, "label_embed_fwd y", torch.int64, ("B",), like=table)
     B, D = y.shape[0], table.shape[1]
+    drop = _arg(drop, "label_embed_fwd drop", _FLAGS, (B,), like=table)
     out = torch.empty(B, D, dtype=torch.float32, device=table.device)
     call("ldmae_label_embed_fwd", ptr(table), ptr(y), ptr(drop), ptr(out), B, D, num_classes, stream())
     return out
 
 
 def label_embed_bwd(dout, y, drop, num_classes, rows):
-    dtable = torch.zeros(rows, dout.shape[1], dtype=torch.float32, device=dout.device)
-    call("ldmae_label_embed_bwd", ptr(_c(dout)), ptr(y), ptr(drop), ptr(dtable), dout.shape[0], dout.shape[1], num_classes, rows, stream())
+    dout = _arg(dout, "label_embed_bwd dout", torch.float32, ("B", "D"))
+    B, D = dout.shape
+    y = _arg(y, "label_embed_bwd y", torch.int64, (B,), like=dout)
+    drop = _arg(drop, "label_embed_bwd drop", _FLAGS, (B,), like=dout)
+    dtable = torch.zeros(rows, D, dtype=torch.float32, device=dout.device)
+    call("ldmae_label_embed_bwd", ptr(dout), ptr(y), ptr(drop), ptr(dtable), B, D, num_classes, rows, stream())
     return dtable
 
 
@@ -919,55 +1065,47 @@ def invalidate_weight_cache() -> None:
     WEIGHT_EPOCH += 1
 
 
+def _cached(key, anchor, stamp, make):
+    """The one lookup of the forward-only weight caches: the value under `key` while `stamp` is unchanged and `anchor` (the tensor whose id() is
+    in the key) is still that object -- the weak reference guards against a recycled id(); otherwise make() is stored and returned."""
+    hit = _WCACHE.get(key)
+    if hit is not None and hit[0]() is anchor and hit[1] == stamp:
+        return hit[2]
+    if len(_WCACHE) > 4096:
+        _WCACHE.clear()
+    c = make()
+    _WCACHE[key] = (weakref.ref(anchor), stamp, c)
+    return c
+
+
 def cached_weight_copy(w, dtype):
     """`dtype` copy of the f32 master weight `w` for FORWARD-ONLY use (sampling / encoding under no_grad runs the same weights hundreds of
     times: 112 cast launches per XL/1 forward).  Valid while the storage pointer, torch's version counter of `w` and WEIGHT_EPOCH are
     unchanged; training never comes here (its weights change every step)."""
-    key = (id(w), dtype)
-    stamp = (w.data_ptr(), w._version, WEIGHT_EPOCH)
-    hit = _WCACHE.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == stamp:      # the weak reference guards against a recycled id()
-        return hit[2]
-    if len(_WCACHE) > 4096:
-        _WCACHE.clear()
-    c = cast_weight(w, dtype, transposed=False, straight=True)[0]
-    _WCACHE[key] = (weakref.ref(w), stamp, c)
-    return c
+    return _cached((id(w), dtype), w, (w.data_ptr(), w._version, WEIGHT_EPOCH), lambda: cast_weight(w, dtype, transposed=False, straight=True)[0])
 
 
 def cached_weight_mx8(w):
     """(q, scales) of the f32 master weight `w` [N, K], MX-quantised along K, for FORWARD-ONLY use: cached under the rule of
-    cached_weight_copy (storage pointer, torch's version counter, WEIGHT_EPOCH; weak reference against a recycled id())."""
-    key = (id(w), "mx8")
-    stamp = (w.data_ptr(), w._version, WEIGHT_EPOCH)
-    hit = _WCACHE.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == stamp:
-        return hit[2]
-    if len(_WCACHE) > 4096:
-        _WCACHE.clear()
-    c = mx8_quantize(w)
-    _WCACHE[key] = (weakref.ref(w), stamp, c)
-    return c
+    cached_weight_copy."""
+    return _cached((id(w), "mx8"), w, (w.data_ptr(), w._version, WEIGHT_EPOCH), lambda: mx8_quantize(w))
 
 
 def cached_stack_copy(tensors, dtype):
     """cast_stack for FORWARD-ONLY use (sampling re-runs the same weights hundreds of times): valid while every source's storage pointer and
-    version counter and WEIGHT_EPOCH are unchanged.  Keyed by the first tensor (weak reference, like cached_weight_copy)."""
+    version counter and WEIGHT_EPOCH are unchanged.  Keyed by the first tensor, like cached_weight_copy."""
     w = tensors[0]
-    key = (id(w), dtype, "stack", len(tensors))
-    stamp = (tuple((t.data_ptr(), t._version) for t in tensors), WEIGHT_EPOCH)
-    hit = _WCACHE.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == stamp:
-        return hit[2]
-    if len(_WCACHE) > 4096:
-        _WCACHE.clear()
-    c = cast_stack(tensors, dtype)
-    _WCACHE[key] = (weakref.ref(w), stamp, c)
-    return c
+    return _cached((id(w), dtype, "stack", len(tensors)), w, (tuple((t.data_ptr(), t._version) for t in tensors), WEIGHT_EPOCH),
+                   lambda: cast_stack(tensors, dtype))
 
 
 def adamw_ema(p, g, m, v, ema, step, lr, beta1, beta2, eps, weight_decay, ema_decay, grad_scale=1.0):
     global WEIGHT_EPOCH
+    _arg(p, "adamw_ema p", torch.float32, out=True)
+    _arg(g, "adamw_ema g", torch.float32, numel=p.numel(), like=p, out=True)
+    _arg(m, "adamw_ema m", torch.float32, numel=p.numel(), like=p, out=True)
+    _arg(v, "adamw_ema v", torch.float32, numel=p.numel(), like=p, out=True)
+    _arg(ema, "adamw_ema ema", torch.float32, numel=p.numel(), like=p, out=True)
     WEIGHT_EPOCH += 1
     call("ldmae_adamw_ema", ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), int(step), float(lr), float(beta1), float(beta2),
          float(eps), float(weight_decay), float(ema_decay), float(grad_scale), stream())
@@ -975,6 +1113,8 @@ def adamw_ema(p, g, m, v, ema, step, lr, beta1, beta2, eps, weight_decay, ema_de
 
 def ema_only(ema, p, ema_decay):
     global WEIGHT_EPOCH
+    _arg(p, "ema_only p", torch.float32, copy=False)
+    _arg(ema, "ema_only ema", torch.float32, numel=p.numel(), like=p, out=True)
     WEIGHT_EPOCH += 1
     call("ldmae_ema_only", ptr(ema), ptr(p), p.numel(), float(ema_decay), stream())
 
@@ -1009,7 +1149,8 @@ def ema_tracks_only(p, tracks, coefs):
     """The track update alone, for parameters the optimizer does not touch (the frozen tail)."""
     op = "ema_tracks_only"
     _arg(p, op + " p", dtype=torch.float32, copy=False)
-    call("ldmae_ema_tracks_only", ptr(p), p.numel(), *_track_args(op, tracks, coefs, p), stream())
+    tail = _track_args(op, tracks, coefs, p)
+    call("ldmae_ema_tracks_only", ptr(p), p.numel(), *tail, stream())
 
 
 def snapshot_accumulate(acc, x, coef):
@@ -1030,23 +1171,31 @@ def snapshot_finish(acc, out=None):
 
 # ----------------------------------------------------------------------------- VMAE
 def random_masking(noise, keep):
+    noise = _arg(noise, "random_masking noise", torch.float32, ("N", "L"))
     N, Lq = noise.shape
     ids_restore = torch.empty(N, Lq, dtype=torch.int64, device=noise.device)
     mask = torch.empty(N, Lq, dtype=torch.float32, device=noise.device)
     ids_keep = torch.empty(N, keep, dtype=torch.int64, device=noise.device)
-    call("ldmae_random_masking", ptr(_c(noise)), ptr(ids_restore), ptr(mask), ptr(ids_keep), N, Lq, keep, stream())
+    call("ldmae_random_masking", ptr(noise), ptr(ids_restore), ptr(mask), ptr(ids_keep), N, Lq, keep, stream())
     return ids_keep, mask, ids_restore
 
 
 def patch_embed_kept(img, ids_keep, pos, w2d, bias, patch, dtype):
     """Patch embedding of the kept tokens only: img [N,C,S,S] f32, ids_keep [N,keep] i64, pos [L,D] f32, w2d [D, C*p*p] f32 master weight
     -> [N, keep, D] f32 = conv(img)[kept] + bias + pos[kept].  Same bits as embedding all patches (gemm_nt_pos) and gathering."""
-    N, C, S, _ = img.shape
+    img = _arg(img.float(), "patch_embed_kept img", torch.float32, ("N", "C", "S", "S"))
+    N, C, S, S2 = img.shape
+    if S2 != S or patch <= 0 or S % patch:
+        raise RuntimeError(f"patch_embed_kept img: shape {tuple(img.shape)}, expected square images of whole {patch}-pixel patches")
+    ids_keep = _arg(ids_keep, "patch_embed_kept ids_keep", torch.int64, (N, "keep"), like=img)
+    w2d = _arg(w2d, "patch_embed_kept w2d", torch.float32, ("D", C * patch * patch), like=img)
     keep, D = ids_keep.shape[1], w2d.shape[0]
+    pos = _arg(pos, "patch_embed_kept pos", torch.float32, ("L", D), like=img, at_least=(S // patch) ** 2 * D)
+    bias = _arg(bias, "patch_embed_kept bias", torch.float32, (D,), like=img)
     tok = torch.empty(N * keep, C * patch * patch, dtype=dtype, device=img.device)
     posg = torch.empty(N * keep, D, dtype=torch.float32, device=img.device)
-    call("ldmae_patch_gather", dt(dtype), ptr(_c(img.float())), ptr(ids_keep), ptr(pos), ptr(tok), ptr(posg), N, keep, C, S, patch, D, stream())
-    wb = cast(_c(w2d), dtype)          # 192 x 192: one tiny launch (w2d is a fresh view per call, so the id-keyed weight cache does not apply)
+    call("ldmae_patch_gather", dt(dtype), ptr(img), ptr(ids_keep), ptr(pos), ptr(tok), ptr(posg), N, keep, C, S, patch, D, stream())
+    wb = cast(w2d, dtype)         # 192 x 192: one tiny launch (w2d is a fresh view per call, so the id-keyed weight cache does not apply)
     out, _ = gemm_nt_gate_res(tok, wb, bias, posg, None, keep, save_y=False, xout=posg, y_dtype=torch.float32)   # unrounded, as gemm_nt_pos
     return out.view(N, keep, D)
 
@@ -1054,14 +1203,16 @@ def patch_embed_kept(img, ids_keep, pos, w2d, bias, patch, dtype):
 def latent_prologue(moments, noise=None, lat_mean=None, lat_std=None, multiplier=1.0, sample=True):
     """Device-side counterpart of ImgLatentDataset.__getitem__ after the shard read: moments [B, 2C, H, W] f32 (sample) or latents
     [B, C, H, W] -> normalised model input [B, C, H, W] f32.  noise [B, C, H, W] (drawn by the caller); lat_mean / lat_std [C]-sized."""
-    B, C2, H, W = moments.shape
+    mom = _arg(moments.float(), "latent_prologue moments", torch.float32, ("B", "2C" if sample else "C", "H", "W"))
+    B, C2, H, W = mom.shape
+    if sample and C2 % 2:
+        raise RuntimeError(f"latent_prologue moments: shape {tuple(mom.shape)}, expected [B, 2C, H, W] (mean | logvar)")
     C = C2 // 2 if sample else C2
-    out = torch.empty(B, C, H, W, dtype=torch.float32, device=moments.device)
-    mom = _c(moments.float())
-    nz = _c(noise.float()) if noise is not None else None
-    mu, sd = (_c(t.float().reshape(-1)) if t is not None else None for t in (lat_mean, lat_std))
-    call("ldmae_latent_prologue", ptr(mom), ptr(nz) if nz is not None else None, ptr(mu) if mu is not None else None,
-         ptr(sd) if sd is not None else None, float(multiplier), ptr(out), B, C, H * W, 1 if sample else 0, stream())
+    nz = _arg(noise.float() if noise is not None and sample else None, "latent_prologue noise", torch.float32, (B, C, H, W), like=mom)
+    mu = _arg(lat_mean.float().reshape(-1) if lat_mean is not None else None, "latent_prologue lat_mean", torch.float32, (C,), like=mom)
+    sd = _arg(lat_std.float().reshape(-1) if lat_std is not None else None, "latent_prologue lat_std", torch.float32, (C,), like=mom)
+    out = torch.empty(B, C, H, W, dtype=torch.float32, device=mom.device)
+    call("ldmae_latent_prologue", ptr(mom), ptr(nz), ptr(mu), ptr(sd), float(multiplier), ptr(out), B, C, H * W, 1 if sample else 0, stream())
     return out
 
 
@@ -1213,7 +1364,9 @@ def crop_resize_flip(blob, offsets, geom, S, mean=0.5, std=0.5, out_dtype=torch.
 
 
 def gather_rows(x, ids):
+    x = _arg(x, "gather_rows x", torch.float32, ("N", "L", "D"))
     N, Lq, D = x.shape
+    ids = _arg(ids, "gather_rows ids", torch.int64, (N, "keep"), like=x)
     keep = ids.shape[1]
     out = torch.empty(N, keep, D, dtype=torch.float32, device=x.device)
     call("ldmae_gather_rows", ptr(x), ptr(ids), ptr(out), N, Lq, keep, D, stream())
@@ -1221,42 +1374,56 @@ def gather_rows(x, ids):
 
 
 def scatter_rows(dout, ids, Lq):
+    dout = _arg(dout, "scatter_rows dout", torch.float32, ("N", "keep", "D"))
     N, keep, D = dout.shape
+    ids = _arg(ids, "scatter_rows ids", torch.int64, (N, keep), like=dout)
     dx = torch.zeros(N, Lq, D, dtype=torch.float32, device=dout.device)
-    call("ldmae_scatter_rows", ptr(_c(dout)), ptr(ids), ptr(dx), N, Lq, keep, D, stream())
+    call("ldmae_scatter_rows", ptr(dout), ptr(ids), ptr(dx), N, Lq, keep, D, stream())
     return dx
 
 
 def restore_tokens(x, mask_token, pos, ids_restore):
     """Decoder input of the pre-training step (models_mae.py:536-541) in one pass: x [B, keep, D] f32, mask_token [D], pos [L, D], ids_restore
     [B, L] i64 -> [B, L, D] = (kept row or mask token) + pos."""
+    x = _arg(x, "restore_tokens x", torch.float32, ("B", "keep", "D"))
     B, keep, D = x.shape
+    ids_restore = _arg(ids_restore, "restore_tokens ids_restore", torch.int64, (B, "L"), like=x)
     Lq = ids_restore.shape[1]
+    mask_token = _arg(mask_token, "restore_tokens mask_token", torch.float32, (D,), like=x)
+    pos = _arg(pos, "restore_tokens pos", torch.float32, ("L", D), like=x, at_least=Lq * D)
     out = torch.empty(B, Lq, D, dtype=torch.float32, device=x.device)
-    call("ldmae_restore_tokens", ptr(_c(x)), ptr(_c(mask_token)), ptr(_c(pos)), ptr(_c(ids_restore)), ptr(out), B, Lq, keep, D, stream())
+    call("ldmae_restore_tokens", ptr(x), ptr(mask_token), ptr(pos), ptr(ids_restore), ptr(out), B, Lq, keep, D, stream())
     return out
 
 
 def restore_tokens_bwd(dout, ids_restore, keep, need_mask_grad=True):
     """-> (dx [B, keep, D], dmask_token [D] or None)."""
+    dout = _arg(dout, "restore_tokens_bwd dout", torch.float32, ("B", "L", "D"))
     B, Lq, D = dout.shape
+    ids_restore = _arg(ids_restore, "restore_tokens_bwd ids_restore", torch.int64, (B, Lq), like=dout)
     dx = torch.empty(B, keep, D, dtype=torch.float32, device=dout.device)
     dm = torch.empty(D, dtype=torch.float32, device=dout.device) if need_mask_grad else None
-    ws = workspace(L.load().ldmae_restore_tokens_bwd_workspace_bytes(B, Lq, D), dout.device) if need_mask_grad else None
-    call("ldmae_restore_tokens_bwd", ptr(_c(dout)), ptr(_c(ids_restore)), ptr(dx), ptr(dm), B, Lq, keep, D, ptr(ws), stream())
+    ws = workspace(_ws_bytes("ldmae_restore_tokens_bwd_workspace_bytes", B, Lq, D), dout.device) if need_mask_grad else None
+    call("ldmae_restore_tokens_bwd", ptr(dout), ptr(ids_restore), ptr(dx), ptr(dm), B, Lq, keep, D, ptr(ws), stream())
     return dx, dm
+
+
+def _vmae_encoder_args(x, blob, nblocks, dim):
+    """What the two forms of the fused VMAE encoder share: x [B, tokens, dim] (any float type: converted to f32) and the weight blob of the
+    size the kernels expect, read in place -> (x, out, B, tokens)."""
+    x = _arg(x.float(), "vmae_encoder_fwd x", torch.float32, ("B", "tokens", dim))
+    _arg(blob, "vmae_encoder_fwd blob", like=x, copy=False)
+    need = L.load().ldmae_vmae_encoder_blob_bytes(nblocks)
+    if blob.numel() * blob.element_size() != need:
+        raise RuntimeError(f"vmae_encoder_fwd: weight blob has {blob.numel() * blob.element_size()} bytes, the kernels expect {need}")
+    return x, torch.empty(x.shape, dtype=torch.float32, device=x.device), x.shape[0], x.shape[1]
 
 
 def vmae_encoder_fwd(x, blob, nblocks, dim, heads, hidden, eps=1e-6):
     """The whole VMAE encoder stack (blocks + closing LayerNorm) in one launch: x [B, tokens, dim] f32 -> same shape (inference, bf16 MFMA,
     f32 residual stream in registers).  `blob`: weights packed by tokenizer/fused_encoder.py."""
-    B, T, D = x.shape
-    x = _c(x.float())
-    need = L.load().ldmae_vmae_encoder_blob_bytes(nblocks)
-    if blob.numel() * blob.element_size() != need:
-        raise RuntimeError(f"vmae_encoder_fwd: weight blob has {blob.numel() * blob.element_size()} bytes, the kernel expects {need}")
-    out = torch.empty_like(x)
-    call("ldmae_vmae_encoder_fwd", ptr(x), ptr(out), ptr(blob), B, T, D, heads, hidden, nblocks, float(eps), stream())
+    x, out, B, T = _vmae_encoder_args(x, blob, nblocks, dim)
+    call("ldmae_vmae_encoder_fwd", ptr(x), ptr(out), ptr(blob), B, T, dim, heads, hidden, nblocks, float(eps), stream())
     return out
 
 
@@ -1264,13 +1431,9 @@ def vmae_encoder_fwd_tiled(x, blob, nblocks, dim, heads, hidden, eps=1e-6, f16=F
     """The same stack on sequences of several whole 256-token tiles per image (the docking encoder on all 1024 patches): three launches per
     block -- q|k|v of a tile, flash attention on the packed qkv, proj + MLP of a tile -- from the same weight blob.  f16: the TF32-class form
     (the blob packed in fp16)."""
-    B, T, D = x.shape
-    x = _c(x.float())
-    need = L.load().ldmae_vmae_encoder_blob_bytes(nblocks)
-    if blob.numel() * blob.element_size() != need:
-        raise RuntimeError(f"vmae_encoder_fwd_tiled: weight blob has {blob.numel() * blob.element_size()} bytes, the kernels expect {need}")
-    out = torch.empty_like(x)
-    ws = workspace(L.load().ldmae_vmae_encoder_fwd_tiled_workspace_bytes(B, T), x.device)
+    x, out, B, T = _vmae_encoder_args(x, blob, nblocks, dim)
+    D = dim
+    ws = workspace(_ws_bytes("ldmae_vmae_encoder_fwd_tiled_workspace_bytes", B, T), x.device)
     call("ldmae_vmae_encoder_fwd_tiled_f16" if f16 else "ldmae_vmae_encoder_fwd_tiled", ptr(x), ptr(out), ptr(blob), ptr(ws), B, T, D, heads, hidden,
          nblocks, float(eps), stream())
     return out
@@ -1278,6 +1441,7 @@ def vmae_encoder_fwd_tiled(x, blob, nblocks, dim, heads, hidden, eps=1e-6, f16=F
 
 def heads_split(qkv, B, N, H, hd):
     """[B,N,3,H,hd] -> q,k,v [B,H,N,hd] (no norm / rope)."""
+    qkv = _arg(qkv, "heads_split qkv", _F32_BF16, numel=B * N * 3 * H * hd)
     if hd % 8 != 0:
         # head dims off the kernels' 8-element grid (12: the pre-training tree's mae_for_ldmae_f8d16_small, VMAE/models_mae.py:1036-1041): a pure
         # re-layout, done by torch's copy; the attention wrappers then zero-pad the heads to the next instantiated head dim
@@ -1291,6 +1455,8 @@ def heads_split(qkv, B, N, H, hd):
 
 def heads_merge(dq, dk, dv, B, N, H, hd):
     """inverse of heads_split for the gradients: -> [B*N, 3*H*hd]."""
+    dq = _arg(dq, "heads_merge dq", _F32_BF16, (B, H, N, hd))
+    dk, dv = _arg(dk, "heads_merge dk", dq.dtype, (B, H, N, hd), like=dq), _arg(dv, "heads_merge dv", dq.dtype, (B, H, N, hd), like=dq)
     if hd % 8 != 0:                                   # (see heads_split)
         return torch.stack((dq, dk, dv), 0).permute(1, 3, 0, 2, 4).reshape(B * N, 3 * H * hd)
     dqkv = torch.empty(B * N, 3 * H * hd, dtype=dq.dtype, device=dq.device)
@@ -1300,40 +1466,58 @@ def heads_merge(dq, dk, dv, B, N, H, hd):
 
 
 def conv3x3(x, w, b):
+    x = _arg(x, "conv3x3 x", torch.float32, ("B", "C", "H", "W"))
     B, C, Hh, Ww = x.shape
-    out = torch.empty_like(x)
-    call("ldmae_conv3x3", ptr(_c(x)), ptr(_c(w)), ptr(b), ptr(out), B, C, Hh, Ww, stream())
+    w, b = _arg(w, "conv3x3 w", torch.float32, (C, C, 3, 3), like=x), _arg(b, "conv3x3 b", torch.float32, (C,), like=x)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    call("ldmae_conv3x3", ptr(x), ptr(w), ptr(b), ptr(out), B, C, Hh, Ww, stream())
     return out
 
 
 def conv3x3_bwd(dout, x, w, need_dx=True):
+    x = _arg(x, "conv3x3_bwd x", torch.float32, ("B", "C", "H", "W"))
     B, C, Hh, Ww = x.shape
-    dx = torch.empty_like(x) if need_dx else None
-    dw = torch.empty_like(w)
+    dout, w = _arg(dout, "conv3x3_bwd dout", torch.float32, x.shape, like=x), _arg(w, "conv3x3_bwd w", torch.float32, (C, C, 3, 3), like=x)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dx else None
+    dw = torch.empty(C, C, 3, 3, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
-    ws = workspace(L.load().ldmae_conv3x3_bwd_workspace_bytes(C), x.device, "conv")
-    call("ldmae_conv3x3_bwd", ptr(_c(dout)), ptr(_c(x)), ptr(_c(w)), ptr(dx), ptr(dw), ptr(db), B, C, Hh, Ww, ptr(ws), stream())
+    ws = workspace(_ws_bytes("ldmae_conv3x3_bwd_workspace_bytes", C), x.device, "conv")
+    call("ldmae_conv3x3_bwd", ptr(dout), ptr(x), ptr(w), ptr(dx), ptr(dw), ptr(db), B, C, Hh, Ww, ptr(ws), stream())
     return dx, dw, db
+
+
+def _mae_loss_args(pred_img, imgs, mask, p):
+    """What the two passes of the MAE loss share: imgs and pred_img [B, C, H, W] f32, mask [B, (H/p)*(W/p)] f32 (1 = masked)."""
+    imgs = _arg(imgs, "mae_loss imgs", torch.float32, ("B", "C", "H", "W"))
+    B, C, Hh, Ww = imgs.shape
+    if int(p) <= 0 or Hh % int(p) or Ww % int(p):
+        raise RuntimeError(f"mae_loss imgs: shape {tuple(imgs.shape)}, expected whole {p}-pixel patches")
+    pred_img = _arg(pred_img, "mae_loss pred_img", torch.float32, imgs.shape, like=imgs)
+    mask = _arg(mask, "mae_loss mask", torch.float32, (B, (Hh // int(p)) * (Ww // int(p))), like=imgs)
+    return pred_img, imgs, mask, B, C, Hh, Ww
 
 
 def mae_loss_fwd(pred_img, imgs, mask, p):
     """-> [2] f32 on the device: (sum over masked patches' pixels of (pred - img)^2, the same over visible patches)."""
-    B, C, Hh, Ww = imgs.shape
+    pred_img, imgs, mask, B, C, Hh, Ww = _mae_loss_args(pred_img, imgs, mask, p)
     G = L.load().ldmae_mae_loss_groups(imgs.numel())
     part = torch.empty(G, 2, dtype=torch.float32, device=imgs.device)
-    call("ldmae_mae_loss_fwd", ptr(_c(pred_img)), ptr(_c(imgs)), ptr(_c(mask)), ptr(part), B, C, Hh, Ww, int(p), stream())
+    call("ldmae_mae_loss_fwd", ptr(pred_img), ptr(imgs), ptr(mask), ptr(part), B, C, Hh, Ww, int(p), stream())
     return part.sum(0)
 
 
 def mae_loss_bwd(pred_img, imgs, mask, coef, p):
-    B, C, Hh, Ww = imgs.shape
-    d = torch.empty_like(pred_img)
-    call("ldmae_mae_loss_bwd", ptr(_c(pred_img)), ptr(_c(imgs)), ptr(_c(mask)), ptr(_c(coef)), ptr(d), B, C, Hh, Ww, int(p), stream())
+    pred_img, imgs, mask, B, C, Hh, Ww = _mae_loss_args(pred_img, imgs, mask, p)
+    coef = _arg(coef, "mae_loss_bwd coef", torch.float32, (2,), like=imgs)
+    d = torch.empty(imgs.shape, dtype=torch.float32, device=imgs.device)
+    call("ldmae_mae_loss_bwd", ptr(pred_img), ptr(imgs), ptr(mask), ptr(coef), ptr(d), B, C, Hh, Ww, int(p), stream())
     return d
 
 
 def layernorm_fwd(x, w, b, out_dtype, eps=1e-6):
+    x = _arg(x, "layernorm_fwd x", torch.float32, ("M", "D"))
     M, D = x.shape
+    w, b = _arg(w, "layernorm_fwd w", torch.float32, (D,), like=x), _arg(b, "layernorm_fwd b", torch.float32, (D,), like=x)
     out = torch.empty(M, D, dtype=out_dtype, device=x.device)
     mean = torch.empty(M, dtype=torch.float32, device=x.device)
     rstd = torch.empty_like(mean)
@@ -1343,10 +1527,15 @@ def layernorm_fwd(x, w, b, out_dtype, eps=1e-6):
 
 def layernorm_bwd(dout, x, w, mean, rstd, dx_accum, cast=False):
     """dx_accum += dLN/dx; -> (dw, db), with cast=True (16-bit dout) also the updated dx_accum rounded to dout's type."""
+    x = _arg(x, "layernorm_bwd x", torch.float32, ("M", "D"))
     M, D = x.shape
+    dout = _arg(dout, "layernorm_bwd dout", _FLOATS, (M, D), like=x)
+    w = _arg(w, "layernorm_bwd w", torch.float32, (D,), like=x)
+    mean, rstd = _arg(mean, "layernorm_bwd mean", torch.float32, (M,), like=x), _arg(rstd, "layernorm_bwd rstd", torch.float32, (M,), like=x)
+    _arg(dx_accum, "layernorm_bwd dx_accum", torch.float32, (M, D), out=True, like=x)
     dw = torch.empty(D, dtype=torch.float32, device=x.device)
     db = torch.empty_like(dw)
-    ws = workspace(L.load().ldmae_layernorm_bwd_workspace_bytes(M, D), x.device)
+    ws = workspace(_ws_bytes("ldmae_layernorm_bwd_workspace_bytes", M, D), x.device)
     dxc = torch.empty(M, D, dtype=dout.dtype, device=x.device) if cast else None
     call("ldmae_layernorm_bwd_cast", dt(dout.dtype), ptr(dout), ptr(x), ptr(w), ptr(mean), ptr(rstd), ptr(dx_accum), ptr(dxc), ptr(dw), ptr(db), 0.0,
          M, D, ptr(ws), stream())
@@ -1354,21 +1543,26 @@ def layernorm_bwd(dout, x, w, mean, rstd, dx_accum, cast=False):
 
 
 def gelu_bwd(dout, pre):
-    dx = torch.empty_like(pre)
+    pre = _arg(pre, "gelu_bwd pre", _FLOATS)
+    dout = _arg(dout, "gelu_bwd dout", pre.dtype, pre.shape, like=pre)
+    dx = torch.empty(pre.shape, dtype=pre.dtype, device=pre.device)
     call("ldmae_gelu_bwd", dt(pre.dtype), ptr(dout), ptr(pre), ptr(dx), pre.numel(), stream())
     return dx
 
 
 def gelu_tanh_fwd(x):
     """nn.GELU(approximate="tanh") (the timm Mlp of a use_swiglu=False LightningDiT block, lightningdit.py:208,219-224)."""
-    out = torch.empty_like(x)
-    call("ldmae_gelu_tanh_fwd", dt(x.dtype), ptr(_c(x)), ptr(out), x.numel(), stream())
+    x = _arg(x, "gelu_tanh_fwd x", _F32_BF16)
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    call("ldmae_gelu_tanh_fwd", dt(x.dtype), ptr(x), ptr(out), x.numel(), stream())
     return out
 
 
 def gelu_tanh_bwd(dout, pre):
-    dx = torch.empty_like(pre)
-    call("ldmae_gelu_tanh_bwd", dt(pre.dtype), ptr(_c(dout)), ptr(pre), ptr(dx), pre.numel(), stream())
+    pre = _arg(pre, "gelu_tanh_bwd pre", _F32_BF16)
+    dout = _arg(dout, "gelu_tanh_bwd dout", pre.dtype, pre.shape, like=pre)
+    dx = torch.empty(pre.shape, dtype=pre.dtype, device=pre.device)
+    call("ldmae_gelu_tanh_bwd", dt(pre.dtype), ptr(dout), ptr(pre), ptr(dx), pre.numel(), stream())
     return dx
 
 
@@ -1438,7 +1632,7 @@ def kid_sums(a, b, idx_a, idx_b, gamma, coef0=1.0, nsplit=None):
     ia, ib = ia.to(a.device), ib.to(a.device)
     _arg(ia, "kid_sums idx_a", torch.int32, (S, m), copy=False, like=a)
     _arg(ib, "kid_sums idx_b", torch.int32, (S, m), copy=False, like=a)
-    nbytes = L.load().ldmae_kid_workspace_bytes(S, m)
+    nbytes = _ws_bytes("ldmae_kid_workspace_bytes", S, m)
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=a.device)
     out = torch.empty(S, 3, dtype=torch.float64, device=a.device)
     call("ldmae_kid_sums", ptr(a), Na, ptr(b), Nb, D, ptr(ia), ptr(ib), S, m, float(gamma), float(coef0), nsplit, ptr(ws), ptr(out), stream())
@@ -1534,6 +1728,7 @@ def softmax_xent(logits, labels, num_classes=None, grad_scale=None, dlogits=None
         _arg(dlogits, "softmax_xent dlogits", torch.float32, (B, "W >= C"), rows=True, out=True, like=logits)
         if dlogits.shape[1] < C:
             raise RuntimeError(f"softmax_xent dlogits: {dlogits.shape[1]} columns for {C} classes")
+    labels = _device_labels(labels, C, logits, B, "softmax_xent labels")      # (idempotent: the device vector made above passes as it is)
     loss = torch.empty(B, dtype=torch.float32, device=logits.device)
     rank = torch.empty(B, dtype=torch.int32, device=logits.device)
     call("ldmae_softmax_xent", F32, ptr(logits), _ld(logits), ptr(labels), ptr(loss), ptr(dlogits), 0 if dlogits is None else max(_ld(dlogits), C),
@@ -1551,7 +1746,7 @@ def lars_norms(p, g, weight_decay=0.0, out=None):
         out = torch.empty(2, dtype=torch.float32, device=p.device)
     else:
         _arg(out, "lars_norms out", torch.float32, (2,), out=True, like=p)
-    nbytes = L.load().ldmae_lars_workspace_bytes(p.numel())
+    nbytes = _ws_bytes("ldmae_lars_workspace_bytes", p.numel())
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=p.device)
     call("ldmae_lars_norms", F32, ptr(p), ptr(g), p.numel(), float(weight_decay), ptr(ws), ptr(out), stream())
     return out
@@ -1800,7 +1995,7 @@ def adm_softmax_is(logits, split=5000):
     M, Cc = logits.shape
     if split < 1:
         raise RuntimeError(f"adm_softmax_is: split {split} (>= 1)")
-    ws = workspace(L.load().ldmae_adm_is_workspace_bytes(M, Cc, split), logits.device, "adm_is")
+    ws = workspace(_ws_bytes("ldmae_adm_is_workspace_bytes", M, Cc, split), logits.device, "adm_is")
     h = torch.empty(M, dtype=torch.float64, device=logits.device)
     S = torch.empty(-(-M // split), Cc, dtype=torch.float64, device=logits.device)
     call("ldmae_adm_softmax_is", ptr(logits), M, Cc, split, ptr(ws), ptr(h), ptr(S), stream())
@@ -1839,7 +2034,7 @@ def _lpips_tap(op, f, lin_w, f_dtype, align):
 def _lpips_layer(op, f, lin_w, out, f_dtype, align):
     lin_w, B, h, w, C = _lpips_tap(op, f, lin_w, f_dtype, align)
     _arg(out, op + " out", torch.float32, (B,), out=True, like=f)
-    ws = workspace(L.load().ldmae_lpips_workspace_bytes(B, h, w), f.device, "lpips")
+    ws = workspace(_ws_bytes("ldmae_lpips_workspace_bytes", B, h, w), f.device, "lpips")
     call("ldmae_" + op, ptr(f), ptr(lin_w), ptr(out), B, h, w, C, ptr(ws), stream())
     return out
 
@@ -1994,7 +2189,7 @@ def ssim(preds, target, lo=-1.0, hi=1.0, data_range=2.0):
     if H < 11 or W < 11:
         raise RuntimeError(f"ssim: {H} x {W} images are smaller than the 11 x 11 Gaussian window")
     out = torch.empty(B, dtype=torch.float32, device=preds.device)
-    ws = workspace(L.load().ldmae_ssim_workspace_bytes(B, C, H, W), preds.device, "ssim")
+    ws = workspace(_ws_bytes("ldmae_ssim_workspace_bytes", B, C, H, W), preds.device, "ssim")
     call("ldmae_ssim", ptr(preds), ptr(target), ptr(out), B, C, H, W, float(lo), float(hi), float(data_range), ptr(ws), stream())
     return out
 
@@ -2008,7 +2203,7 @@ def recon_quantize_sse(decoded, ref):
     dec8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device=decoded.device)
     ref8 = torch.empty_like(dec8)
     sse = torch.empty(B, dtype=torch.int64, device=decoded.device)
-    ws = workspace(L.load().ldmae_sse_workspace_bytes(B, H * W), decoded.device, "sse")
+    ws = workspace(_ws_bytes("ldmae_sse_workspace_bytes", B, H * W), decoded.device, "sse")
     call("ldmae_recon_quantize_psnr", ptr(decoded), ptr(ref), ptr(dec8), ptr(ref8), ptr(sse), B, H, W, ptr(ws), stream())
     return dec8, ref8, sse
 
@@ -2021,7 +2216,7 @@ def sse_u8(a, b):
     _arg(b, "sse_u8 b", torch.uint8, a.shape, copy=False, like=a)
     B, n = a.shape[0], a[0].numel()
     sse = torch.empty(B, dtype=torch.int64, device=a.device)
-    ws = workspace(L.load().ldmae_sse_workspace_bytes(B, n), a.device, "sse")
+    ws = workspace(_ws_bytes("ldmae_sse_workspace_bytes", B, n), a.device, "sse")
     call("ldmae_sse_u8", ptr(a), ptr(b), ptr(sse), B, n, ptr(ws), stream())
     return sse
 
