@@ -89,7 +89,8 @@ def load():
             fn.argtypes = args
         for kv in filter(None, os.environ.get("LDMAE_TUNE", "").split(",")):
             k, v = kv.split("=")
-            lib.ldmae_tune(int(k), int(v))
+            if lib.ldmae_tune(int(k), int(v)) != 0:
+                raise RuntimeError(f"LDMAE_TUNE={kv!r}: {lib.ldmae_last_error().decode()}")
     elif os.environ.get("LDMAE_TUNE"):
         raise RuntimeError("LDMAE_TUNE is set but the loaded library has no A/B knobs: point LDMAE_HIP_LIB at "
                            "ldmae_amd/libldmae_hip_diag.so (make -C ldmae_amd/csrc diag)")

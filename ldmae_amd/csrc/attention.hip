@@ -1,7 +1,6 @@
 // Attention for the LightningDiT and VMAE blocks on gfx950: the product kernels (16-bit flash forward, dQ, dK/dV; the f32 parity family)
 // and the C ABI.  The scheme (transposed scores, the dual-use LDS image) and the device helpers are in attention_common.h; the concluded
-// experiments (one-pass backward, fused head-dim-16 backward) live in probe/attn_onepass.hip and probe/attn_fused16.hip and are linked
-// into the diagnostic library only.
+// experiments (one-pass backward, fused head-dim-16 backward) are retired: tools/README.md, "Retired experiments".
 #include "attention_common.h"
 
 // ================================================================================================ forward, bf16
@@ -1067,14 +1066,6 @@ static int attention_bwd_core(int dtype, const void* q, const void* k, const voi
   // delta = [2][B*H*NP] f32 workspace, NP = N rounded up to 64 (bf16: -delta | -lse*log2e, rows padded to whole tiles; f32: slot 0 = delta, unpadded)
   const long items = (long)B * N * H, rcs = (long)B * H * ((N + 63) / 64 * 64);
   const unsigned dgrid = (unsigned)((items * 8 + 255) / 256 < 8192 ? (items * 8 + 255) / 256 : 8192);
-#ifdef LDMAE_DIAG
-  // tune key 21 = 1 (diagnostic build only): the VMAE heads on whole 256-token blocks in one kernel (probe/attn_fused16.hip); `delta` stays
-  // unused.  Built and 1.06x SLOWER than the pair (profiles/r05_attn16_onepass.txt).
-  if (ldmae_tune_get(21) == 1 && ldmae_launch_attn_fused16(dtype, q, k, v, o, do_, lse, dq, dk, dv, B, H, N, hd, scale, Lq, Lv, st)) {
-    LDMAE_CHECK_LAUNCH("attention_bwd(fused, head_dim 16)");
-    return LDMAE_OK;
-  }
-#endif
   // The 16-bit pair of head dim HD; R: the ragged instantiations (N % 64 != 0), F: fp16 operands / gradients, P: prefetch depth.
   // dQ first: it forms delta = rowsum(dO * O) from its own fragments and publishes it for the dK/dV kernel
   auto pair16 = [&](auto HD, auto R, auto F, auto P) {
@@ -1183,17 +1174,11 @@ extern "C" int ldmae_attention_bwd_pv(int dtype, const void* q, const void* k, c
 // ---- attention backward + QK-RMSNorm / RoPE backward in one (LightningDiT block, bf16): dq / dk never exist head-major; the packed dqkv
 // comes out complete (q | k through the norm / rope backward in the epilogues, v as attention_bwd_pv), with the norm-weight gradients
 // and the qkv bias gradient.  Replaces ldmae_attention_bwd_pv + ldmae_qknorm_rope_bwd for head dims 64 / 128.
-// the diagnostic build's one-pass kernel: its shapes (f32 dQ scratch [B*H][N][hd] at the end of the workspace)
-#ifdef LDMAE_DIAG
-static bool attn_onepass_shape(int N, int hd) { return hd == 64 && N % 128 == 0; }
-#else
-static constexpr bool attn_onepass_shape(int, int) { return false; }
-#endif
 extern "C" long ldmae_attention_bwd_pv_qknorm_workspace_bytes(int B, int H, int N, int hd) {
   const long blk = (long)B * ((N + 127) / 128);
   const long cw = ldmae_colsum_workspace_bytes((int)(blk * H), 2 * hd), cb = ldmae_colsum_workspace_bytes((int)blk, 3 * H * hd);
   const long cmax = ((cw > cb ? cw : cb) + 15) / 16 * 16;
-  return (2L * B * H * N + blk * H * 2 * hd + blk * 3 * H * hd + 2L * hd) * 4 + cmax + (attn_onepass_shape(N, hd) ? 4L * B * H * N * hd : 0);
+  return (2L * B * H * N + blk * H * 2 * hd + blk * 3 * H * hd + 2L * hd) * 4 + cmax;
 }
 extern "C" int ldmae_attention_bwd_pv_qknorm(int dtype, const void* q, const void* k, const void* qkv, const void* o, const void* do_,
                                              const float* lse, const float* wq, const float* wk, const float* cos, const float* sin, float eps,
@@ -1217,28 +1202,19 @@ extern "C" int ldmae_attention_bwd_pv_qknorm(int dtype, const void* q, const voi
   const unsigned grid = (unsigned)B * H * ((N + 127) / 128);
   const bf16* v = (const bf16*)qkv + 2 * hw;
   bf16* dv = (bf16*)dqkv + 2 * hw;
-  bool onepass = false;
-#ifdef LDMAE_DIAG
-  // tune key 17 = 1 (diagnostic build only): one pass over the scores instead of the dQ + dK/dV pair (probe/attn_onepass.hip; its f32 dQ
-  // scratch lies behind the column-sum workspace).  Built and 1.4x SLOWER (profiles/r04_attn_onepass_ab.txt).
-  const long cw = ldmae_colsum_workspace_bytes((int)(blk * H), 2 * hd), cb = ldmae_colsum_workspace_bytes((int)blk, 3 * H * hd);
-  onepass = attn_onepass_shape(N, hd) && ldmae_tune_get(17) == 1 &&
-            ldmae_launch_attn_onepass(q, k, v, o, do_, lse, rowc, dv, (float*)((char*)cws + ((cw > cb ? cw : cb) + 15) / 16 * 16), B, H, N, hd, scale, hm, pk, qn, st);
-#endif
-  if (!onepass) {                // dQ first, as in attention_bwd_core; whole tiles only (N % 64 == 0, above)
-    auto fused = [&](auto HD) {
-      constexpr int hd_ = decltype(HD)::value;
-      attn_pf_dispatch<hd_, 2>(attn_pf_depth(24, hd_), [&](auto P) {
-        attn_launch(attn_bwd_dq_bf16_kernel<hd_, true, false, false, decltype(P)::value>, grid, attn_lds(hd_, 0), st, q, k, v, o, do_, lse, rowc, items, nullptr, H, N,
-                    scale, hm, pk, qn);
-      });
-      attn_pf_dispatch<hd_, 2>(attn_pf_depth(23, hd_), [&](auto P) {
-        attn_launch(attn_bwd_dkdv_bf16_kernel<hd_, true, false, false, decltype(P)::value>, grid, attn_lds(hd_, 1024), st, q, k, v, do_, rowc, items, nullptr, dv, H, N,
-                    scale, hm, pk, qn);
-      });
-    };
-    if (hd == 64) fused(IC<64>{}); else fused(IC<128>{});
-  }
+  // dQ first, as in attention_bwd_core; whole tiles only (N % 64 == 0, above)
+  auto fused = [&](auto HD) {
+    constexpr int hd_ = decltype(HD)::value;
+    attn_pf_dispatch<hd_, 2>(attn_pf_depth(24, hd_), [&](auto P) {
+      attn_launch(attn_bwd_dq_bf16_kernel<hd_, true, false, false, decltype(P)::value>, grid, attn_lds(hd_, 0), st, q, k, v, o, do_, lse, rowc, items, nullptr, H, N,
+                  scale, hm, pk, qn);
+    });
+    attn_pf_dispatch<hd_, 2>(attn_pf_depth(23, hd_), [&](auto P) {
+      attn_launch(attn_bwd_dkdv_bf16_kernel<hd_, true, false, false, decltype(P)::value>, grid, attn_lds(hd_, 1024), st, q, k, v, do_, rowc, items, nullptr, dv, H, N,
+                  scale, hm, pk, qn);
+    });
+  };
+  if (hd == 64) fused(IC<64>{}); else fused(IC<128>{});
   LDMAE_CHECK_LAUNCH("attention_bwd_pv_qknorm");
   if (!wq) {}                   // RoPE only: no norm-weight gradients
   else if (dwk == dwq + hd) {        // the caller keeps dwq | dwk adjacent: reduce straight into them

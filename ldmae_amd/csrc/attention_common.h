@@ -21,8 +21,7 @@
 // f32 path (parity contract): same structure on mfma_f32_32x32x2f32 with padded f32 LDS tiles.
 //
 // This header: the device helpers every 16-bit attention kernel uses (the dual-use LDS image, tile staging, register fragments, the
-// row-store and fused QK-norm / RoPE backward epilogues).  Included by attention.hip (the product kernels and the C ABI) and by the
-// diagnostic build's experiments, probe/attn_onepass.hip and probe/attn_fused16.hip.
+// row-store and fused QK-norm / RoPE backward epilogues).  Included by attention.hip (the product kernels and the C ABI).
 #pragma once
 #include "common.h"
 
@@ -437,15 +436,3 @@ static inline void attn_launch(void (*kernel)(P...), unsigned grid, size_t lds, 
   hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(THREADS), lds, st, (P)args...);
 }
-
-#ifdef LDMAE_DIAG
-// probe/attn_fused16.hip (diagnostic build, tune key 21 = 1): the 16-bit head-dim-16 backward on whole 256-token blocks in one kernel, one
-// workgroup per (batch, head).  Returns 0 when the shape is outside what it covers (the caller then runs the dQ + dK/dV pair).
-int ldmae_launch_attn_fused16(int dtype, const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, void* dq,
-                              void* dk, void* dv, int B, int H, int N, int hd, float scale, QkvLayout Lq, QkvLayout Lv, hipStream_t st);
-// probe/attn_onepass.hip (diagnostic build, tune key 17 = 1): the fused QK-norm backward at head dim 64, N % 128 == 0, in one pass over the
-// scores (rowc kernel, main kernel, dQ finish).  dq_scratch: f32 [B*H][N][64].  Returns 0 when the shape is outside what it covers.
-int ldmae_launch_attn_onepass(const void* q, const void* k, const void* v, const void* o, const void* do_, const float* lse, float* rowc, void* dv,
-                              float* dq_scratch, int B, int H, int N, int hd, float scale, QkvLayout Lq, QkvLayout Lv, const struct QkNormBwd& qn,
-                              hipStream_t st);
-#endif

@@ -81,11 +81,32 @@ extern "C" int ldmae_launch_counts(long* counts, int n, int reset) {
 
 #ifdef LDMAE_DIAG
 // ---------------------------------------------------------------- tuning knobs (kernel variant selection; not part of the reference seam)
+// The live keys: each steers code the product library contains, or is the instrument behind a kept tool.  Every other key -- retired
+// (tools/README.md, "Retired experiments") or never assigned -- is refused: a key that nothing reads would silently be the shipped path.
+static constexpr int LIVE_KEYS[] = {
+    1,    // 1 = the 128 x 128 TN kernel for every bf16 shape
+    5,    // start delay of every other workgroup of gemm_nt_persist_kernel (units of 8128 clocks)
+    7,    // 1 = the per-K-step stamp build of gemm_nt_persist_kernel (tools/gemm_timeline.py)
+    8,    // NT launch mode: 2 = one tile per workgroup for every call
+    9,    // TN split target (workgroups per launch)
+    10,   // grid cap of the row kernels
+    11,   // launch-gap probes: 1 = empty kernel, 2 = the real kernel with ntiles = 0 (tools/gap_probe.py)
+    16,   // column-group tile walk of gemm_nt_persist_kernel (column tiles per group)
+    19,   // 1 = the half-line NT kernel where the whole-line one is the default
+    23,   // operand-fragment prefetch depth of the fused attention backward's dK/dV kernel (1 / 2 = that depth, 3 = none)
+    24,   // the same for its dQ kernel
+    25,   // the same for the plain dQ + dK/dV pair (1 = depth 1, 3 = none)
+};
 static int g_tune[32] = {0};
+static bool tune_key_live(int key) {
+  for (int k : LIVE_KEYS)
+    if (k == key) return true;
+  return false;
+}
 int ldmae_tune_get(int key) { return (key >= 0 && key < 32) ? g_tune[key] : 0; }
 extern "C" int ldmae_tune_query(int key) { return ldmae_tune_get(key); }
 extern "C" int ldmae_tune(int key, int value) {
-  if (key < 0 || key >= 32) LDMAE_FAIL(LDMAE_ERR_INVALID, "tune: key %d out of range", key);
+  if (!tune_key_live(key)) LDMAE_FAIL(LDMAE_ERR_INVALID, "tune: key %d is not a live tune key (retired or never assigned)", key);
   g_tune[key] = value;
   return LDMAE_OK;
 }

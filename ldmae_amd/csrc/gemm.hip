@@ -42,12 +42,14 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(const bf16* __rest
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const unsigned tiles_n = (N + BN - 1) / BN;
-  // LDS map.  3-deep ring: the epilogue strips behind the ring (96 KiB ..), the SwiGLU-bwd column-sum scratch `ex` (1024 floats per wave) on
-  // ring stage 2, which is free during an epilogue (the prologue of the next tile fills stages 0 and 1 only).  4-deep ring (128 KiB): the
-  // strips (34 KiB) are ALIASED onto stages 2 and 3 -- free during an epilogue for the same reason: stage 2 of the next tile is requested
-  // behind the tile-start barrier, which every wave reaches after its epilogue -- and `ex` sits behind the ring (.. 160 KiB).
-  float* ew = (float*)(smem + (STAGES == 3 ? 3 : 2) * STAGE_BYTES) + wave * (16 * 68);
-  float* ex = (float*)(smem + (STAGES == 3 ? 2 : 4) * STAGE_BYTES) + wave * 1024;
+  // 3-deep ring only.  A 4-deep one (128 KiB, strips aliased onto it) measured neutral (profiles/r04_ring4_ab.txt: block total 8.158 -> 8.118 ms):
+  // the L2 read latency seen by the CU is ~360 cycles (TCP_TCC_READ_REQ_LATENCY / READ_REQ, profiles/r04_pmc_ta.md), far inside what two
+  // stages in flight cover.
+  static_assert(STAGES == 3, "the LDS map and the wait accounting below are written for the 3-deep ring");
+  // LDS map:the epilogue strips behind the ring (96 KiB ..), the SwiGLU-bwd column-sum scratch `ex` (1024 floats per wave) on
+  // ring stage 2, which is free during an epilogue (the prologue of the next tile fills stages 0 and 1 only).
+  float* ew = (float*)(smem + 3 * STAGE_BYTES) + wave * (16 * 68);
+  float* ex = (float*)(smem + 2 * STAGE_BYTES) + wave * 1024;
   static_assert(STAGE_BYTES >= 8 * 1024 * 4, "epilogue scratch does not fit a ring stage");
   // workgroup b sits on XCD b % 8 (256 workgroups, one per CU): give each XCD a contiguous run of 32 tiles per round so the
   // workgroups that share an A row-block (and the whole of B) share an L2
@@ -101,16 +103,14 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(const bf16* __rest
   const int a_off = (wm * TM + (lane & 15)) * 64 + fpos, b_off = (BM + wn * TNn + (lane & 15)) * 64 + fpos;
   const int nk = K / 32;
   const bool grpB = wm >= WM / 2;
-  static_assert(STAGES == 3 || STAGES == 4, "wait accounting below is written for a 3- or 4-deep ring");
   // own pieces of stage kt+1 landed; the stages requested after it (kt+2 .. kt+STAGES-1, as far as the tile has them) may stay in flight
   auto wait_next = [&](int kt, bool) {
     const int after = nk - kt - 2;                 // stages of this tile behind stage kt+1
     if (after >= STAGES - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * PPW) : "memory");
-    else if (STAGES == 4 && after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
     else if (after == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
 
-  constexpr int PRO = 2;            // K-steps put in flight ahead of a tile's epilogue (a 4-deep ring requests its third at the tile start)
+  constexpr int PRO = 2;            // K-steps put in flight ahead of a tile's epilogue
   int t = first;
   if (t < tend) {
     set_tile(t);
@@ -147,7 +147,6 @@ __global__ __launch_bounds__(512) void gemm_nt_persist_kernel(const bf16* __rest
     // have landed too, and the previous tile's stores are drained (~0.2 us per tile).
     __builtin_amdgcn_s_waitcnt(0x0F70);
     __builtin_amdgcn_s_barrier();
-    if constexpr (STAGES == 4) { if (PRO < nk) issue(PRO); }       // behind the barrier: every wave has left the strips that alias this stage
     if (grpB) __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < nk; ++kt) {
       tstamp(kt, 0);
@@ -382,7 +381,7 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const bf16* __restric
 
 // ------------------------------------------------------------------------------------------------
 // bf16 TN GEMM, ring-pipelined (the product kernel; the 128x128 one above is the fallback for M % 32 != 0): 256(n) x 256(k)
-// output tile, WNn x 4 waves (default 2 x 4: 128 x 64 per wave), 32 token rows per step, STAGES LDS buffers in flight across the
+// output tile, WNn x 4 waves (2 x 4: 128 x 64 per wave), 32 token rows per step, STAGES LDS buffers in flight across the
 // barriers (same protocol as gemm_nt_persist_kernel; STAG = the two wave groups run half a step apart).
 // Stage image: A rows then B rows, [32 m][256 cols] bf16 = 512-B rows; 16-B chunk ch of row r sits at
 // ch ^ sw(r), sw(r) = ((r&3)<<1) | (((r>>3)&1)<<3): the 32 lanes of a ds_read_b64_tr_b16 half hit 32 distinct
@@ -395,6 +394,7 @@ template <int STAGES, int WNn = 2, bool STAG = false, bool F16 = false>
 __global__ __launch_bounds__(WNn * 4 * 64) void gemm_tn_ring_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B, float* __restrict__ P,
                                                            float* __restrict__ Pb, int M, int N, int K, int lda, int ldb,
                                                            int rows_per_split) {
+  static_assert(STAGES == 4 && WNn == 2 && STAG, "written for the shipped form: 4-deep ring, 2 x 4 waves, staggered wave groups");
   constexpr int BNn = 256, BKk = 256, WKk = 4, NW = WNn * WKk, MI = 256 / WNn / 16, NI = 4, STEP = 32;
   constexpr int OP_BYTES = STEP * 512, STAGE_BYTES = 2 * OP_BYTES, PPW = (2 * OP_BYTES / 1024) / NW;   // 32 pieces over the waves
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -456,50 +456,19 @@ __global__ __launch_bounds__(WNn * 4 * 64) void gemm_tn_ring_kernel(const bf16* 
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s)
     if (s < nsteps) issue(s);
-  if constexpr (STAG) {
-    // two wave groups half a step apart (as in gemm_nt_persist_kernel): loads + transposed fragment reads of one group
-    // run beside the MFMAs of the other on every SIMD
-    const bool grpB = wn >= WNn / 2;
-    auto wait_next = [&](int st) {
-      const int ahead = min(STAGES - 2, nsteps - 2 - st);
-      if (ahead >= 2) { if constexpr (STAGES >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory"); }
-      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-      else if (ahead == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    wait_next(-1);
-    __builtin_amdgcn_s_barrier();
-    if (grpB) __builtin_amdgcn_s_barrier();
-    for (int st = 0; st < nsteps; ++st) {
-      if (st + STAGES - 1 < nsteps) issue(st + STAGES - 1);
-      const char* ta = smem + (st % STAGES) * STAGE_BYTES;
-      const char* tb = ta + OP_BYTES;
-      bf16x8 af[MI], bfr[NI];
-#pragma unroll
-      for (int j = 0; j < NI; ++j) bfr[j] = frag(tb, wk * 64 + j * 16);
-#pragma unroll
-      for (int i = 0; i < MI; ++i) af[i] = frag(ta, wn * (MI * 16) + i * 16);
-      if (grpB) wait_next(st);
-      __builtin_amdgcn_s_barrier();
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = mfma16<F16>(af[i], bfr[j], acc[i][j]);
-      if (want_bias) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i) accb[i] = mfma16<F16>(af[i], ones, accb[i]);
-      }
-      if (!grpB) wait_next(st);
-      __builtin_amdgcn_s_barrier();
-    }
-    if (!grpB) __builtin_amdgcn_s_barrier();
-  } else {
-  for (int st = 0; st < nsteps; ++st) {
-    const int ahead = min(STAGES - 2, nsteps - 1 - st);
-    if (ahead >= 3) { if constexpr (STAGES >= 5) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PPW) : "memory"); }
-    else if (ahead == 2) { if constexpr (STAGES >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory"); }
+  // two wave groups half a step apart (as in gemm_nt_persist_kernel): loads + transposed fragment reads of one group
+  // run beside the MFMAs of the other on every SIMD
+  const bool grpB = wn >= WNn / 2;
+  auto wait_next = [&](int st) {
+    const int ahead = min(STAGES - 2, nsteps - 2 - st);
+    if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
     else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    else if (ahead == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
+  wait_next(-1);
+  __builtin_amdgcn_s_barrier();
+  if (grpB) __builtin_amdgcn_s_barrier();
+  for (int st = 0; st < nsteps; ++st) {
     if (st + STAGES - 1 < nsteps) issue(st + STAGES - 1);
     const char* ta = smem + (st % STAGES) * STAGE_BYTES;
     const char* tb = ta + OP_BYTES;
@@ -508,7 +477,8 @@ __global__ __launch_bounds__(WNn * 4 * 64) void gemm_tn_ring_kernel(const bf16* 
     for (int j = 0; j < NI; ++j) bfr[j] = frag(tb, wk * 64 + j * 16);
 #pragma unroll
     for (int i = 0; i < MI; ++i) af[i] = frag(ta, wn * (MI * 16) + i * 16);
-    __builtin_amdgcn_s_setprio(1);
+    if (grpB) wait_next(st);
+    __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -517,9 +487,10 @@ __global__ __launch_bounds__(WNn * 4 * 64) void gemm_tn_ring_kernel(const bf16* 
 #pragma unroll
       for (int i = 0; i < MI; ++i) accb[i] = mfma16<F16>(af[i], ones, accb[i]);
     }
-    __builtin_amdgcn_s_setprio(0);
+    if (!grpB) wait_next(st);
+    __builtin_amdgcn_s_barrier();
   }
-  }
+  if (!grpB) __builtin_amdgcn_s_barrier();
   // ---- epilogue: f32 partial tile through a per-wave LDS tile for row-contiguous stores (8 waves at a time: 139 KiB)
   __syncthreads();
   constexpr int ELD = 68;
@@ -729,41 +700,9 @@ template <typename OutT>
 static bool nt_diag_route(int dtype, int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, const NtGrid& g,
                           hipStream_t st, const char*& what) {
   if (dtype != LDMAE_BF16) return false;
-  constexpr bool out16 = sizeof(OutT) == 2;
-  // tune key 0: 1 / 2 = the experimental kernels of probe/gemm_w4.hip
-  if (ldmae_tune_get(0) != 0 && (ldmae_tune_get(0) == 1 ? ldmae_launch_nt_w4(epi, out16, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)
-                                                         : ldmae_launch_nt_p8(epi, out16, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st))) {
-    what = "gemm_nt_w4";
-    return true;
-  }
-  // tune key 12 = 1: the fused epilogue's elementwise part runs inside the next tile's main loop (probe/gemm_nt_defer.hip).  Built, bitwise
-  // equal, and 5-9 % SLOWER than the fused epilogues (profiles/r04_defer_ab.txt).
-  if (out16 && g.pers && g.grid != g.ntiles && (epi == LDMAE_EPI_GATE_RES || epi == LDMAE_EPI_SWIGLU) && ldmae_tune_get(12) == 1 &&
-      ldmae_launch_nt_defer(epi, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
-    what = "gemm_nt_defer";
-    return true;
-  }
-  // tune key 15 = 1: whole-line ring DMA (probe/gemm_nt_wl.hip: 128-B LDS rows, pieces of 8 rows x 128 B).  Built, bitwise equal on every
-  // epilogue, 6.5 % SLOWER over the block's eight GEMMs (profiles/r04_wl_ab.txt): the CU's DMA path is limited in BYTES per cycle, not in
-  // line requests.
-  if (ldmae_tune_get(15) == 1 && out16 && M % 8 == 0 && N % 8 == 0 && M >= 8 && N >= 8 && K % 64 == 0 && lda % 64 == 0 && ldb % 64 == 0 &&
-      ((uintptr_t)A & 127) == 0 && ((uintptr_t)B & 127) == 0 && (epi != LDMAE_EPI_SWIGLU || N % 256 == 0) &&
-      ldmae_launch_nt_wl(epi, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
-    what = "gemm_nt_wl";
-    return true;
-  }
-  // The rest are forms of gemm_nt_persist_kernel (keys 14, 7 and 11 also switch the whole-line kernel off: launch_nt).
-  // tune key 14 = 1: 4-deep ring, 128 KiB, strips aliased onto it, the SwiGLU-bwd scratch behind it (160 KiB in all).  Measured neutral
-  // (profiles/r04_ring4_ab.txt: block total 8.158 -> 8.118 ms): the L2 read latency seen by the CU is ~360 cycles (TCP_TCC_READ_REQ_LATENCY /
-  // READ_REQ, profiles/r04_pmc_ta.md), far inside what two stages in flight cover.
-  if (ldmae_tune_get(14) == 1)
-    return persist_epi_dispatch<OutT>(epi, [&](auto E) {
-      constexpr int lds4 = 4 * 512 * 64 + (decltype(E)::value == LDMAE_EPI_SWIGLU_BWD ? 8 * 1024 * 4 : 0);
-      nt_launch(gemm_nt_persist_kernel<4, decltype(E)::value, OutT>, g.grid, 512, lds4, st, A, B, M, N, K, lda, ldb, e, g.ntiles, ldmae_tune_get(5),
-                g_nt_stamps);
-    });
   // tune key 7 = 1: the per-K-step stamp build (TL) of the bias and SwiGLU epilogues
   if (ldmae_tune_get(7) == 1) {
+    constexpr bool out16 = sizeof(OutT) == 2;
     auto tl = [&](auto E) {
       nt_launch(gemm_nt_persist_kernel<3, decltype(E)::value, OutT, true>, g.grid, 512, PERS_LDS, st, A, B, M, N, K, lda, ldb, e, g.ntiles,
                 ldmae_tune_get(5) | (ldmae_tune_get(16) << 16), g_nt_stamps);
@@ -802,9 +741,9 @@ static int launch_nt(int dtype, int epi, bool tile_launch, bool half_lines, cons
 #endif
   if (ok) {
   } else if (dtype == LDMAE_BF16 && !half_lines && ldmae_tune_get(19) == 0 && ldmae_tune_get(7) == 0 && ldmae_tune_get(11) == 0 &&
-             ldmae_tune_get(14) == 0 && ldmae_launch_nt_lines(epi, sizeof(OutT) == 2, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
+             ldmae_launch_nt_lines(epi, sizeof(OutT) == 2, A, B, M, N, K, lda, ldb, e, g.grid, g.ntiles, st)) {
     // bf16, whole-line form (gemm_nt_lines.hip): every shape whose rows start on 128-B lines.  LDMAE_EPI_HALF_LINES and the diagnostic tune
-    // keys 19, 7, 11 and 14 keep the half-line kernel below.
+    // keys 19, 7 and 11 keep the half-line kernel below.
     ok = true;
     what = "gemm_nt_lines";
   } else if (dtype == LDMAE_BF16) {
@@ -978,15 +917,10 @@ extern "C" int ldmae_gemm_tn(int dtype, const void* A, int lda, const void* B, i
   if (ring) {
     const unsigned grid = cdiv(N, 256) * cdiv(K, 256) * splits;
     float* pb = dbias ? Pb : nullptr;
-    // default: 8 waves (128x64 each), 4-deep ring, the two wave groups half a step apart (1115-1135 TF/s with the fused bias
-    // gradient vs 965-1030 for 16 lock-step waves); tune key 4 (diagnostic build): 3 = 16 lock-step waves, 4 = 16 staggered waves.
+    // 8 waves (128x64 each), 4-deep ring, the two wave groups half a step apart (1115-1135 TF/s with the fused bias
+    // gradient vs 965-1030 for 16 lock-step waves).
     // The bias-gradient MFMAs stay on the wk == 0 waves: spreading them over all waves (a wave-uniform switch on wk, or one
     // slot per K-tile workgroup) measured 8-15 % SLOWER -- every wave's MFMA phase is on the staggered loop's critical path.
-#ifdef LDMAE_DIAG
-    if (ldmae_tune_get(4) == 3) tn_ring_launch<4, false, false>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
-    else if (ldmae_tune_get(4) == 4) tn_ring_launch<4, true, false>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
-    else
-#endif
     if (half) tn_ring_launch<2, true, true>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
     else tn_ring_launch<2, true, false>(grid, st, A, B, P, pb, M, N, K, lda, ldb, rows);
   } else if (dtype == LDMAE_BF16) {

@@ -33,7 +33,7 @@ struct EpiArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Host side shared by every NT launcher (gemm.hip, gemm_nt_lines.hip, mx8.hip, probe/gemm_*.hip)
+// Host side shared by every NT launcher (gemm.hip, gemm_nt_lines.hip, mx8.hip)
 // ------------------------------------------------------------------------------------------------
 // Grid plan of the 256 x 256-tile kernels: one persistent workgroup per CU (`grid` = the CU count rounded down to whole XCDs), or one tile per
 // workgroup (`grid` = ntiles) -- when the caller asks for it (LDMAE_EPI_TILE_LAUNCH: a data-parallel caller while RCCL's collective kernels
@@ -75,24 +75,8 @@ int ldmae_launch_nt_lines(int epi, int out_bf16, const void* A, const void* B, i
 int ldmae_launch_nt_lines_f16(int epi, int out_f16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const struct EpiArgs& e,
                               int grid, int ntiles, hipStream_t st);
 
-#ifdef LDMAE_DIAG
-// probe/gemm_nt_defer.hip (diagnostic build): persistent bf16 NT kernel whose fused epilogue (gated residual / SwiGLU) runs inside the NEXT
-// tile's main loop.  Returns 0 when the shape or the arguments are outside what it covers.
-int ldmae_launch_nt_defer(int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles,
-                          hipStream_t st);
-// probe/gemm_nt_wl.hip (diagnostic build): the same tile with a whole-line ring DMA (128-B LDS rows); bf16 outputs, epilogues 0 / 1 / 4 / 5
-int ldmae_launch_nt_wl(int epi, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid, int ntiles,
-                       hipStream_t st);
-// probe/gemm_w4.hip (diagnostic build): experimental NT kernels; return 0 if they have no instantiation for `epi`
-int ldmae_launch_nt_w4(int epi, int out_bf16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid,
-                       int ntiles, hipStream_t st);
-int ldmae_launch_nt_p8(int epi, int out_bf16, const void* A, const void* B, int M, int N, int K, int lda, int ldb, const EpiArgs& e, int grid,
-                       int ntiles, hipStream_t st);
-#endif
-
 // The gated residual adds gate * y with y AS STORED in the activation type (the reference's autocast Linear returns bf16:
-// lightningdit.py:248-249); every kernel that forms it -- the fused epilogues here, the deferred units of gemm_nt_defer.hip --
-// uses this one definition, so they agree bit for bit.
+// lightningdit.py:248-249); every kernel that forms it uses this one definition, so they agree bit for bit.
 template <typename OutT> __device__ __forceinline__ float act_round(float y) { return to_f<OutT>(from_f<OutT>(y)); }
 template <typename OutT> __device__ __forceinline__ float4 act_round4(float4 y) {
   return make_float4(act_round<OutT>(y.x), act_round<OutT>(y.y), act_round<OutT>(y.z), act_round<OutT>(y.w));

@@ -4,7 +4,7 @@
 // ring-DMA piece is 16 rows x 64 B = sixteen HALF-line requests, and the other half of every line is asked for again one K-step later.  The
 // probe shows what that costs: with all 256 CUs loading, an XCD's L2 serves ~13 requests per clock whether they are 64 B or 128 B, so a CU
 // takes in 21-28 B/clk in half lines (1170-1450 cycles for the 32 KiB of a 256 x 256 x 32 K-step, against 1024 cycles of MFMA issue) and
-// 40-52 B/clk in whole lines.  Round 4's whole-line kernel (probe/gemm_nt_wl.hip) asked for whole lines but kept only ONE 64-KiB block in
+// 40-52 B/clk in whole lines.  Round 4's whole-line kernel (retired: tools/README.md) asked for whole lines but kept only ONE 64-KiB block in
 // flight behind full vmcnt(0) drains and lost what the request shape won.  Here:
 //   * LDS rows hold 64 k = one 128-B line; a piece = 8 rows x 128 B; a line is requested ONCE per tile.
 //   * The ring is five HALF-block slots of 32 KiB (the 256 A rows, or the 256 B rows, x 128 B): 160 KiB.  The issue stream is

@@ -1,5 +1,5 @@
-"""The GEMM routes of the diagnostic library (nt_diag_route and the tune keys of csrc/gemm.hip, csrc/probe/gemm_w4.hip, gemm_nt_defer.hip,
-gemm_nt_wl.hip), element by element, with the bounds of tests/gemm_check.py.
+"""The GEMM routes of the diagnostic library (nt_diag_route and the live tune keys of csrc/gemm.hip), element by element, with the bounds
+of tests/gemm_check.py.
 
 The product library holds none of this code, so the module starts ONE child Python process with LDMAE_HIP_LIB pointing at
 libldmae_hip_diag.so; the child runs every case of CASES and prints one result line per case, the tests below each look one up.  A case
@@ -8,27 +8,20 @@ with the case's keys set: NaN-padded Canvas operands and outputs, every element 
 rerun and the launch count -- all as in that module.  Where the source says a variant computes the same products in the same order
 (`bitwise`), every output must also equal the shipped kernel's bit for bit.  Every key is reset to 0 between cases.
 
-  whole-line -> half-line kernel (key 19), 4-deep ring (14), per-K-step stamp build (7, bias and SwiGLU only), probe/gemm_nt_wl.hip (15),
-      one tile per workgroup (8 = 2): M = 2056, N = 264, K = 192 -- nine row-blocks (persistent mapping, grid != ntiles), a ragged row tile
-      and a ragged column tile; bias and SwiGLU-backward (Hs = 264).  Bitwise.
+  whole-line -> half-line kernel (key 19), per-K-step stamp build (7, bias and SwiGLU only), one tile per workgroup (8 = 2):
+      M = 2056, N = 264, K = 192 -- nine row-blocks (persistent mapping, grid != ntiles), a ragged row tile and a ragged column tile;
+      bias and SwiGLU-backward (Hs = 264).  Bitwise.
   start delay (5) and column-group walk (16 = 2 at N = 512: two column tiles) act on gemm_nt_persist_kernel only, so these cases pass
       LDMAE_EPI_HALF_LINES in both runs.  Bitwise.
-  probe/gemm_nt_defer.hip (12): needs the persistent mapping, M, N % 256 == 0 and K / 32 >= 24 (gated residual: 2048 x 512 x 768,
-      rows_per_batch 256) or >= 16 (SwiGLU: 2048 x 512 x 512, ldc = N).  Bitwise.
-  probe/gemm_w4.hip (0 = 1: w4, 2: p8) on bias, gated residual and SwiGLU; the TN ring kernel with 16 waves (4 = 3 lock-step, 4 staggered),
-      the 128 x 128 TN kernel (1) and a split target of 8 (9) at M = 4096, N = 264, K = 264 with the bias gradient: other orders of
+  the 128 x 128 TN kernel (1) and a split target of 8 (9) at M = 4096, N = 264, K = 264 with the bias gradient: other orders of
       summation, so the per-element bound and the bitwise rerun only.
 
-That a case's key takes its route rests on READING the predicates of nt_diag_route and of the probe launchers against the shapes above
-(defer: grid != ntiles, K / 32 = 24 / 16, gate_ld = N + 12 a multiple of 4, rows_per_batch 256; wl: everything a multiple of 8 / 64,
-128-B aligned operands; ring4, stamps: any epilogue they list), not on the test: a launcher that refuses a shape falls through to the
-shipped kernel silently, with the same launch count, and then passes the bitwise comparison trivially.
+That a case's key takes its route rests on READING the predicates of nt_diag_route and launch_nt against the shapes above (stamps: the
+epilogues it lists), not on the test: a route that refuses a shape falls through to the shipped kernel silently, with the same launch
+count, and then passes the bitwise comparison trivially.  A key that nothing reads can no longer do so: ldmae_tune refuses every key
+outside the live set of core.hip (tests/test_host_api.py), and the child asserts that each ldmae_tune call succeeds.
 
-Not in the table: key 12 with key 13 = 1, 2, 3 -- the deferred kernel's timing-only ablations (no deferred work / loads only / no stores).
-The source calls their results wrong, and they are: measured before and after the commit that added this module, all six (three values
-on two shapes) leave the deferred output -- xout of the gated residual, hid of SwiGLU -- holding the canvas's NaN payload in every
-element (1048576 of 1048576 and 524288 of 524288 out of bound, worst |got - ref| / bound = inf).  Key 11 (launch-gap
-probes: an empty kernel, or ntiles = 0) gives wrong results by design and is never set.
+Key 11 (launch-gap probes: an empty kernel, or ntiles = 0) gives wrong results by design and is never set.
 """
 import json
 import os
@@ -61,27 +54,21 @@ def _case_table():
     def add(name, shape, keys, bitwise):
         cs.append(dict(name=f"{name}_{shape}", shape=shape, keys=keys, bitwise=bitwise))
 
-    for shape in ("gate", "swiglu"):
-        add("defer_key12", shape, [(12, 1)], True)
-    for name, key in (("wl_key15", 15), ("half_lines_key19", 19), ("ring4_key14", 14)):
-        for shape in ("bias", "swiglu_bwd"):
-            add(name, shape, [(key, 1)], True)
+    for shape in ("bias", "swiglu_bwd"):
+        add("half_lines_key19", shape, [(19, 1)], True)
     for shape in ("bias", "swiglu"):
         add("stamps_key7", shape, [(7, 1)], True)
     add("delay_key5", "bias_half", [(5, 3)], True)
     add("colgroup_key16", "gate_half", [(16, 2)], True)
     for shape in ("bias", "gate"):
         add("tile_launch_key8", shape, [(8, 2)], True)
-    for name, val in (("w4_key0", 1), ("p8_key0", 2)):
-        for shape in ("bias", "gate", "swiglu"):
-            add(name, shape, [(0, val)], False)
-    for name, keys in (("tn_16_waves_key4_3", [(4, 3)]), ("tn_16_waves_key4_4", [(4, 4)]), ("tn_128_key1", [(1, 1)]), ("tn_target_key9", [(9, 8)])):
+    for name, keys in (("tn_128_key1", [(1, 1)]), ("tn_target_key9", [(9, 8)])):
         add(name, "tn", keys, False)
     return cs
 
 
 CASES = _case_table()
-KEYS = (0, 1, 4, 5, 7, 8, 9, 12, 13, 14, 15, 16, 19)
+KEYS = (1, 5, 7, 8, 9, 16, 19)
 
 
 # ----------------------------------------------------------------------------- the child process
@@ -113,7 +100,7 @@ def _child():
                 defaults[c["shape"]] = run(c["shape"])
             res["default"] = defaults[c["shape"]][1]
             for k, v in c["keys"]:
-                lib.ldmae_tune(k, v)
+                assert lib.ldmae_tune(k, v) == 0, f"{c['name']}: {_lib.last_error()}"
             outs, res["variant"] = run(c["shape"])
             assert outs and outs.keys() == defaults[c["shape"]][0].keys(), f"{c['name']}: outputs {sorted(outs)} to compare with {sorted(defaults[c['shape']][0])}"
             if c["bitwise"]:

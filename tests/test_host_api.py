@@ -206,3 +206,20 @@ def test_signatures_carry_the_headers_types():
     assert C.c_void_p.from_param((C.c_float * 4)()) is not None and C.c_void_p.from_param(C.byref(C.c_double())) is not None
     assert _lib.DIAG_SIGNATURES == {"ldmae_tune": (C.c_int, [C.c_int, C.c_int]), "ldmae_tune_query": (C.c_int, [C.c_int]),
                                     "ldmae_debug_nt_stamps": (None, [C.c_void_p])}
+
+
+def test_diagnostic_library_refuses_every_dead_tune_key():
+    """ldmae_tune takes the live keys of csrc/core.hip and nothing else: a retired or never assigned key is an error that names the key,
+    not silently the shipped path (host code only: no GPU call)."""
+    path = os.path.join(ROOT, "ldmae_amd", "libldmae_hip_diag.so")
+    if not os.path.exists(path):
+        pytest.skip("libldmae_hip_diag.so is not built (make -C ldmae_amd/csrc diag)")
+    lib = ctypes.CDLL(path)
+    lib.ldmae_last_error.restype = ctypes.c_char_p
+    live = {1, 5, 7, 8, 9, 10, 11, 16, 19, 23, 24, 25}
+    for k in sorted(live):
+        assert lib.ldmae_tune(k, 0) == 0, (k, lib.ldmae_last_error())
+    for k in [-1, 32] + [k for k in range(32) if k not in live]:
+        assert lib.ldmae_tune(k, 1) < 0, f"dead key {k} was accepted"
+        assert re.search(rf"key {k}\b", lib.ldmae_last_error().decode()), (k, lib.ldmae_last_error())
+    assert all(lib.ldmae_tune_query(k) == 0 for k in range(-1, 33))

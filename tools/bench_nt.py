@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The eight bf16 NT GEMMs of one LightningDiT-B/1 block (bs=256: M = 262144 token rows) with their real epilogues, timed
-for each value of a tune key (default key 8: 1 = persistent workgroups, 2 = one tile per workgroup).
+for each value of a tune key (default key 8: 1 = persistent workgroups, 2 = one tile per workgroup).  A key outside the live set of
+csrc/core.hip is refused by the library and ends the run: it would time the shipped path twice.
     python tools/bench_nt.py [--key 8] [--values 1,2] [--rounds 3]"""
 import os, argparse, os, sys
 import torch
@@ -25,7 +26,6 @@ def main():
     ap.add_argument("--values", default="1,2")
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
-    lib = _lib.load()
     vals = [int(v) for v in args.values.split(",")] if args.key >= 0 else [0]
     M, D, H = 262144, 768, 2048
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -51,10 +51,10 @@ def main():
         for name, fl, fn in cases:
             for v in vals:
                 if args.key >= 0:
-                    lib.ldmae_tune(args.key, v)
+                    _lib.call("ldmae_tune", args.key, v)
                 res[(name, v)].append(timed(fn))
     if args.key >= 0:
-        lib.ldmae_tune(args.key, 0)
+        _lib.call("ldmae_tune", args.key, 0)
     tot = {v: 0.0 for v in vals}
     for name, fl, fn in cases:
         line = f"{name}:"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Launch a few GEMMs of one shape (for rocprofv3 --pmc runs).  python3 tools/one_gemm.py kind N K [variant]"""
+"""Launch a few GEMMs of one shape (for rocprofv3 --pmc runs).  python3 tools/one_gemm.py kind N K [nt launch mode]"""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,8 +8,8 @@ from ldmae_amd import _lib, ops
 kind, N, K = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 v = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 M = 262144
-if kind in ("nt", "tn"):
-    _lib.load().ldmae_tune(8 if kind == "nt" else 4, v)      # nt: 2 = one tile per workgroup; tn: 3 / 4 = 16-wave variants
+if kind == "nt":
+    _lib.call("ldmae_tune", 8, v)      # 2 = one tile per workgroup
 g = torch.Generator(device="cuda").manual_seed(0)
 if kind == "nt":
     a = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
