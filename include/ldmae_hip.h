@@ -769,6 +769,28 @@ int ldmae_row_mse(int a_dtype, const void* a, const float* u, float* loss, int B
 int ldmae_guidance_combine(int rule, int in_dtype, const void* pos, const void* neg, const float* x, const float* t, float* mom, float* out,
                            int B, int C, int HW, int k, float scale, float phi, float eta, float norm_threshold, float momentum, void* stream);
 
+/* ---- Dispersive Loss on one block's features (csrc/dispersive.hip, transport.Transport(dispersive=...)) ----
+ * Wang & He 2025, "Diffuse and Disperse: Image Generation with Representation Regularization", the InfoNCE-L2 variant.  z [B, K] f32 dense:
+ * the f32 residual stream after one block, flattened per sample (K = N D); tau > 0.
+ *     d_ij = ||z_i - z_j||^2                      (d_ii = 0)
+ *     e_ij = exp(-d_ij / (K tau))     r_i = sum_j e_ij     S = sum_i r_i      (diagonal included: S >= B)
+ *     L    = log S - 2 log B                      (= log mean_ij e_ij; B = 1: L = 0)
+ *     dL/dz = C z,  C_ij = 4 / (S K tau) (e_ij - delta_ij r_i)                (C symmetric, rows sum to zero: sum_i dL/dz_i = 0)
+ *   The largest exponent is 0, on the diagonal: no running maximum, no overflow.  When every off-diagonal e underflows, L = -log B and C = 0.
+ * dispersive_fwd: loss [1] f32 and C [B, B] f32.  G = z z^T on v_mfma_f32_32x32x2_f32 with exact f32 operands, only the 64 x 64 tiles on or above
+ *   the diagonal; K is cut into ldmae_dispersive_slabs(B, K) slabs, a block writes its partial tiles to the workspace and G is their sum in slab
+ *   order.  Within a slab G_ij is one f32 fma chain over k, the same order for every (i, j).  Then, in f64: d_ij = max(G_ii + G_jj - 2 G_ij, 0),
+ *   d_ii = 0 set, e = exp(-d / (K tau)) with K tau formed in f64 from the f32 tau; r_i: thread t of 256 adds j = t, t + 256, ... in order, then the
+ *   fixed-order block sum; S likewise over r; L = (float) log(S / B^2); C_ij = (float)(4 / (S K tau) (e_ij - delta_ij r_i)), bitwise symmetric.
+ *   No atomics: two calls give the same bits.  workspace: ldmae_dispersive_workspace_bytes(B, K) bytes, 16-byte aligned.
+ * dispersive_bwd: dz [B, K] = g * (C z), g = upstream gradient times the weight, by value: one f32 fma chain over j per element (on the same
+ *   MFMA, one writer per element), then one multiply by g.  dz overlaps neither input.
+ * 1 <= B <= 1024, K % 4 == 0, z and dz 16-byte aligned. */
+int ldmae_dispersive_slabs(int B, long K);
+long ldmae_dispersive_workspace_bytes(int B, long K);
+int ldmae_dispersive_fwd(const float* z, float* loss, float* C, int B, long K, float tau, void* workspace, void* stream);
+int ldmae_dispersive_bwd(const float* C, const float* z, float g, float* dz, int B, long K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

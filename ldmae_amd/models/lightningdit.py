@@ -490,7 +490,10 @@ class _DiTBlockFn(torch.autograd.Function):
         ctx.direct = bool(direct) and not input_only
         ctx.wparams = None if input_only else (qkvw, pw, w12, w3)
         ctx.sparams = (n1w, qkvb, qnw, knw, pb, n2w, b12, b3, qnb, knb) if ctx.direct else None      # in _BLOCK_SMALL's order
-        if chain is not None:
+        # the backward hand-off from the next member (_GradChain.norm_bwd) gates THIS block's dy2 from the next member's own dx; a block whose
+        # output has a second consumer (LightningDiT.tap_block: inplace is False) gets the sum of two gradients instead, possibly accumulated in
+        # place in that very buffer, so it is not registered: the next member takes its unfused norm backward and this block its own gate_bwd
+        if chain is not None and inplace:
             chain.up[idx] = (y2, mod)
         return xout.view(B, N, D)
 
@@ -920,6 +923,7 @@ class LightningDiT(nn.Module):
         self.final_layer = FinalLayer(hidden_size, patch_size, self.out_channels, use_rmsnorm=use_rmsnorm)
         self.precision = None          # None: follow torch.autocast; or torch.float32 / torch.bfloat16
         self._input_grad_only = False  # see input_grad_only()
+        self._tap, self.tapped = None, None      # see tap_block()
         self.gemm_precision = None     # see set_gemm_precision()
         self.initialize_weights()
 
@@ -975,6 +979,26 @@ class LightningDiT(nn.Module):
         finally:
             self._input_grad_only = was
 
+    @contextlib.contextmanager
+    def tap_block(self, i):
+        """Inside this context every forward keeps a reference to the output of block i (counted from 0) -- the f32 residual stream [B, N, D], with
+        its graph -- in `self.tapped`, for an objective that reads intermediate features (transport.Transport(dispersive=...)).  The output then
+        has two consumers, and ONLY block i changes: it works on a private copy of its incoming gradient (inplace off) and does not take the
+        backward hand-off from block i + 1 (_DiTBlockFn.forward has the reason); the chain, batched adaLN, direct parameter gradients and the
+        fused residual + norm passes of every block stay.  Off by default; refused with use_checkpoint (the recomputed block output is not the
+        tensor the caller holds) and with input_grad_only (no parameter gradient to regularise).  `tapped` is cleared on exit."""
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(self.blocks):
+            raise ValueError(f"ldmae_amd LightningDiT: tap_block index {i!r}, expected an integer in 0 .. {len(self.blocks) - 1}")
+        if self.use_checkpoint:
+            raise NotImplementedError("ldmae_amd LightningDiT: tap_block with use_checkpoint is not implemented")
+        if self._input_grad_only:
+            raise NotImplementedError("ldmae_amd LightningDiT: tap_block with input_grad_only is not implemented")
+        was, self._tap = self._tap, i
+        try:
+            yield self
+        finally:
+            self._tap, self.tapped = was, None
+
     def initialize_weights(self):
         """:340-374."""
         def _basic_init(module):
@@ -1021,6 +1045,9 @@ class LightningDiT(nn.Module):
         io = self._input_grad_only and torch.is_grad_enabled()
         if io and self.use_checkpoint:
             raise NotImplementedError("ldmae_amd LightningDiT: input_grad_only with use_checkpoint is not implemented (nothing to recompute for: no parameter gradients)")
+        tap = self._tap
+        if tap is not None and (self.use_checkpoint or io):
+            raise NotImplementedError(f"ldmae_amd LightningDiT: tap_block with {'use_checkpoint' if self.use_checkpoint else 'input_grad_only'} is not implemented")
         with torch.autocast(device_type="cuda", enabled=False):
             if io:                        # input_grad_only(): the conditioning does not depend on x -- no graph through it
                 x = self.x_embedder(x, self.pos_embed[0], input_only=True)
@@ -1063,7 +1090,9 @@ class LightningDiT(nn.Module):
                 if self.use_checkpoint:
                     x = checkpoint(block, x, c, self.feat_rope, sc, dtype, not hooked[i], use_reentrant=True)
                 else:
-                    x = block(x, c, self.feat_rope, sc, dtype, not hooked[i], chain, i, self.direct_param_grads and chain is not None and not io, mod_all, io)
+                    x = block(x, c, self.feat_rope, sc, dtype, not hooked[i] and i != tap, chain, i, self.direct_param_grads and chain is not None and not io, mod_all, io)
+                    if i == tap:
+                        self.tapped = x
             x = self.final_layer(x, c, sc, dtype, chain, len(self.blocks), io)
             x = self.unpatchify(x)
             if self.learn_sigma:

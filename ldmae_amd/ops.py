@@ -2511,3 +2511,8 @@ def sde_combine(ins, coef, out, noise_coef=0.0, z=None, seed=None, counter=0, me
     call("ldmae_sde_combine_f32", p[0], p[1], p[2], p[3], cf, m, ptr(z), float(noise_coef), mode, int(seed or 0) & (2 ** 64 - 1),
          int(counter) & (2 ** 64 - 1), ptr(out), ptr(mean_out), n, float(t_next), ptr(t_out), 0 if t_out is None else t_out.numel(), stream())
     return out
+
+
+# ----------------------------------------------------------------------------- Dispersive Loss (csrc/dispersive.hip)
+# ops.dispersive_fwd / ops.dispersive_bwd: written in dispersive.py on this module's argument checker (_arg), workspace and stream
+from .dispersive import dispersive_bwd, dispersive_fwd      # noqa: E402,F401

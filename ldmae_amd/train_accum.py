@@ -99,6 +99,20 @@ def posthoc_ema_config(tr_cfg, ckpt_dir):
     return tuple(check_sigma_rel(s) for s in sig), every, str(ph_cfg.get('dir') or f"{ckpt_dir}/ema_snapshots")
 
 
+def dispersive_config(cfg, depth, world=1):
+    """The optional ``train.dispersive: {weight: 0.5, tau: 0.5, block: <int>}`` (not a reference key; Wang & He 2025) as the checked option of
+    transport.dispersive_options, or None when the key is absent.  depth: the number of blocks of the model the configuration names; block,
+    counted from 0, defaults to depth // 4.  Refused here, before anything is trained: weight < 0, tau <= 0, a block outside the model, a
+    per-GPU batch of 1 and model.use_checkpoint."""
+    tr_cfg = cfg['train']
+    if tr_cfg.get('dispersive') is None:
+        return None
+    from ldmae_amd.transport.transport import dispersive_options
+    per_gpu = int(np.round(tr_cfg['global_batch_size'] / world))
+    return dispersive_options(tr_cfg['dispersive'], depth, per_gpu_batch=per_gpu, use_checkpoint=bool(cfg['model'].get('use_checkpoint', False)),
+                              where="train.dispersive")
+
+
 def make_loader(cfg, per_gpu, rank, world, synthetic):
     from torch.utils.data import DataLoader
     from torch.utils.data.distributed import DistributedSampler
@@ -148,6 +162,7 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
     precision = {"no": "fp32"}.get(precision, precision)
 
     model = build_model(cfg)
+    disp = dispersive_config(cfg, len(model.blocks), world)      # train.dispersive (opt-in, not a reference key): refused here if it cannot run
     if 'weight_init' in tr_cfg:
         ck = torch.load(tr_cfg['weight_init'], map_location='cpu')
         load_weights_with_shape_check(model, ck, rank)
@@ -175,7 +190,7 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
     opt.ema.copy_(opt.flat.params)                               # update_ema(ema, model, decay=0), train_accum.py:166
     t = cfg['transport']
     transport = create_transport(t['path_type'], t['prediction'], t['loss_weight'], t['train_eps'], t['sample_eps'],
-                                 use_cosine_loss=t.get('use_cosine_loss', False), use_lognorm=t.get('use_lognorm', False))
+                                 use_cosine_loss=t.get('use_cosine_loss', False), use_lognorm=t.get('use_lognorm', False), dispersive=disp)
     train_steps = 0
     if tr_cfg.get('resume', False):
         files = sorted(glob(f"{ckpt_dir}/*.pt"))                 # by step (the reference sorts by file size, :176)
@@ -214,6 +229,8 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
                 f"batch {per_gpu}/gpu x {world} gpus x {accum} accumulation; precision {precision}")
     max_steps = max_steps or tr_cfg['max_steps']
     running = torch.zeros((), device=device)
+    # the Dispersive Loss of THIS rank's micro-batch (no collective: its value depends on the per-GPU batch), logged as the mean over ranks
+    running_disp = torch.zeros((), device=device) if disp else None
     log_steps, micro, start = 0, 0, time()
     opt.zero_grad()
     epoch = 0
@@ -231,6 +248,9 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
             if 'cos_loss' in terms:
                 loss = loss + terms["cos_loss"].mean()
             running += terms["loss"].mean().detach()
+            if disp:
+                loss = loss + disp['weight'] * terms["disp_loss"]
+                running_disp += terms["disp_loss"].detach()
             # the slab accumulates the local micro-step gradients; ONE all-reduce on the last micro-step gives sum over ranks of
             # the local sums = what the reference's per-micro-step DDP mean accumulates to (train_accum.py:223-244), times world
             reducer.sync = micro + 1 == accum
@@ -254,7 +274,14 @@ def do_train(cfg, synthetic=False, max_steps=None, precision=None):
                 if world > 1:
                     dist.all_reduce(avg, op=dist.ReduceOp.SUM)
                 comm = f", exposed all-reduce {reducer.exposed_comm_ms() / max(log_steps, 1):.2f} ms/step (batched adaLN {'on' if model.batched_adaln else 'off'})" if world > 1 else ""
-                logger.info(f"(step={train_steps:07d}) Train Loss: {avg.item() / world:.4f}, Train Steps/Sec: {log_steps / (time() - start):.2f}{comm}")
+                dl = ""
+                if disp:
+                    davg = running_disp / (log_steps * accum)
+                    if world > 1:
+                        dist.all_reduce(davg, op=dist.ReduceOp.SUM)
+                    dl = f" Dispersive Loss: {davg.item() / world:.4f},"
+                    running_disp.zero_()
+                logger.info(f"(step={train_steps:07d}) Train Loss: {avg.item() / world:.4f},{dl} Train Steps/Sec: {log_steps / (time() - start):.2f}{comm}")
                 running.zero_()
                 log_steps, start = 0, time()
             at_ckpt = train_steps % tr_cfg['ckpt_every'] == 0 and train_steps > 0

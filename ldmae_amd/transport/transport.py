@@ -28,9 +28,63 @@ class WeightType(enum.Enum):
     LIKELIHOOD = enum.auto()
 
 
+class _DispersiveFn(th.autograd.Function):
+    """L = log mean_ij exp(-||z_i - z_j||^2 / (K tau)) of z [B, K] f32 (ops.dispersive_fwd; the contract is in include/ldmae_hip.h).  The forward
+    leaves C [B, B]; the backward is dz = g C z (ops.dispersive_bwd) with the upstream gradient g read on the host: it is the loss weight over
+    the accumulation steps, a number the driver already holds, and one scalar read per step where the tapped block's backward is about to
+    start anyway."""
+
+    @staticmethod
+    def forward(ctx, z, tau):
+        from .. import ops
+        loss, C = ops.dispersive_fwd(z, tau)
+        ctx.save_for_backward(z, C)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import ops
+        z, C = ctx.saved_tensors
+        return ops.dispersive_bwd(C, z, float(g)), None
+
+
+def dispersive_options(opt, depth, *, per_gpu_batch=None, use_checkpoint=False, where="dispersive"):
+    """The option {weight: 0.5, tau: 0.5, block: <int>} of the Dispersive Loss, checked -> {'weight', 'tau', 'block'}, or None for None.  block
+    (counted from 0) defaults to depth // 4.  Refused by name: an unknown key, weight < 0, tau <= 0, a block outside 0 .. depth - 1, a per-GPU
+    batch of 1 (the loss of a single sample is the constant 0) and use_checkpoint (LightningDiT.tap_block)."""
+    if opt is None:
+        return None
+    if not isinstance(opt, dict) or set(opt) - {"weight", "tau", "block"}:
+        raise ValueError(f"{where} must be a mapping with the keys weight, tau and block (all optional); got {opt!r}")
+
+    def number(key, default):
+        v = opt.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+            raise ValueError(f"{where}.{key} must be a finite number; got {v!r}")
+        return float(v)
+
+    weight, tau = number("weight", 0.5), number("tau", 0.5)
+    if weight < 0:
+        raise ValueError(f"{where}.weight must not be negative; got {weight!r}")
+    if tau <= 0:
+        raise ValueError(f"{where}.tau must be > 0; got {tau!r}")
+    block = opt.get("block", depth // 4)
+    if isinstance(block, bool) or not isinstance(block, int) or not 0 <= block < depth:
+        raise ValueError(f"{where}.block must be an integer in 0 .. {depth - 1} (depth {depth}, counted from 0); got {block!r}")
+    if per_gpu_batch is not None and per_gpu_batch < 2:
+        raise ValueError(f"{where} needs a per-GPU batch of at least 2 (the term is computed per rank and micro-batch; one sample has no pair); "
+                         f"got {per_gpu_batch}")
+    if use_checkpoint:
+        raise ValueError(f"{where} with model.use_checkpoint: true is not supported (LightningDiT.tap_block needs the block output of the forward)")
+    return {"weight": weight, "tau": tau, "block": block}
+
+
 class Transport:
     def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps, use_cosine_loss=False, use_lognorm=False,
-                 partitial_train=None, partial_ratio=1.0, shift_lg=False):
+                 partitial_train=None, partial_ratio=1.0, shift_lg=False, dispersive=None):
+        """dispersive (not a reference option): None, or {'tau': ..., 'block': ...} (and 'weight', which the driver applies): training_losses
+        then runs the model under LightningDiT.tap_block(block) and adds terms['disp_loss'], the Dispersive Loss of that block's output."""
+        self.dispersive = dispersive
         self.loss_type, self.model_type = loss_type, model_type
         if path_type != PathType.LINEAR or model_type != ModelType.VELOCITY:
             raise NotImplementedError("ldmae_amd Transport: linear path + velocity prediction only (SURVEY.md 2.1 #7)")
@@ -100,9 +154,21 @@ class Transport:
         model_kwargs = model_kwargs or {}
         t, x0, x1 = self.sample(x1, sp_timesteps, shifted_mu)
         t, xt, ut = self.path_sampler.plan(t, x0, x1)
-        out = model(xt, t, **model_kwargs)
+        if self.dispersive is None:
+            out = model(xt, t, **model_kwargs)
+            z = None
+        else:
+            owner = getattr(model, "__self__", model)                       # model may be a bound method
+            if not hasattr(owner, "tap_block"):
+                raise RuntimeError("ldmae_amd Transport: dispersive needs a model with tap_block (LightningDiT); got " + type(owner).__name__)
+            with owner.tap_block(self.dispersive['block']):
+                out = model(xt, t, **model_kwargs)
+                z = owner.tapped
         assert out.size() == xt.size()
         terms = {'pred': out}
+        if z is not None:                                                   # a scalar, on the f32 tap: outside the autocast region
+            with th.autocast(device_type="cuda", enabled=False):
+                terms['disp_loss'] = _DispersiveFn.apply(z.reshape(z.shape[0], -1), self.dispersive['tau'])
         terms['loss'] = mean_flat((out - ut) ** 2)
         if self.use_cosine_loss:
             terms['cos_loss'] = mean_flat(1 - th.nn.functional.cosine_similarity(out, ut, dim=1))
